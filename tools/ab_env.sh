@@ -2,7 +2,7 @@
 # usage: ab_env.sh "ENV1=a ENV2=b" "ENV1=c" ...   -- same-box A/B of bench.py under different environments (two rounds)
 for round in 1 2; do
   for envs in "$@"; do
-    out=$(env $envs python bench.py --no-cpu-baseline ${BENCH_ARGS:-} 2>/dev/null | tail -1)
+    out=$(env $envs python bench.py --full --no-cpu-baseline ${BENCH_ARGS:-} 2>/dev/null | tail -1)
     python - "$round" "$envs" "$out" <<'PY'
 import json, sys
 d = json.loads(sys.argv[3])

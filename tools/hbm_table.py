@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """HBM-bound kernels of the step: algorithmic bytes per launch / average duration from a rocprofv3 kernel-stats CSV of
-`MMHIP_OVERLAP=0 python bench.py --steps 5 --warmup 2 --no-cpu-baseline` (kernels one at a time).  hbm_table.py <kernel_stats.csv>"""
+`MMHIP_OVERLAP=0 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline` (kernels one at a time).  hbm_table.py <kernel_stats.csv>"""
 import csv, sys
 B, T, H, I, P, V = 64, 128, 768, 3072, 197, 250002
 Mt, Mv = B * T, B * P

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Aggregate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes (separate runs of `bench.py --steps 3 --warmup 1 --no-cpu-baseline`) into
+"""Aggregate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes (separate runs of `bench.py --full --steps 3 --warmup 1 --no-cpu-baseline`) into
 bytes per launch per kernel family.  rocprofv3 reports both in kilobytes; FETCH_SIZE is doubled (gfx950 tallies 128-B requests
 at 64 B, MI355X_MICROARCH.md "HBM").  The output carries the sha256 of the kernel sources it was collected on: bench.py uses
 the number only for a build of the same sources.   pmc_traffic.py <fetch.csv|dir> <write.csv|dir> [out.json]"""
@@ -56,7 +56,7 @@ def csrc_hash():
 
 
 f, w = per_kernel(sys.argv[1], "FETCH_SIZE"), per_kernel(sys.argv[2], "WRITE_SIZE")
-out = {"command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (separate passes) -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline",
+out = {"command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (separate passes) -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline",
        "fetch_correction": "x2 (gfx950 FETCH_SIZE tallies 128-B requests at 64 B)", "kernel": "gemm_nt (gemm_nt_kernel + gemm_nt8_kernel)",
        "csrc_sha256_16": csrc_hash(), "dtype": "bf16"}
 for k in f:
