@@ -367,7 +367,7 @@ int mmhip_op_attn_bwd(int dtype, const void* qkv, const float* maskbias, const v
 int mmhip_op_colsum(int dtype, const void* x, int rows, int cols, int ld, float* out, void* stream);
 int mmhip_op_cast(int dtype, const float* src, void* dst, uint64_t n, int transpose_rows, int transpose_cols, void* stream);
 /* hardware-layout probe: runs one MFMA of each shape and one transposing LDS read on index-coded data and writes what
- * each lane received (tests/test_hw_layouts.py checks the lane maps every kernel here is built on). out: int32[4096] */
+ * each lane received (tests/test_gpu_ops.py::test_hw_layouts checks the lane maps every kernel here is built on). out: int32[4096] */
 int mmhip_op_probe_layouts(int32_t* out, void* stream);
 
 /* ==== early-fusion engine (BASELINE config 5): the LXMERT step of the reference's models/mm_early.py as ONE native call path (round 4;

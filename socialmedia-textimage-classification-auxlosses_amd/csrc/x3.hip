@@ -603,9 +603,170 @@ __global__ __launch_bounds__(256) void attn_bwd_f32_kernel(AttnBwdArgs a) {
     }
 }
 
+// The same two kernels for sequences whose rows do not fit the LDS forms above (forward: S > 317 -- K, V and the key bias of a head are 516 S bytes of the 160 KB --, backward: S > 128): the rows of Q, K, V and dO
+// are read where they lie (global memory; a head's rows stay in L2), only the per-row scalars (key bias, lse, D) go to LDS.  Same arithmetic in the
+// same order, thread <-> (role, key) / query by a strided loop instead of tid.  Slow and rare: an unaligned tensor or a forward past 768 tokens,
+// the backward of more than 128 tokens (no engine path takes either).
+__global__ __launch_bounds__(256) void attn_fwd_f32_long_kernel(AttnArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int S = a.S, head = blockIdx.x, post = blockIdx.y, tid = threadIdx.x;
+    float* mb = sm;                        // [Sk]
+    const int Sq = a.Sq_live > 0 ? a.Sq_live : S, Sk = a.Sk_live > 0 ? a.Sk_live : S;
+    const int qr = a.q_rps > 0 ? a.q_rps : S, kr = a.kv_rps > 0 ? a.kv_rps : S, cr = a.ctx_rps > 0 ? a.ctx_rps : S;
+    const float* base = (const float*)a.qkv + (size_t)post * qr * a.ld_qkv + head * HD;
+    const float* Kg = (const float*)a.qkv + (size_t)post * kr * a.ld_qkv + a.hidden + head * HD;
+    const float* Vg = Kg + a.hidden;
+    const size_t ld = (size_t)a.ld_qkv;
+    for (int k = tid; k < Sk; k += 256) mb[k] = a.maskbias ? a.maskbias[(size_t)post * S + k] : 0.f;
+    __syncthreads();
+    const int qlim = a.q_tiles > 0 ? min(Sq, a.q_tiles * 32) : Sq;
+    const bool dropping = a.drop.thresh16 != 0;
+    for (int q = tid; q < qlim; q += 256) {
+        float qv[HD];
+#pragma unroll
+        for (int d = 0; d < HD; d += 4) {
+            const f32x4 x = *reinterpret_cast<const f32x4*>(base + (size_t)q * ld + d);
+            qv[d] = x[0]; qv[d + 1] = x[1]; qv[d + 2] = x[2]; qv[d + 3] = x[3];
+        }
+        float mx = -INFINITY;
+        for (int key = 0; key < Sk; ++key) mx = fmaxf(mx, dot64(qv, Kg + key * ld) * a.scale + mb[key]);
+        const float msafe = (mx == -INFINITY) ? 0.f : mx;
+        float o[HD];
+#pragma unroll
+        for (int d = 0; d < HD; ++d) o[d] = 0.f;
+        float l = 0.f;
+        const uint32_t ebase = (uint32_t)(((size_t)post * a.heads + head) * S + (uint32_t)q) * (uint32_t)S;
+        for (int key = 0; key < Sk; ++key) {
+            const float p = __expf(dot64(qv, Kg + key * ld) * a.scale + mb[key] - msafe);
+            l += p;
+            float pd = p;
+            if (dropping) pd = mm_keep(ebase + (uint32_t)key, a.drop) ? p * a.drop.keep_scale : 0.f;
+            const float* vr = Vg + key * ld;
+#pragma unroll
+            for (int d = 0; d < HD; d += 4) {
+                const f32x4 vv = *reinterpret_cast<const f32x4*>(vr + d);
+                o[d] = fmaf(pd, vv[0], o[d]); o[d + 1] = fmaf(pd, vv[1], o[d + 1]); o[d + 2] = fmaf(pd, vv[2], o[d + 2]); o[d + 3] = fmaf(pd, vv[3], o[d + 3]);
+            }
+        }
+        if (a.lse) a.lse[((size_t)post * a.heads + head) * S + q] = msafe + __logf(l);
+        const float inv = 1.0f / l;
+        float* op = (float*)a.ctx + ((size_t)post * cr + q) * a.ld_ctx + head * HD;
+#pragma unroll
+        for (int d = 0; d < HD; d += 4) *reinterpret_cast<f32x4*>(op + d) = f32x4{o[d] * inv, o[d + 1] * inv, o[d + 2] * inv, o[d + 3] * inv};
+    }
+}
+
+__global__ __launch_bounds__(256) void attn_bwd_f32_long_kernel(AttnBwdArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int S = a.S, head = blockIdx.x, post = blockIdx.y, tid = threadIdx.x;
+    float* lse = sm;                       // [S] each
+    float* Dv = lse + S;
+    float* mb = Dv + S;
+    const int Sq = a.Sq_live > 0 ? a.Sq_live : S, Sk = a.Sk_live > 0 ? a.Sk_live : S;
+    const size_t qrow0 = (size_t)post * (a.q_rps > 0 ? a.q_rps : S), krow0 = (size_t)post * (a.kv_rps > 0 ? a.kv_rps : S), crow0 = (size_t)post * (a.ctx_rps > 0 ? a.ctx_rps : S);
+    const float* Qg = (const float*)a.qkv + qrow0 * a.ld_qkv + head * HD;
+    const float* Kg = (const float*)a.qkv + krow0 * a.ld_qkv + a.hidden + head * HD;
+    const float* Vg = Kg + a.hidden;
+    const float* Gg = (const float*)a.dctx + crow0 * a.ld_ctx + head * HD;      // dO
+    const float* ob = (const float*)a.ctx + crow0 * a.ld_ctx + head * HD;
+    const size_t ld = (size_t)a.ld_qkv, ldc = (size_t)a.ld_ctx;
+    for (int k = tid; k < Sk; k += 256) mb[k] = a.maskbias ? a.maskbias[(size_t)post * S + k] : 0.f;
+    for (int q = tid; q < Sq; q += 256) {
+        float d = 0.f;
+#pragma unroll
+        for (int c = 0; c < HD; c += 4) {
+            const f32x4 o = *reinterpret_cast<const f32x4*>(ob + q * ldc + c), g = *reinterpret_cast<const f32x4*>(Gg + q * ldc + c);
+            d += o[0] * g[0] + o[1] * g[1] + o[2] * g[2] + o[3] * g[3];
+        }
+        Dv[q] = d;
+        lse[q] = a.lse[((size_t)post * a.heads + head) * S + q];
+    }
+    __syncthreads();
+    const int qlim = a.q_tiles > 0 ? min(Sq, a.q_tiles * 32) : Sq;
+    const bool dropping = a.drop.thresh16 != 0;
+    const uint32_t hbase = (uint32_t)(((size_t)post * a.heads + head) * S);
+    for (int item = tid; item < 2 * Sk; item += 256) {          // role 0: dK of a key, role 1: its dV
+        const int role = item >= Sk ? 1 : 0, key = item - role * Sk;
+        float kr[HD], acc[HD];
+#pragma unroll
+        for (int d = 0; d < HD; d += 4) {
+            const f32x4 x = *reinterpret_cast<const f32x4*>(Kg + key * ld + d);
+            kr[d] = x[0]; kr[d + 1] = x[1]; kr[d + 2] = x[2]; kr[d + 3] = x[3];
+            acc[d] = 0.f; acc[d + 1] = 0.f; acc[d + 2] = 0.f; acc[d + 3] = 0.f;
+        }
+        const float mbk = mb[key];
+        float* outp = (float*)a.dqkv + (krow0 + key) * a.ld_qkv + (role == 0 ? 1 : 2) * a.hidden + head * HD;
+        if (role == 0) {
+            float vr[HD];
+#pragma unroll
+            for (int d = 0; d < HD; d += 4) {
+                const f32x4 x = *reinterpret_cast<const f32x4*>(Vg + key * ld + d);
+                vr[d] = x[0]; vr[d + 1] = x[1]; vr[d + 2] = x[2]; vr[d + 3] = x[3];
+            }
+            for (int q = 0; q < qlim; ++q) {
+                const float* qr = Qg + q * ld;
+                const float p = __expf(dot64(kr, qr) * a.scale + mbk - lse[q]);
+                float dpd = dot64(vr, Gg + q * ldc);
+                if (dropping) dpd = mm_keep((hbase + (uint32_t)q) * (uint32_t)S + (uint32_t)key, a.drop) ? dpd * a.drop.keep_scale : 0.f;
+                const float ds = p * (dpd - Dv[q]) * a.scale;
+#pragma unroll
+                for (int d = 0; d < HD; d += 4) {
+                    const f32x4 x = *reinterpret_cast<const f32x4*>(qr + d);
+                    acc[d] = fmaf(ds, x[0], acc[d]); acc[d + 1] = fmaf(ds, x[1], acc[d + 1]); acc[d + 2] = fmaf(ds, x[2], acc[d + 2]); acc[d + 3] = fmaf(ds, x[3], acc[d + 3]);
+                }
+            }
+        } else {
+            for (int q = 0; q < qlim; ++q) {
+                float pd = __expf(dot64(kr, Qg + q * ld) * a.scale + mbk - lse[q]);
+                if (dropping) pd = mm_keep((hbase + (uint32_t)q) * (uint32_t)S + (uint32_t)key, a.drop) ? pd * a.drop.keep_scale : 0.f;
+                const float* gr = Gg + q * ldc;
+#pragma unroll
+                for (int d = 0; d < HD; d += 4) {
+                    const f32x4 x = *reinterpret_cast<const f32x4*>(gr + d);
+                    acc[d] = fmaf(pd, x[0], acc[d]); acc[d + 1] = fmaf(pd, x[1], acc[d + 1]); acc[d + 2] = fmaf(pd, x[2], acc[d + 2]); acc[d + 3] = fmaf(pd, x[3], acc[d + 3]);
+                }
+            }
+        }
+#pragma unroll
+        for (int d = 0; d < HD; d += 4) *reinterpret_cast<f32x4*>(outp + d) = f32x4{acc[d], acc[d + 1], acc[d + 2], acc[d + 3]};
+    }
+    for (int q = tid; q < qlim; q += 256) {       // dQ: thread = query
+        float qr[HD], gr[HD], acc[HD];
+#pragma unroll
+        for (int d = 0; d < HD; d += 4) {
+            const f32x4 x = *reinterpret_cast<const f32x4*>(Qg + q * ld + d), g = *reinterpret_cast<const f32x4*>(Gg + q * ldc + d);
+            qr[d] = x[0]; qr[d + 1] = x[1]; qr[d + 2] = x[2]; qr[d + 3] = x[3];
+            gr[d] = g[0]; gr[d + 1] = g[1]; gr[d + 2] = g[2]; gr[d + 3] = g[3];
+            acc[d] = 0.f; acc[d + 1] = 0.f; acc[d + 2] = 0.f; acc[d + 3] = 0.f;
+        }
+        const float lq = lse[q], dq = Dv[q];
+        for (int k = 0; k < Sk; ++k) {
+            const float* kr = Kg + k * ld;
+            const float p = __expf(dot64(qr, kr) * a.scale + mb[k] - lq);
+            float dpd = dot64(gr, Vg + k * ld);
+            if (dropping) dpd = mm_keep((hbase + (uint32_t)q) * (uint32_t)S + (uint32_t)k, a.drop) ? dpd * a.drop.keep_scale : 0.f;
+            const float ds = p * (dpd - dq) * a.scale;
+#pragma unroll
+            for (int d = 0; d < HD; d += 4) {
+                const f32x4 x = *reinterpret_cast<const f32x4*>(kr + d);
+                acc[d] = fmaf(ds, x[0], acc[d]); acc[d + 1] = fmaf(ds, x[1], acc[d + 1]); acc[d + 2] = fmaf(ds, x[2], acc[d + 2]); acc[d + 3] = fmaf(ds, x[3], acc[d + 3]);
+            }
+        }
+        float* outp = (float*)a.dqkv + (qrow0 + q) * a.ld_qkv + head * HD;
+#pragma unroll
+        for (int d = 0; d < HD; d += 4) *reinterpret_cast<f32x4*>(outp + d) = f32x4{acc[d], acc[d + 1], acc[d + 2], acc[d + 3]};
+    }
+}
+
+static constexpr int ATTN_F32_LONG_MAX_S = 4096;      // three rows of per-query scalars in the default 64 KB of LDS
+
 hipError_t launch_attn_fwd_f32(const AttnArgs& a, hipStream_t s) {
     const size_t lds = ((size_t)2 * a.S * HD + a.S) * 4;
-    if (a.ld_qkv % 4 || a.ld_ctx % 4 || lds > 160 * 1024) return hipErrorInvalidValue;
+    if (a.ld_qkv % 4 || a.ld_ctx % 4 || a.S > ATTN_F32_LONG_MAX_S) return hipErrorInvalidValue;
+    if (lds > 160 * 1024) {
+        hipLaunchKernelGGL(attn_fwd_f32_long_kernel, dim3(a.heads, a.posts), dim3(256), (size_t)a.S * 4, s, a);
+        return hipGetLastError();
+    }
     static size_t set = 0;
     if (lds > set) { (void)hipFuncSetAttribute((const void*)attn_fwd_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); set = 160 * 1024; }
     hipLaunchKernelGGL(attn_fwd_f32_kernel, dim3(a.heads, a.posts), dim3(256), lds, s, a);
@@ -613,7 +774,11 @@ hipError_t launch_attn_fwd_f32(const AttnArgs& a, hipStream_t s) {
 }
 hipError_t launch_attn_bwd_f32(const AttnBwdArgs& a, hipStream_t s) {
     const size_t lds = ((size_t)4 * a.S * HD + 3 * a.S) * 4;
-    if (a.ld_qkv % 4 || a.ld_ctx % 4 || a.S > 128) return hipErrorInvalidValue;
+    if (a.ld_qkv % 4 || a.ld_ctx % 4 || a.S > ATTN_F32_LONG_MAX_S) return hipErrorInvalidValue;
+    if (a.S > 128) {
+        hipLaunchKernelGGL(attn_bwd_f32_long_kernel, dim3(a.heads, a.posts), dim3(256), (size_t)3 * a.S * 4, s, a);
+        return hipGetLastError();
+    }
     static bool done = false;
     if (!done) { (void)hipFuncSetAttribute((const void*)attn_bwd_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); done = true; }
     hipLaunchKernelGGL(attn_bwd_f32_kernel, dim3(a.heads, a.posts), dim3(256), lds, s, a);

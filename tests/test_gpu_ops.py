@@ -1,6 +1,8 @@
 """-m gpu: every hand-written kernel, called through the C ABI, against a torch fp32 reference of the same op on the
 same (16-bit-rounded) inputs.  Tolerances: 16-bit outputs carry one rounding of the output type (bf16 2^-8, f16 2^-11
-relative) on top of fp32 accumulation-order noise; fp32 outputs only the latter."""
+relative) on top of fp32 accumulation-order noise; fp32 outputs only the latter.
+Per-element checks with derived bounds, the long / plane-pair attention forms, quick-GELU, mmhip_op_cast_group and the host-side rejects live in
+tests/test_gpu_ops_attention.py and tests/test_gpu_ops_blocks.py (bounds: tests/op_bounds.py, tests/test_op_bounds_cpu.py)."""
 import math
 
 import numpy as np
