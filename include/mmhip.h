@@ -366,6 +366,25 @@ int mmhip_op_attn_bwd(int dtype, const void* qkv, const float* maskbias, const v
                       void* dqkv, int posts, int S, int heads, float p_drop, uint64_t seed, uint32_t stream_id, void* stream);
 int mmhip_op_colsum(int dtype, const void* x, int rows, int cols, int ld, float* out, void* stream);
 int mmhip_op_cast(int dtype, const float* src, void* dst, uint64_t n, int transpose_rows, int transpose_cols, void* stream);
+/* Which kernel ran: what the GEMM launchers actually launched for the CALLING THREAD's most recent NT (which = 0: mmhip_op_gemm_nt and every NT product
+ * of a composite operator) or TN (which = 1: mmhip_op_gemm_tn / _group) launcher call.  Host-side record only: no device work, read-only, dispatch is not
+ * affected.  The launchers fall back silently (a forced tile whose width does not divide N, a deep-pipelined tile whose shape rules fail, operands that
+ * are not 16-byte aligned); a test that names a kernel asserts it here.  out receives 8 int32:
+ *   NT  out[0] family: 0 nothing launched, 1 generic (one thread per element), 2 tile kernel (gemm.hip), 3 deep-pipelined tile (gemm8.hip), 4 split-K + finish,
+ *              5 parity direct (128 x 128), 6 parity small (few rows, K over the waves), 7 parity scratch-split (operand planes copied, then the deep-pipelined
+ *              tile), 8 parity plane pairs through the deep-pipelined tile
+ *       out[1] tile code actually used -- the force_slow >> 4 codes: 1 = 128x128, 6 = 128x192, 9 = role-specialised 256x128, 10 = 128x96, 12 = role-specialised
+ *              256x96, 20 / 21 = 128x128 on a 4- / 3-deep ring, 13 / 15 = deep-pipelined 256x256 one-shot / persistent, 14 / 16 = 256x128, 17 / 18 = 256x192;
+ *              family 4: the number of K slices; families 1, 5, 6: 0
+ *       out[2] deep-pipelined tiles: epilogue class 0 plain (bias / dropout / residual), 1 GELU, 2 gelu', 3 any (run-time flags); -1 otherwise
+ *       out[3] 1 = the persistent loop ran more than one tile per workgroup;  out[4] workgroups, out[5] tiles, out[6] problems in the launch, out[7] 0
+ *   TN  out[0] family bits: 1 generic kernel, 2 tile kernel, 4 parity direct kernel, 8 parity scratch-split (through the tile kernel), 16 parity plane pairs
+ *       out[1] variant of the tile kernel actually used (1 .. 5: 128x128 2-stage, 128x128 4-stage, 256x128 3-stage, role-specialised 256x128, role-specialised
+ *              128x128; 3 / 4 fall back to 1 when an Nn is not a multiple of 256); 0 = tile kernel not used
+ *       out[2] problems on the tile kernel, out[3] problems on the generic kernel, out[4] launches of the tile kernel (a group flushes every
+ *              mmhip_tn_max_group() problems), out[5] problems on the parity direct kernel, out[6] parity scratch-split problems, out[7] 0 */
+int mmhip_op_last_gemm_path(int which, int32_t* out);
+int mmhip_tn_max_group(void);      /* problems per launch of the grouped TN tile kernel */
 /* hardware-layout probe: runs one MFMA of each shape and one transposing LDS read on index-coded data and writes what
  * each lane received (tests/test_gpu_ops.py::test_hw_layouts checks the lane maps every kernel here is built on). out: int32[4096] */
 int mmhip_op_probe_layouts(int32_t* out, void* stream);

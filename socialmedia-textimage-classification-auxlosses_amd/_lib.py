@@ -103,6 +103,8 @@ _SIGS = {
     "mmhip_op_gemm_nt": (I, [I, P, I, P, I, P, I, I, I, I, P, I, P, I, P, I, F, U64, U32, P, I, I, I, P]),
     "mmhip_op_gemm_tn": (I, [I, P, I, P, I, P, I, I, I, I, I, I, P, P]),
     "mmhip_op_gemm_tn_group": (I, [I, P, I, I, P]),
+    "mmhip_op_last_gemm_path": (I, [I, C.POINTER(C.c_int32)]),
+    "mmhip_tn_max_group": (I, []),
     "mmhip_op_cast_group": (I, [I, P, I, P]),
     "mmhip_op_self_att_block_fwd": (I, [I, P, P, P, P, P, P, P, P, F, I, I, I, F, F, U64, P, P, P, P, P, P, P, P]),
     "mmhip_op_cross_att_block_fwd": (I, [I, P, P, P, P, P, P, P, P, P, F, I, I, I, I, F, F, U64, P, P, P, P, P, P, P, P, P, P, P]),
@@ -149,6 +151,18 @@ def lib():
             fn.restype, fn.argtypes = res, args
         _lib = l
     return _lib
+
+
+# include/mmhip.h mmhip_op_last_gemm_path: NT families / TN family bits
+NT_NONE, NT_GENERIC, NT_TILE, NT_DEEP, NT_SPLITK, NT_X3_DIRECT, NT_X3_SMALL, NT_X3_SPLIT, NT_X3_PAIR = range(9)
+TN_GENERIC, TN_TILE, TN_X3_DIRECT, TN_X3_SPLIT, TN_X3_PAIR = 1, 2, 4, 8, 16
+
+
+def last_gemm_path(which):
+    """the 8 fields of mmhip_op_last_gemm_path for this thread's last NT (which = 0) / TN (which = 1) launcher call"""
+    out = (C.c_int32 * 8)()
+    check(lib().mmhip_op_last_gemm_path(which, out), "mmhip_op_last_gemm_path")
+    return tuple(out)
 
 
 def check(rc, what=""):

@@ -128,9 +128,20 @@ int mmhip_op_gemm_nt(int dtype, const void* A, int lda, const void* B, int ldb, 
         a.x3_ws_bytes = x3_nt_scratch_bytes(M, N, K);
         a.x3_ws = ops_x3_scratch(a.x3_ws_bytes, stream);
     }
+    // 16-bit, few rows, long K: the split-K path the engine's CLS-row GEMMs take (gemm.hip splitk_slices); its fp32 partial products live in the same
+    // per-stream scratch (one operator at a time per stream; the parity mode never takes this path)
+    if (const size_t sk = nt_splitk_scratch_bytes(a, dtype)) a.splitk_ws = (float*)ops_x3_scratch(sk, stream);
     CHECK_HIP(launch_gemm_nt(a, dtype, (hipStream_t)stream));
     return 0;
 }
+
+int mmhip_op_last_gemm_path(int which, int32_t* out) {
+    if (!out || (which != 0 && which != 1)) return MMHIP_E_INVALID;
+    const GemmPathRecord& r = gemm_path_record();
+    for (int i = 0; i < 8; ++i) out[i] = which ? r.tn[i] : r.nt[i];
+    return 0;
+}
+int mmhip_tn_max_group(void) { return GEMM_TN_MAX_GROUP; }
 
 int mmhip_op_gemm_tn(int dtype, const void* A, int lda, const void* B, int ldb, float* C, int ldc, int M, int Nn, int Nc,
                      int accumulate, int force_slow, float* colsum, void* stream) {
@@ -392,7 +403,7 @@ int mmhip_op_attn_bwd(int dtype, const void* qkv, const float* maskbias, const v
     return 0;
 }
 int mmhip_op_colsum(int dtype, const void* x, int rows, int cols, int ld, float* out, void* stream) {
-    if (!x || !out) return MMHIP_E_INVALID;
+    if (!x || !out || (dtype != MMHIP_BF16 && dtype != MMHIP_F16 && dtype != MMHIP_F32)) return MMHIP_E_INVALID;      // (any other code would be read as fp32)
     CHECK_HIP(launch_colsum(x, rows, cols, ld, out, dtype, (hipStream_t)stream));
     return 0;
 }

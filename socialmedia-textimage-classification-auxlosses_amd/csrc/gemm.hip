@@ -624,12 +624,13 @@ static void launch_nt_t(const GemmNTArgs& a, hipStream_t s) {
 
 // few rows, long K: K / 384 slices side by side, then the epilogue over their sum (two launches instead of one 128-row block per
 // 128 columns walking all of K: 64 x 768 x 3072 took 54 us)
-static int splitk_slices(const GemmNTArgs& a) {
+static int splitk_rule(const GemmNTArgs& a) {      // everything but the workspace
     static int on = -1;
     if (on < 0) { const char* e = getenv("MMHIP_SPLITK"); on = e ? atoi(e) : 1; }
-    if (!on || !a.splitk_ws || a.tile || a.M > 128 || a.K < 1536 || a.K % 384 || a.N % 128 || (a.flags & (GEMM_TANH | GEMM_QGELU))) return 0;
+    if (!on || a.tile || a.M > 128 || a.K < 1536 || a.K % 384 || a.N % 128 || (a.flags & (GEMM_TANH | GEMM_QGELU))) return 0;
     return a.K / 384;
 }
+static int splitk_slices(const GemmNTArgs& a) { return a.splitk_ws ? splitk_rule(a) : 0; }
 template <typename T>
 static void launch_nt_splitk(const GemmNTArgs& a, int slices, hipStream_t s) {
     using C = NTCfg<128, 128, 2, 2, 2, 0>;
@@ -719,7 +720,13 @@ static void launch_nt_d(const GemmNTArgs& a, hipStream_t s) {
         const int bn = tile >= 17 ? 192 : ((tile == 13 || tile == 15) ? 256 : 128);
         if (launch_gemm_nt8(a, dt, bn, tile == 15 || tile == 16 || tile == 18, s)) return;
     }
-    switch ((tile >= 13 && tile <= 18) ? 1 : tile) {
+    const int used = (tile >= 13 && tile <= 18) ? 1 : tile;
+    {
+        int* r = gemm_path_record().nt;
+        const int bm = (used == 9 || used == 12) ? 256 : 128, bnn = used == 6 ? 192 : ((used == 10 || used == 12) ? 96 : 128);
+        r[0] = PATH_TILE; r[1] = used; r[2] = -1; r[3] = 0; r[4] = r[5] = ((a.M + bm - 1) / bm) * (a.N / bnn); r[6] = 1;
+    }
+    switch (used) {
         case 20: launch_nt_t<T, 128, 128, 2, 2, 4>(a, s); break;      // 128 x 128 on a 4-deep LDS ring (one block per CU): grids of <= 256 tiles, where
                                                                       // nothing else on the CU hides the load latency of the 2-stage variant
         case 21: launch_nt_t<T, 128, 128, 2, 2, 3>(a, s); break;      // ... 3-deep
@@ -737,6 +744,10 @@ static bool debug_force_slow() {
     return v != 0;
 }
 
+GemmPathRecord& gemm_path_record() {
+    static thread_local GemmPathRecord rec = {};
+    return rec;
+}
 static thread_local GemmTimingSink* g_timing_sink = nullptr;
 void gemm_timing_sink(GemmTimingSink* sink) { g_timing_sink = sink; }
 static hipError_t launch_gemm_nt_untimed(const GemmNTArgs& a, int dtype, hipStream_t s);
@@ -753,11 +764,19 @@ hipError_t launch_gemm_nt(const GemmNTArgs& a, int dtype, hipStream_t s) {
     if (r == hipSuccess) k->used++;
     return r;
 }
+size_t nt_splitk_scratch_bytes(const GemmNTArgs& a, int dtype) {
+    if ((dtype != DT_BF16 && dtype != DT_F16) || a.M <= 0 || a.N <= 0 || !nt_fast_ok(a) || a.force_slow || debug_force_slow()) return 0;
+    return (size_t)splitk_rule(a) * a.M * a.N * sizeof(float);
+}
 static hipError_t launch_gemm_nt_untimed(const GemmNTArgs& a, int dtype, hipStream_t s) {
+    int* rec = gemm_path_record().nt;
+    for (int i = 0; i < 8; ++i) rec[i] = 0;
+    rec[2] = -1;
     if (a.M <= 0 || a.N <= 0) return hipSuccess;
     if (dtype == DT_F32) return launch_gemm_nt_x3(a, s);
     if (nt_fast_ok(a) && !a.force_slow && !debug_force_slow()) {
         if (const int slices = splitk_slices(a)) {
+            rec[0] = PATH_SPLITK; rec[1] = slices; rec[4] = ((a.M + 127) / 128) * (a.N / 128) * slices; rec[5] = rec[4]; rec[6] = 1;
             if (dtype == DT_BF16) launch_nt_splitk<bf16_t>(a, slices, s);
             else launch_nt_splitk<f16_t>(a, slices, s);
             return launch_splitk_finish(a, dtype, slices, s);
@@ -766,6 +785,7 @@ static hipError_t launch_gemm_nt_untimed(const GemmNTArgs& a, int dtype, hipStre
         else launch_nt_d<f16_t>(a, s);
     } else {
         dim3 grid((a.N + 255) / 256, a.M);
+        rec[0] = PATH_GENERIC; rec[6] = 1;
         if (dtype == DT_BF16) hipLaunchKernelGGL(slow_nt_kernel<bf16_t>, grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL(slow_nt_kernel<f16_t>, grid, dim3(256), 0, s, a);
     }
@@ -784,6 +804,8 @@ static void launch_tn_t(const GemmTNGroup& g, int tiles, hipStream_t s) {
 // 2 = 128x128 4-stage ring, 3 = 256x128 3-stage ring, 4 = role-specialised 256x128 (8 MFMA + 4 loader waves, 3-stage
 // ring), 5 = role-specialised 128x128 (4 + 4, 4-stage ring); env MMHIP_TN_TILE overrides
 hipError_t launch_gemm_tn(const GemmTNProblem* probs, int count, int accumulate, int dtype, int force_slow, hipStream_t s, float alpha, void* x3_ws, size_t x3_ws_bytes) {
+    int* rec = gemm_path_record().tn;
+    for (int i = 0; i < 8; ++i) rec[i] = 0;
     if (dtype == DT_F32) return launch_gemm_tn_x3(probs, count, accumulate, s, alpha, force_slow ? nullptr : x3_ws, x3_ws_bytes);
     static int env = -1;
     if (env < 0) { const char* e = getenv("MMHIP_TN_TILE"); env = e ? atoi(e) : 0; }
@@ -805,6 +827,7 @@ hipError_t launch_gemm_tn(const GemmTNProblem* probs, int count, int accumulate,
     int tiles = 0;
     auto flush = [&]() {
         if (!g.count) return;
+        rec[0] |= TNPATH_TILE; rec[1] = variant >= 2 && variant <= 5 ? variant : 1; rec[2] += g.count; rec[4] += 1;
         if (dtype == DT_BF16) {
             if (variant == 4) launch_tn_t<bf16_t, 256, 128, 4, 2, 3, 4>(g, tiles, s);
             else if (variant == 5) launch_tn_t<bf16_t, 128, 128, 2, 2, 4, 4>(g, tiles, s);
@@ -832,6 +855,7 @@ hipError_t launch_gemm_tn(const GemmTNProblem* probs, int count, int accumulate,
             if (g.count == GEMM_TN_MAX_GROUP) flush();
         } else if (P.M > 0) {
             dim3 grid((P.Nc + 255) / 256, P.Nn);
+            rec[0] |= TNPATH_GENERIC; rec[3] += 1;
             if (dtype == DT_BF16) hipLaunchKernelGGL(slow_tn_kernel<bf16_t>, grid, dim3(256), 0, s, P, accumulate, alpha);
             else hipLaunchKernelGGL(slow_tn_kernel<f16_t>, grid, dim3(256), 0, s, P, accumulate, alpha);
             if (P.colsum) {       // generic shapes: the column sums take their own pass

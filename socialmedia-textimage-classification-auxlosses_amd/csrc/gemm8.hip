@@ -631,6 +631,11 @@ static void launch_nt8_e(const GemmNTPair& g, int persistent, hipStream_t s) {
         const int tn = g.p[0].N / BN, ng = (tn + 7) / 8;
         g2.gw = (tn + ng - 1) / ng;
     }
+    {
+        int* r = gemm_path_record().nt;
+        r[0] = PATH_DEEP; r[1] = BN == 256 ? (persistent ? 15 : 13) : (BN == 128 ? (persistent ? 16 : 14) : (persistent ? 18 : 17));
+        r[2] = EPI; r[3] = persistent && ntiles > grid ? 1 : 0; r[4] = grid; r[5] = ntiles; r[6] = g.count;
+    }
     hipLaunchKernelGGL((gemm_nt8_kernel<T, BN, EPI, ET, SEG>), dim3(grid), dim3(512), lds, s, g2, persistent && ntiles > grid ? 1 : 0);
 }
 // epilogue class that covers a flag set (a pair uses the class that covers both)

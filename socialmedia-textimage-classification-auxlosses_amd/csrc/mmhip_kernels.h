@@ -77,6 +77,18 @@ struct SmallGemmArgs {
     int sam, sak, sbk, sbn;   // element strides of A(m,k) and B(k,n); filled by the launch_small_* wrappers
 };
 hipError_t launch_gemm_nt(const GemmNTArgs& a, int dtype, hipStream_t s);
+// What the launchers actually launched for the calling thread's most recent launch_gemm_nt / launch_gemm_tn call (host-side, thread_local, no device
+// work; include/mmhip.h mmhip_op_last_gemm_path documents the fields).  Every silent fallback of the launchers shows here: a forced tile whose N does
+// not divide, launch_gemm_nt8 returning false, nt_fast_ok / the TN shape rules dropping to the generic kernels, TN variants 3 / 4 dropping to 1.
+enum { PATH_NONE = 0, PATH_GENERIC = 1, PATH_TILE = 2, PATH_DEEP = 3, PATH_SPLITK = 4, PATH_X3_DIRECT = 5, PATH_X3_SMALL = 6, PATH_X3_SPLIT = 7, PATH_X3_PAIR = 8 };
+enum { TNPATH_GENERIC = 1, TNPATH_TILE = 2, TNPATH_X3_DIRECT = 4, TNPATH_X3_SPLIT = 8, TNPATH_X3_PAIR = 16 };
+struct GemmPathRecord {
+    int nt[8];      // family, tile code / split-K slices, gemm8 epilogue class (-1: none), persistent loop ran > 1 tile per workgroup, workgroups, tiles, problems, 0
+    int tn[8];      // family bits, variant of the tile kernel, problems on it, problems on the generic kernel, launches of the tile kernel, parity direct, parity scratch-split, 0
+};
+GemmPathRecord& gemm_path_record();
+// fp32 scratch bytes the split-K path of launch_gemm_nt would use for `a` (0: its rules -- splitk_slices, nt_fast_ok -- do not hold; a.splitk_ws itself is not looked at)
+size_t nt_splitk_scratch_bytes(const GemmNTArgs& a, int dtype);
 // Measurement hook (round 5): while a sink is set on the calling thread, launch_gemm_nt brackets every launch with HIP events recorded on the
 // launch's own stream (the early-fusion engine enqueues its NT GEMMs from composite blocks on three streams: there is no single call site to wrap)
 struct GemmTimingSink {

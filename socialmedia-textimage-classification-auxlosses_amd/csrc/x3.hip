@@ -283,7 +283,9 @@ static bool nt_x3_fast(const GemmNTArgs& a, hipStream_t s) {
         GemmNTArgs b = a;
         b.x3_ws = nullptr; b.splitk_ws = nullptr;
         if (a.nprod == 1) { b.a_pair = b.b_pair = 0; }      // hi . hi only: the hi planes are ordinary bf16 matrices of leading dimension lda / ldb
-        return launch_gemm_nt8(b, DT_F32, bn, 1, s);
+        if (!launch_gemm_nt8(b, DT_F32, bn, 1, s)) return false;
+        gemm_path_record().nt[0] = PATH_X3_PAIR;      // tile, class and persistence as launch_gemm_nt8 recorded them
+        return true;
     }
     GemmNTArgs b = a;
     char* pa = (char*)a.x3_ws;
@@ -291,7 +293,7 @@ static bool nt_x3_fast(const GemmNTArgs& a, hipStream_t s) {
     b.A = pa; b.lda = 3 * a.K; b.B = pb; b.ldb = 3 * a.K; b.K = 3 * a.K; b.x3_ws = nullptr; b.splitk_ws = nullptr;
     launch_split3((const float*)a.A, a.lda, a.M, a.K, pa, 3 * a.K, 0, (size_t)a.K, (size_t)2 * a.K, s);
     launch_split3((const float*)a.B, a.ldb, a.N, a.K, pb, 3 * a.K, 0, (size_t)2 * a.K, (size_t)a.K, s);
-    if (launch_gemm_nt8(b, DT_F32, bn, 1, s)) return true;
+    if (launch_gemm_nt8(b, DT_F32, bn, 1, s)) { gemm_path_record().nt[0] = PATH_X3_SPLIT; return true; }
     return false;          // (the two copies above are harmless: the caller falls back to the direct kernel)
 }
 
@@ -305,10 +307,13 @@ hipError_t launch_gemm_nt_x3(const GemmNTArgs& a, hipStream_t s) {
                       (!(a.flags & GEMM_MUL_GELU_GRAD) || (a.ldmul % 4 == 0 && al(a.mul_in))) && (!(a.flags & GEMM_BIAS) || al(a.bias));
     static int small_on = -1;
     if (small_on < 0) { const char* e = getenv("MMHIP_X3_SMALL"); small_on = e ? atoi(e) : 1; }
+    int* rec = gemm_path_record().nt;
+    rec[6] = 1;
     if (fast && small_on && a.M <= 128 && a.K % 128 == 0 && a.N % 16 == 0) {          // few rows: K split over the waves of a 64 x 16 tile (MMHIP_X3_SMALL=0: the 128 x 128 kernel)
+        rec[0] = PATH_X3_SMALL;
         hipLaunchKernelGGL(gemm_nt_x3_small_kernel, dim3(a.N / 16, (a.M + 63) / 64), dim3(256), 0, s, a);
-    } else if (fast) hipLaunchKernelGGL(gemm_nt_x3_kernel, dim3((a.N + 127) / 128, (a.M + 127) / 128), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(slow_nt_f32_kernel, dim3((a.N + 255) / 256, a.M), dim3(256), 0, s, a);
+    } else if (fast) { rec[0] = PATH_X3_DIRECT; hipLaunchKernelGGL(gemm_nt_x3_kernel, dim3((a.N + 127) / 128, (a.M + 127) / 128), dim3(256), 0, s, a); }
+    else { rec[0] = PATH_GENERIC; hipLaunchKernelGGL(slow_nt_f32_kernel, dim3((a.N + 255) / 256, a.M), dim3(256), 0, s, a); }
     return hipGetLastError();
 }
 
@@ -421,11 +426,17 @@ hipError_t launch_gemm_tn_x3(const GemmTNProblem* probs, int count, int accumula
         fastp[nfast++] = Q;
         taken[i] = true;
     }
+    int npair = 0;
+    for (int i = 0; i < count && i < 64; ++i) npair += taken[i] && probs[i].pair ? 1 : 0;
     if (nfast) { hipError_t e = launch_gemm_tn(fastp, nfast, accumulate, DT_BF16, 0, s, alpha); if (e != hipSuccess) return e; }
+    int* rec = gemm_path_record().tn;          // (the nested call above has recorded the tile kernel's variant, problems and launches)
+    if (nfast - npair) { rec[0] |= TNPATH_X3_SPLIT; rec[6] = nfast - npair; }
+    if (npair) rec[0] |= TNPATH_X3_PAIR;
     for (int i = 0; i < count; ++i) {
         const GemmTNProblem& P = probs[i];
         if (i < 64 && taken[i]) continue;
         if (P.M <= 0 || P.Nn <= 0 || P.Nc <= 0) continue;
+        rec[0] |= TNPATH_X3_DIRECT; rec[5] += 1;
         hipLaunchKernelGGL(gemm_tn_x3_kernel, dim3((P.Nc + 127) / 128, (P.Nn + 127) / 128), dim3(256), 0, s, P, accumulate, alpha);
     }
     return hipGetLastError();

@@ -1,4 +1,4 @@
-"""fp64 references of the attention / quick-GELU / LayerNorm operators and the per-element error bounds the op tests hold the HIP kernels to
+"""fp64 references of the attention / quick-GELU / LayerNorm / GEMM (NT epilogues, TN, column sums) operators and the per-element error bounds the op tests hold the HIP kernels to
 (pure torch on the CPU: tests/test_op_bounds_cpu.py checks the bounds themselves, the -m gpu modules check the kernels against them).
 
 Every bound is a sum of named terms read off the kernels' rounding points, from four constants only:
@@ -296,6 +296,15 @@ def ln_bounds(x, gamma, beta, eps, u_out):
     return yb, mean_b, rstd_b
 
 
+def ln_edge_rows(rows, width, g, dt):
+    """the LayerNorm inputs of the op tests: ordinary rows (spread 2, mean 0.3), every fourth row with mean 1e3 and unit spread, row 2 (if any) constant"""
+    x = torch.randn(rows, width, generator=g) * 2 + 0.3
+    x[1::4] = torch.randn(len(range(1, rows, 4)), width, generator=g) + 1e3
+    if rows > 2:
+        x[2] = 0.3
+    return rnd(x.double(), dt)
+
+
 # ---------------------------------------------------------------------------------------------------------------- GEMM epilogues, LayerNorm backward
 def erf_gelu(v):
     return v * 0.5 * torch.erfc(-v / math.sqrt(2.0))
@@ -308,18 +317,29 @@ def erf_gelu_grad(u):
 GELU_ABS, GELU_GRAD_ABS = 4.8e-7, 1.3e-6          # mm_gelu / mm_gelu_grad2: absolute error by construction (csrc/mmhip_common.h, tests/test_gpu_ops.py)
 
 
-def gemm_nt_reference(A, B, dt, bias=None, act=0, mulg=None, keep=None, scale=1.0, resid=None, out="t"):
+NTProducts = namedtuple("NTProducts", "v ab se K")
+
+
+def gemm_nt_products(A, B, dt):
+    """step one of gemm_nt_reference, computed once per (A, B) and shared by every epilogue variant of that pair: the fp64 product A B^T, |A| |B|^T
+    and split_err(A, B) (0 for the 16-bit formats).  Works on whatever device A and B live on."""
+    A, B = A.double(), B.double()
+    return NTProducts(A @ B.t(), A.abs() @ B.abs().t(), split_err(FMT[dt], A, B), A.shape[-1])
+
+
+def gemm_nt_reference(A, B, dt, bias=None, act=0, mulg=None, keep=None, scale=1.0, resid=None, out="t", products=None):
     """fp64 epilogue(A B^T) of mmhip_op_gemm_nt on the values the kernel reads, with its per-element bound:
         acc:   split_err(A, B) + K U_32 |A| |B|^T   [the product]  + U_32 |acc + bias|  [bias add]
         act 1: GELU_ABS + |gelu'| <= 1.13 times the accumulator's error + U_32 |.|;   aux (the pre-activation) = acc error + u_out |pre|
         mulg:  times gelu'(u): (acc error) |gelu'(u)| + GELU_GRAD_ABS |acc| + U_32 |.|
         dropout: times keep * scale (+ U_32);  residual: + U_32 |sum|;  store: u_out |result|;    all times SLACK.
+    out = "f32": the result is stored as fp32 (u_out = U_32); with no bias and no activation that is the bare accumulator against K U_32 |A| |B|^T.
+    products: gemm_nt_products(A, B, dt) when several variants share one (A, B) -- A and B are then not touched.
     Returns (C, C bound, pre, pre bound)."""
     fmt = FMT[dt]
-    A, B = A.double(), B.double()
-    K = A.shape[-1]
-    v = A @ B.t()
-    e = split_err(fmt, A, B) + K * U_32 * (A.abs() @ B.abs().t())
+    pr = products if products is not None else gemm_nt_products(A, B, dt)
+    v = pr.v
+    e = pr.se + pr.K * U_32 * pr.ab
     if bias is not None:
         v = v + bias.double()
         e = e + U_32 * v.abs()
@@ -340,6 +360,45 @@ def gemm_nt_reference(A, B, dt, bias=None, act=0, mulg=None, keep=None, scale=1.
         v = v + resid.double()
         e = e + U_32 * v.abs()
     return v, SLACK * (e + u_out * v.abs()), pre, pre_b
+
+
+def gemm_tn_reference(A, B, dt, C0=None, colsum0=None):
+    """fp64  C = C0 + A^T B  (A [M, Nn], B [M, Nc]: the weight gradient dW = dY^T X) and the column sums  cs = colsum0 + sum_r A[r]  of
+    mmhip_op_gemm_tn / _group on the values the kernels read, each with its per-element bound:
+        C:   split_err(A^T, B^T)   [parity mode: what the three bf16 products lose; 0 for the 16-bit formats, whose operands enter the matrix cores exactly]
+           + M U_32 |A|^T |B|      [fp32 accumulation of M products in any order: MFMA chains, partial sums, atomics]
+           + U_32 |C|              [the store: alpha * acc rounded to fp32]   + U_32 |C| once more with C0 [the accumulate add]
+        cs:  sum_r |A - hi - lo|   [parity mode: the sums are taken over the hi and lo planes, the residual is not carried; 0 otherwise]
+           + M U_32 sum_r |A|      [fp32 accumulation]  + U_32 |cs| [store]  + U_32 |cs| with colsum0 [accumulate add]
+    all times SLACK.  Returns (C, C bound, cs, cs bound)."""
+    fmt = FMT[dt]
+    A, B = A.double(), B.double()
+    M = A.shape[0]
+    At, Bt = A.t(), B.t()
+    C = At @ B
+    e = split_err(fmt, At, Bt) + M * U_32 * (At.abs() @ B.abs())
+    cs = A.sum(0)
+    ce = M * U_32 * A.abs().sum(0)
+    if fmt.split:
+        ce = ce + _parts(A)[0].sum(0)
+    if C0 is not None:
+        C = C + C0.double()
+        e = e + U_32 * C.abs()
+    if colsum0 is not None:
+        cs = cs + colsum0.double()
+        ce = ce + U_32 * cs.abs()
+    return C, SLACK * (e + U_32 * C.abs()), cs, SLACK * (ce + U_32 * cs.abs())
+
+
+def colsum_reference(x, out0=None):
+    """fp64  out0 + sum_r x[r]  of mmhip_op_colsum (csrc/rowops.hip colsum_kernel: fp32 partial sums per 64-row chunk, one atomic add per chunk into out --
+    the kernel ADDS to what out holds) with the bound  rows U_32 (|out0| + sum_r |x|)  [every add, in any order, rounds a running sum no larger than
+    that], times SLACK.  The input is read exactly (16-bit and fp32 values are fp32 values)."""
+    x = x.double()
+    ref, mag = x.sum(0), x.abs().sum(0)
+    if out0 is not None:
+        ref, mag = ref + out0.double(), mag + out0.double().abs()
+    return ref, SLACK * x.shape[0] * U_32 * mag
 
 
 def ln_bwd_reference(dy, x, gamma, mean, rstd, keep=None, scale=1.0):

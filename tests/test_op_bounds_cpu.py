@@ -144,3 +144,113 @@ def test_layernorm_backward_bound():
     wrong = OB.ln_bwd_reference(dy, x, gamma, mean, rstd * (1 + 2.0 ** -12))
     assert violates_elementwise(wrong[0], dx, OB.SLACK * (dx_e + OB.U_32 * dx.abs())) > 0
     assert violates_elementwise(wrong[3], dgam, dgam_b) > 0
+
+
+# ---------------------------------------------------------------------------------------------------------------- GEMM NT / TN, column sums, LayerNorm edges
+def _nt_emulate(A, B, dt):
+    """the accumulator as the kernel forms it: an fp32 product of the operands as the matrix cores read them"""
+    if dt == "x3":
+        return (OB.operand(A, dt) @ OB.operand(B, dt).t()).float()
+    return A.float() @ B.float().t()
+
+
+@pytest.mark.parametrize("dt", ["bf16", "f16", "x3"])
+def test_gemm_nt_bound_sees_a_dropped_k_element(dt):
+    """op_bounds.gemm_nt_reference at the GPU tests' operand scales (A ~ 0.5, B ~ 0.05, residual ~ 1): the emulated kernel is inside for the bare fp32
+    accumulator (plain_f32), the plain 16-bit store and bias + residual; a reference that loses the last K element, the last 32 of K, or adds the
+    neighbouring column's bias is outside somewhere -- for every output type, which is what the scales were chosen for.  The products of one (A, B) are
+    computed once (gemm_nt_products) and give the same reference as the one-step call."""
+    M, N, K = 200, 128, 128
+    g = torch.Generator(device="cpu").manual_seed(M + N + K)
+    A, B = OB.rnd((torch.randn(M, K, generator=g) * 0.5).double(), dt), OB.rnd((torch.randn(N, K, generator=g) * 0.05).double(), dt)
+    bias, resid = torch.randn(N, generator=g), OB.rnd(torch.randn(M, N, generator=g).double(), dt)
+    pr = OB.gemm_nt_products(A, B, dt)
+    acc = _nt_emulate(A, B, dt)
+    cases = {"plain_f32": (dict(out="f32"), acc.double()),
+             "plain": (dict(), OB.rnd(acc.double(), dt)),
+             "bias_resid": (dict(bias=bias, resid=resid), OB.rnd(((acc + bias).float() + resid.float()).double(), dt))}
+    for name, (kw, emu) in cases.items():
+        ref, b, _, _ = OB.gemm_nt_reference(None, None, dt, products=pr, **kw)
+        one_step = OB.gemm_nt_reference(A, B, dt, **kw)
+        assert torch.equal(ref, one_step[0]) and torch.equal(b, one_step[1]), name
+        assert assert_close_elementwise(emu, ref, b, "emulated " + name) <= 1
+        wrong = {"last K element dropped": OB.gemm_nt_reference(A[:, :-1], B[:, :-1], dt, **kw)[0],
+                 "last 32 of K dropped": OB.gemm_nt_reference(A[:, :-32], B[:, :-32], dt, **kw)[0]}
+        if "bias" in kw:
+            wrong["bias of the neighbouring column"] = OB.gemm_nt_reference(None, None, dt, products=pr, **dict(kw, bias=torch.roll(bias, 1)))[0]
+        for what, w in wrong.items():
+            assert violates_elementwise(w, ref, b) > 0, (name, what)
+
+
+@pytest.mark.parametrize("dt", ["bf16", "f16", "x3"])
+@pytest.mark.parametrize("accumulate", [False, True])
+def test_gemm_tn_bound_sees_one_row(dt, accumulate):
+    """op_bounds.gemm_tn_reference: fp32 products of the operands as read (+ the accumulate add), stored as fp32, are inside for C and the column sums;
+    one row more or one row fewer in the reduction is outside, for C and for the column sums"""
+    M, Nn, Nc = 64, 40, 72
+    g = torch.Generator(device="cpu").manual_seed(M + Nn)
+    A, B = OB.rnd((torch.randn(M + 1, Nn, generator=g) * 0.1).double(), dt), OB.rnd((torch.randn(M + 1, Nc, generator=g) * 0.5).double(), dt)
+    C0 = torch.randn(Nn, Nc, generator=g) if accumulate else None
+    cs0 = torch.randn(Nn, generator=g) if accumulate else None
+    ref, b, cs, csb = OB.gemm_tn_reference(A[:M], B[:M], dt, C0, cs0)
+    a, bb = (OB.operand(A[:M], dt), OB.operand(B[:M], dt)) if dt == "x3" else (A[:M], B[:M])
+    emu, emu_cs = (a.t() @ bb).float(), a.sum(0).float()
+    if accumulate:
+        emu, emu_cs = (emu + C0).float(), (emu_cs + cs0).float()
+    assert assert_close_elementwise(emu, ref, b, "emulated C") <= 1 and assert_close_elementwise(emu_cs, cs, csb, "emulated column sums") <= 1
+    for rows in (M + 1, M - 1):
+        w = OB.gemm_tn_reference(A[:rows], B[:rows], dt, C0, cs0)
+        assert violates_elementwise(w[0], ref, b) > 0 and violates_elementwise(w[2], cs, csb) > 0, rows
+
+
+@pytest.mark.parametrize("dt", ["bf16", "f16", "x3"])
+def test_colsum_bound_sees_one_row(dt):
+    R, Wd = 1000, 36
+    g = torch.Generator(device="cpu").manual_seed(R)
+    x = OB.rnd(torch.randn(R + 1, Wd, generator=g).double(), dt)
+    ref, b = OB.colsum_reference(x[:R])
+    assert assert_close_elementwise(x[:R].float().sum(0), ref, b, "fp32 column sums") <= 1
+    chunks = torch.stack([x[:R][i:i + 64].float().sum(0) for i in range(0, R, 64)]).sum(0)          # per 64-row chunk, then across chunks
+    assert assert_close_elementwise(chunks, ref, b, "chunked fp32 column sums") <= 1
+    for rows in (R + 1, R - 1):
+        assert violates_elementwise(OB.colsum_reference(x[:rows])[0], ref, b) > 0
+
+
+def _ln_emulate(x, gamma, beta, eps):
+    """ln_fwd_kernel's order in fp32: mean, then the sum of squared differences from it, rsqrt, (x - mean) rstd gamma + beta"""
+    x = x.float()
+    W = x.shape[-1]
+    mean = x.sum(-1, keepdim=True) / W
+    d = x - mean
+    rstd = torch.rsqrt((d * d).sum(-1, keepdim=True) / W + eps)
+    return d * rstd * gamma.float() + beta.float(), mean.squeeze(-1), rstd.squeeze(-1)
+
+
+@pytest.mark.parametrize("dt", ["bf16", "f16", "x3"])
+@pytest.mark.parametrize("width", [768, 4])
+def test_layernorm_bound_holds_on_large_mean_and_constant_rows(dt, width):
+    """rows with mean 1e3 and unit spread, and a constant row (variance 0: rstd = 1 / sqrt(eps), y = beta), are inside ln_bounds for the fp32 emulation
+    rounded as stored; eps left out is outside on the constant row (rstd) and an off-by-one width in the mean is outside on the large-mean rows"""
+    g = torch.Generator(device="cpu").manual_seed(width)
+    x = OB.ln_edge_rows(9, width, g, dt)
+    gamma, beta = 1 + 0.1 * torch.randn(width, generator=g), 0.1 * torch.randn(width, generator=g)
+    u = OB.FMT[dt].u_out
+    y, mean, rstd = OB.ln_reference(x, gamma, beta, 1e-5)
+    yb, mb, rb = OB.ln_bounds(x, gamma, beta, 1e-5, u)
+    ey, em, er = _ln_emulate(x, gamma, beta, 1e-5)
+    assert assert_close_elementwise(OB.rnd(ey.double(), dt), y, yb, "y") <= 1
+    assert assert_close_elementwise(em, mean, mb, "mean") <= 1 and assert_close_elementwise(er, rstd, rb, "rstd") <= 1
+    assert abs(rstd[2].item() - 1e-5 ** -0.5) < 1e-9 and torch.equal(y[2], beta.double())
+    _, _, rstd0 = OB.ln_reference(x, gamma, beta, 2e-5)
+    assert ((rstd0 - rstd).abs() > rb)[2].item()
+    wrong_mean = x.sum(-1) / (width + 1)
+    assert ((wrong_mean - mean).abs() > mb)[1].item()
+    # backward on the saved statistics: fp32 arithmetic in the kernel's order is inside on every row, the constant one included
+    dy = OB.rnd(torch.randn(9, width, generator=g).double(), dt)
+    dx, dx_e, _, dgam, dgam_b, dbet, dbet_b = OB.ln_bwd_reference(dy, x, gamma, em, er)
+    xh = (x.float() - em[:, None]) * er[:, None]
+    gg = dy.float() * gamma.float()
+    c1, c2 = gg.sum(-1, keepdim=True) / width, (gg * xh).sum(-1, keepdim=True) / width
+    edx = er[:, None] * (gg - c1 - xh * c2)
+    assert assert_close_elementwise(OB.rnd(edx.double(), dt), dx, OB.SLACK * (dx_e + u * dx.abs()), "dx") <= 1
+    assert assert_close_elementwise((dy.float() * xh).sum(0), dgam, dgam_b, "dgamma") <= 1 and assert_close_elementwise(dy.float().sum(0), dbet, dbet_b, "dbeta") <= 1
