@@ -1,31 +1,11 @@
 // Operator-level C entry points (parity tests call the very launchers the engine uses) and the hardware-layout probe.
 #include <map>
 #include <mutex>
-#include <cstring>
-#include <cmath>
-#include "mmhip_common.h"
 #include <vector>
-#include "mmhip_kernels.h"
-#include "../../include/mmhip.h"
+#include "mmhip_common.h"
+#include "mmhip_host.h"
 
 using namespace mmhip;
-
-#define CHECK_HIP(expr)                       \
-    do {                                      \
-        hipError_t _e = (expr);               \
-        if (_e != hipSuccess) return (int)_e; \
-    } while (0)
-
-static DropCfg drop_of(float p, uint64_t seed, uint32_t stream) {
-    DropCfg d;
-    d.seed = seed;
-    d.stream = stream;
-    uint32_t t = p > 0.f ? (uint32_t)lrintf(p * 65536.0f) : 0u;
-    if (t > 65535u) t = 65535u;
-    d.thresh16 = t;
-    d.keep_scale = 1.0f / (1.0f - (float)t / 65536.0f);
-    return d;
-}
 
 // ------------------------------------------------------------------------------------------------ probe
 // Index-coded operands make every lane's view of the MFMA / transposing-read layouts observable:
@@ -110,20 +90,18 @@ int mmhip_op_gemm_nt(int dtype, const void* A, int lda, const void* B, int ldb, 
                      float p_drop, uint64_t seed, uint32_t stream_id, const void* residual, int ldres, int out_f32,
                      int force_slow, void* stream) {
     if (!A || !B || !C || M < 0 || N < 1 || K < 1 || (dtype != MMHIP_BF16 && dtype != MMHIP_F16 && dtype != MMHIP_F32)) return MMHIP_E_INVALID;
-    GemmNTArgs a;
-    memset(&a, 0, sizeof(a));
-    a.A = A; a.B = B; a.C = C; a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.M = M; a.N = N; a.K = K;
-    if (bias) { a.bias = bias; a.flags |= GEMM_BIAS; }
-    if (act == 1) a.flags |= GEMM_GELU;
-    if (act == 2) a.flags |= GEMM_TANH;
-    if (act == 3) a.flags |= GEMM_QGELU;
-    if (aux_pre) { a.aux = aux_pre; a.ldaux = ldaux; a.flags |= GEMM_AUX_PRE; }
-    if (mul_gelu_grad_of) { a.mul_in = mul_gelu_grad_of; a.ldmul = ldmul; a.flags |= GEMM_MUL_GELU_GRAD; }
-    if (p_drop > 0.f) { a.drop = drop_of(p_drop, seed, stream_id); a.flags |= GEMM_DROPOUT; }
-    if (residual) { a.residual = residual; a.ldres = ldres; a.flags |= GEMM_RESIDUAL; }
-    if (out_f32) a.flags |= GEMM_OUT_F32;
-    a.force_slow = force_slow & 1;
-    a.tile = force_slow >> 4;      // bits 4.. select the tile variant (test / tuning hook)
+    G g(A, lda, B, ldb, C, ldc, M, N, K);
+    if (bias) g.bias(bias);
+    if (act == 1) g.gelu();
+    if (act == 2) g.tanh();
+    if (act == 3) g.qgelu();
+    if (aux_pre) g.aux(aux_pre, ldaux);
+    if (mul_gelu_grad_of) g.mul_gelu_grad(mul_gelu_grad_of, ldmul);
+    g.dropout(make_drop(p_drop, seed, stream_id));
+    if (residual) g.residual(residual, ldres);
+    if (out_f32) g.out_f32();
+    g.force_slow(force_slow & 1).tile(force_slow >> 4);      // bits 4.. select the tile variant (test / tuning hook)
+    GemmNTArgs& a = g.a;
     if (dtype == MMHIP_F32 && M > 128 && !a.force_slow) {
         a.x3_ws_bytes = x3_nt_scratch_bytes(M, N, K);
         a.x3_ws = ops_x3_scratch(a.x3_ws_bytes, stream);
@@ -170,26 +148,25 @@ int mmhip_op_gemm_tn_group(int dtype, const mmhip_tn_problem* problems, int coun
 
 int mmhip_op_cast_group(int dtype, const mmhip_cast_mat* mats, int count, void* stream) {
     if (!mats || count < 0 || (dtype != MMHIP_BF16 && dtype != MMHIP_F16 && dtype != MMHIP_F32)) return MMHIP_E_INVALID;
-    CastMat g[CAST_MAX_GROUP];
-    for (int i = 0; i < count;) {
-        int n = 0;
-        for (; n < CAST_MAX_GROUP && i < count; ++n, ++i) {
-            if (!mats[i].src || !mats[i].dst || mats[i].rows < 4 || mats[i].cols < 4) return MMHIP_E_INVALID;
-            g[n] = CastMat{mats[i].src, mats[i].dst, mats[i].dst_t, mats[i].rows, mats[i].cols, 0};
-        }
-        CHECK_HIP(launch_cast_group(g, n, dtype, (hipStream_t)stream));
+    std::vector<CastMat> g((size_t)count);
+    for (int i = 0; i < count; ++i) {
+        if (!mats[i].src || !mats[i].dst || mats[i].rows < 4 || mats[i].cols < 4) return MMHIP_E_INVALID;
+        g[i] = CastMat{mats[i].src, mats[i].dst, mats[i].dst_t, mats[i].rows, mats[i].cols, 0};
     }
-    return 0;
+    return launch_cast_groups(g, dtype, (hipStream_t)stream);
 }
 
 // ---- composite operators: one post-LN sub-block of a BERT-shaped stream per call (the early-fusion path's host time is launch
 // and interpreter work: a block is 3-4 launches of the same kernels, enqueued from C++)
+// (dropout stream ids inside a block: 7 attention probabilities, 8 attention output, 9 feed-forward output)
 namespace {
-GemmNTArgs nt(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K) {
-    GemmNTArgs a;
-    memset(&a, 0, sizeof(a));
-    a.A = A; a.lda = lda; a.B = B; a.ldb = ldb; a.C = C; a.ldc = ldc; a.M = M; a.N = N; a.K = K;
-    return a;
+// backward of the block's closing LayerNorm: d pre, and its dropout-backward copy dd when the block's output dropout was on
+LNBwdArgs block_ln_bwd(const void* dy, const void* pre, const float* gamma, const float* mean, const float* rstd, void* dpre, float* dgamma, float* dbeta, int rows, int width,
+                       void* dd, float p_hid, uint64_t seed, uint32_t stream_id) {
+    LNBwdArgs b{};
+    b.dy = dy; b.x = pre; b.gamma = gamma; b.mean = mean; b.rstd = rstd; b.dx = dpre; b.dgamma = dgamma; b.dbeta = dbeta; b.rows = rows; b.width = width; b.alpha = 1.0f;
+    if (p_hid > 0.f) { b.dx_drop = dd; b.drop = make_drop(p_hid, seed, stream_id); b.drop_row_mul = 1; }
+    return b;
 }
 }  // namespace
 
@@ -200,15 +177,9 @@ int mmhip_op_self_att_block_fwd(int dtype, const void* x, const float* maskbias,
         return MMHIP_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const int H = heads * 64, M = posts * S;
-    { GemmNTArgs a = nt(x, H, wqkv, H, qkv, 3 * H, M, 3 * H, H); a.bias = bqkv; a.flags = GEMM_BIAS; CHECK_HIP(launch_gemm_nt(a, dtype, s)); }
-    AttnArgs at;
-    memset(&at, 0, sizeof(at));
-    at.qkv = qkv; at.maskbias = maskbias; at.ctx = att; at.lse = lse; at.posts = posts; at.S = S; at.heads = heads;
-    at.hidden = H; at.ld_qkv = 3 * H; at.ld_ctx = H; at.scale = 0.125f; at.drop = drop_of(p_att, seed, 7);
-    CHECK_HIP(launch_attn_fwd(at, dtype, s));
-    { GemmNTArgs a = nt(att, H, wo, H, pre, H, M, H, H); a.bias = bo; a.residual = x; a.ldres = H; a.flags = GEMM_BIAS | GEMM_RESIDUAL;
-      if (p_hid > 0.f) { a.drop = drop_of(p_hid, seed, 8); a.flags |= GEMM_DROPOUT; }
-      CHECK_HIP(launch_gemm_nt(a, dtype, s)); }
+    CHECK_HIP(launch_gemm_nt(G(x, H, wqkv, H, qkv, 3 * H, M, 3 * H, H).bias(bqkv).a, dtype, s));
+    CHECK_HIP(launch_attn_fwd(attn_args(qkv, maskbias, att, lse, posts, S, heads, H, make_drop(p_att, seed, 7)), dtype, s));
+    CHECK_HIP(launch_gemm_nt(G(att, H, wo, H, pre, H, M, H, H).bias(bo).dropout(make_drop(p_hid, seed, 8)).residual(x, H).a, dtype, s));
     LNArgs ln{pre, y, gamma, beta, mean, rstd, M, H, H, H, eps};
     CHECK_HIP(launch_layernorm_fwd(ln, dtype, s));
     return 0;
@@ -222,20 +193,11 @@ int mmhip_op_self_att_block_bwd(int dtype, const void* dy, const float* maskbias
         return MMHIP_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const int H = heads * 64, M = posts * S;
-    LNBwdArgs b;
-    memset(&b, 0, sizeof(b));
-    b.dy = dy; b.x = pre; b.gamma = gamma; b.mean = mean; b.rstd = rstd; b.dx = dpre; b.dgamma = dgamma; b.dbeta = dbeta; b.rows = M; b.width = H; b.alpha = 1.0f;
-    const bool dropping = p_hid > 0.f;
-    if (dropping) { b.dx_drop = dd; b.drop = drop_of(p_hid, seed, 8); b.drop_row_mul = 1; }
-    CHECK_HIP(launch_layernorm_bwd(b, dtype, s));
-    const void* dsrc = dropping ? dd : dpre;          // gradient of the output projection's result
-    { GemmNTArgs a = nt(dsrc, H, woT, H, datt, H, M, H, H); CHECK_HIP(launch_gemm_nt(a, dtype, s)); }
-    AttnBwdArgs ab;
-    memset(&ab, 0, sizeof(ab));
-    ab.qkv = qkv; ab.maskbias = maskbias; ab.ctx = att; ab.dctx = datt; ab.lse = lse; ab.dqkv = dqkv; ab.posts = posts; ab.S = S; ab.heads = heads;
-    ab.hidden = H; ab.ld_qkv = 3 * H; ab.ld_ctx = H; ab.scale = 0.125f; ab.drop = drop_of(p_att, seed, 7);
-    CHECK_HIP(launch_attn_bwd(ab, dtype, s));
-    { GemmNTArgs a = nt(dqkv, 3 * H, wqkvT, 3 * H, dx, H, M, H, 3 * H); a.residual = dpre; a.ldres = H; a.flags = GEMM_RESIDUAL; CHECK_HIP(launch_gemm_nt(a, dtype, s)); }
+    CHECK_HIP(launch_layernorm_bwd(block_ln_bwd(dy, pre, gamma, mean, rstd, dpre, dgamma, dbeta, M, H, dd, p_hid, seed, 8), dtype, s));
+    const void* dsrc = p_hid > 0.f ? dd : dpre;          // gradient of the output projection's result
+    CHECK_HIP(launch_gemm_nt(G(dsrc, H, woT, H, datt, H, M, H, H).a, dtype, s));
+    CHECK_HIP(launch_attn_bwd(attn_bwd_args(qkv, maskbias, att, datt, lse, dqkv, posts, S, heads, H, make_drop(p_att, seed, 7)), dtype, s));
+    CHECK_HIP(launch_gemm_nt(G(dqkv, 3 * H, wqkvT, 3 * H, dx, H, M, H, 3 * H).residual(dpre, H).a, dtype, s));
     return 0;
 }
 
@@ -262,25 +224,14 @@ int mmhip_op_cross_att_block_fwd(int dtype, const void* xq, const void* xc, cons
     // (AttnArgs::q_rps / kv_rps / ctx_rps) and the two lengths.  Nothing is padded, cleared, remapped or copied; key tiles past Sk are not computed;
     // att is [Mq, H], the operand of the output projection as it is.  The dropout masks, the lse rows and keybias keep the indices of the S x S layout.
     const char* w = (const char*)wqkv;
-    {   // Q = xq Wq^T + bq
-        GemmNTArgs a = nt(xq, H, w, H, qkv, 3 * H, Mq, H, H);
-        a.bias = bqkv; a.flags = GEMM_BIAS;
-        CHECK_HIP(launch_gemm_nt(a, dtype, s));
-    }
-    {   // [K | V] = xc [Wk; Wv]^T + [bk; bv]
-        GemmNTArgs a = nt(xc, H, w + (size_t)H * H * Z, H, (char*)qkv + (size_t)H * Z, 3 * H, Mc, 2 * H, H);
-        a.bias = bqkv + H; a.flags = GEMM_BIAS;
-        CHECK_HIP(launch_gemm_nt(a, dtype, s));
-    }
-    AttnArgs at;
-    memset(&at, 0, sizeof(at));
-    at.qkv = qkv; at.maskbias = keybias; at.ctx = att; at.lse = lse; at.posts = posts; at.S = S; at.heads = heads;
-    at.hidden = H; at.ld_qkv = 3 * H; at.ld_ctx = H; at.scale = 0.125f; at.drop = drop_of(p_att, seed, 7);
-    at.Sq_live = Sq; at.Sk_live = Sk; at.q_rps = Sq; at.kv_rps = Sk; at.ctx_rps = Sq;
+    // Q = xq Wq^T + bq
+    CHECK_HIP(launch_gemm_nt(G(xq, H, w, H, qkv, 3 * H, Mq, H, H).bias(bqkv).a, dtype, s));
+    // [K | V] = xc [Wk; Wv]^T + [bk; bv]
+    CHECK_HIP(launch_gemm_nt(G(xc, H, w + (size_t)H * H * Z, H, (char*)qkv + (size_t)H * Z, 3 * H, Mc, 2 * H, H).bias(bqkv + H).a, dtype, s));
+    AttnArgs at = attn_args(qkv, keybias, att, lse, posts, S, heads, H, make_drop(p_att, seed, 7));
+    attn_cross(at, Sq, Sk);
     CHECK_HIP(launch_attn_fwd(at, dtype, s));
-    { GemmNTArgs a = nt(att, H, wo, H, pre, H, Mq, H, H); a.bias = bo; a.residual = xq; a.ldres = H; a.flags = GEMM_BIAS | GEMM_RESIDUAL;
-      if (p_hid > 0.f) { a.drop = drop_of(p_hid, seed, 8); a.flags |= GEMM_DROPOUT; }
-      CHECK_HIP(launch_gemm_nt(a, dtype, s)); }
+    CHECK_HIP(launch_gemm_nt(G(att, H, wo, H, pre, H, Mq, H, H).bias(bo).dropout(make_drop(p_hid, seed, 8)).residual(xq, H).a, dtype, s));
     LNArgs ln{pre, y, gamma, beta, mean, rstd, Mq, H, H, H, eps};
     CHECK_HIP(launch_layernorm_fwd(ln, dtype, s));
     return 0;
@@ -297,32 +248,19 @@ int mmhip_op_cross_att_block_bwd(int dtype, const void* dy, const float* keybias
     hipStream_t s = (hipStream_t)stream;
     const int H = heads * 64, S = Sq > Sk ? Sq : Sk, Mq = posts * Sq, Mc = posts * Sk;
     const size_t Z = esz_of(dtype);
-    LNBwdArgs b;
-    memset(&b, 0, sizeof(b));
-    b.dy = dy; b.x = pre; b.gamma = gamma; b.mean = mean; b.rstd = rstd; b.dx = dpre; b.dgamma = dgamma; b.dbeta = dbeta; b.rows = Mq; b.width = H; b.alpha = 1.0f;
-    const bool dropping = p_hid > 0.f;
-    if (dropping) { b.dx_drop = dd; b.drop = drop_of(p_hid, seed, 8); b.drop_row_mul = 1; }
-    CHECK_HIP(launch_layernorm_bwd(b, dtype, s));
-    const void* dsrc = dropping ? dd : dpre;
-    { GemmNTArgs a = nt(dsrc, H, woT, H, datt, H, Mq, H, H); CHECK_HIP(launch_gemm_nt(a, dtype, s)); }          // d att, compact [Mq, H] like att
-    AttnBwdArgs ab;
-    memset(&ab, 0, sizeof(ab));
-    ab.qkv = qkv; ab.maskbias = keybias; ab.ctx = att; ab.dctx = datt; ab.lse = lse; ab.dqkv = dqkv; ab.posts = posts; ab.S = S; ab.heads = heads;
-    ab.hidden = H; ab.ld_qkv = 3 * H; ab.ld_ctx = H; ab.scale = 0.125f; ab.drop = drop_of(p_att, seed, 7);
-    ab.Sq_live = Sq; ab.Sk_live = Sk; ab.q_rps = Sq; ab.kv_rps = Sk; ab.ctx_rps = Sq;
+    CHECK_HIP(launch_layernorm_bwd(block_ln_bwd(dy, pre, gamma, mean, rstd, dpre, dgamma, dbeta, Mq, H, dd, p_hid, seed, 8), dtype, s));
+    const void* dsrc = p_hid > 0.f ? dd : dpre;
+    CHECK_HIP(launch_gemm_nt(G(dsrc, H, woT, H, datt, H, Mq, H, H).a, dtype, s));          // d att, compact [Mq, H] like att
+    AttnBwdArgs ab = attn_bwd_args(qkv, keybias, att, datt, lse, dqkv, posts, S, heads, H, make_drop(p_att, seed, 7));
+    attn_cross(ab, Sq, Sk);
     CHECK_HIP(launch_attn_bwd(ab, dtype, s));
     // dqkv as qkv: dQ in rows [0, Mq) of columns [0, H), [dK | dV] in rows [0, Mc) of columns [H, 3H) -- the operands of the two input-gradient products
     // below and of the caller's weight-gradient products (leading dimension 3H), as they are
     const char* wt = (const char*)wqkvT;              // [H, 3H]: columns [0,H) = Wq^T, [H,3H) = [Wk; Wv]^T
-    {   // d xq = dQ Wq + d pre (residual branch)
-        GemmNTArgs a = nt(dqkv, 3 * H, wt, 3 * H, dxq, H, Mq, H, H);
-        a.residual = dpre; a.ldres = H; a.flags = GEMM_RESIDUAL;
-        CHECK_HIP(launch_gemm_nt(a, dtype, s));
-    }
-    {   // d xc = [dK | dV] [Wk; Wv]
-        GemmNTArgs a = nt((const char*)dqkv + (size_t)H * Z, 3 * H, wt + (size_t)H * Z, 3 * H, dxc, H, Mc, H, 2 * H);
-        CHECK_HIP(launch_gemm_nt(a, dtype, s));
-    }
+    // d xq = dQ Wq + d pre (residual branch)
+    CHECK_HIP(launch_gemm_nt(G(dqkv, 3 * H, wt, 3 * H, dxq, H, Mq, H, H).residual(dpre, H).a, dtype, s));
+    // d xc = [dK | dV] [Wk; Wv]
+    CHECK_HIP(launch_gemm_nt(G((const char*)dqkv + (size_t)H * Z, 3 * H, wt + (size_t)H * Z, 3 * H, dxc, H, Mc, H, 2 * H).a, dtype, s));
     return 0;
 }
 
@@ -331,10 +269,8 @@ int mmhip_op_ffn_block_fwd(int dtype, const void* x, const void* w1, const float
                            void* stream) {
     if (!x || !w1 || !b1 || !w2 || !b2 || !gamma || !beta || !h || !u || !pre || !mean || !rstd || !y || M < 1) return MMHIP_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    { GemmNTArgs a = nt(x, H, w1, H, h, I, M, I, H); a.bias = b1; a.aux = u; a.ldaux = I; a.flags = GEMM_BIAS | GEMM_GELU | GEMM_AUX_PRE; CHECK_HIP(launch_gemm_nt(a, dtype, s)); }
-    { GemmNTArgs a = nt(h, I, w2, I, pre, H, M, H, I); a.bias = b2; a.residual = x; a.ldres = H; a.flags = GEMM_BIAS | GEMM_RESIDUAL;
-      if (p_hid > 0.f) { a.drop = drop_of(p_hid, seed, 9); a.flags |= GEMM_DROPOUT; }
-      CHECK_HIP(launch_gemm_nt(a, dtype, s)); }
+    CHECK_HIP(launch_gemm_nt(G(x, H, w1, H, h, I, M, I, H).bias(b1).aux(u, I).gelu().a, dtype, s));
+    CHECK_HIP(launch_gemm_nt(G(h, I, w2, I, pre, H, M, H, I).bias(b2).dropout(make_drop(p_hid, seed, 9)).residual(x, H).a, dtype, s));
     LNArgs ln{pre, y, gamma, beta, mean, rstd, M, H, H, H, eps};
     CHECK_HIP(launch_layernorm_fwd(ln, dtype, s));
     return 0;
@@ -345,15 +281,10 @@ int mmhip_op_ffn_block_bwd(int dtype, const void* dy, const void* w1T, const voi
                            void* dx, void* stream) {
     if (!dy || !w1T || !w2T || !gamma || !u || !pre || !mean || !rstd || !dgamma || !dbeta || !dpre || !dd || !du || !dx) return MMHIP_E_INVALID;
     hipStream_t s = (hipStream_t)stream;
-    LNBwdArgs b;
-    memset(&b, 0, sizeof(b));
-    b.dy = dy; b.x = pre; b.gamma = gamma; b.mean = mean; b.rstd = rstd; b.dx = dpre; b.dgamma = dgamma; b.dbeta = dbeta; b.rows = M; b.width = H; b.alpha = 1.0f;
-    const bool dropping = p_hid > 0.f;
-    if (dropping) { b.dx_drop = dd; b.drop = drop_of(p_hid, seed, 9); b.drop_row_mul = 1; }
-    CHECK_HIP(launch_layernorm_bwd(b, dtype, s));
-    const void* dsrc = dropping ? dd : dpre;
-    { GemmNTArgs a = nt(dsrc, H, w2T, H, du, I, M, I, H); a.mul_in = u; a.ldmul = I; a.flags = GEMM_MUL_GELU_GRAD; CHECK_HIP(launch_gemm_nt(a, dtype, s)); }
-    { GemmNTArgs a = nt(du, I, w1T, I, dx, H, M, H, I); a.residual = dpre; a.ldres = H; a.flags = GEMM_RESIDUAL; CHECK_HIP(launch_gemm_nt(a, dtype, s)); }
+    CHECK_HIP(launch_layernorm_bwd(block_ln_bwd(dy, pre, gamma, mean, rstd, dpre, dgamma, dbeta, M, H, dd, p_hid, seed, 9), dtype, s));
+    const void* dsrc = p_hid > 0.f ? dd : dpre;
+    CHECK_HIP(launch_gemm_nt(G(dsrc, H, w2T, H, du, I, M, I, H).mul_gelu_grad(u, I).a, dtype, s));
+    CHECK_HIP(launch_gemm_nt(G(du, I, w1T, I, dx, H, M, H, I).residual(dpre, H).a, dtype, s));
     return 0;
 }
 
@@ -362,7 +293,7 @@ int mmhip_op_layernorm_fwd(int dtype, const void* x, void* y, const float* gamma
     if (!x || !y || !gamma || !beta) return MMHIP_E_INVALID;
     LNArgs a{x, y, gamma, beta, mean, rstd, rows, width, width, width, eps};
     if (dtype == MMHIP_PAIR) {          // parity mode as the engine runs it: fp32 rows in, the output as a plane pair only ([hi(width) | lo(width)] per row)
-        a.y = nullptr; a.y_pair = y; a.ld_pair = 2 * width; a.lo_pair = width;
+        ln_pair(a, true, y, true);
         dtype = MMHIP_F32;
     }
     CHECK_HIP(launch_layernorm_fwd(a, dtype, (hipStream_t)stream));
@@ -371,8 +302,7 @@ int mmhip_op_layernorm_fwd(int dtype, const void* x, void* y, const float* gamma
 int mmhip_op_layernorm_bwd(int dtype, const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
                            void* dx, const void* dres, float* dgamma, float* dbeta, int rows, int width, void* stream) {
     if (!dy || !x || !gamma || !mean || !rstd || !dx || !dgamma || !dbeta) return MMHIP_E_INVALID;
-    LNBwdArgs a;
-    memset(&a, 0, sizeof(a));
+    LNBwdArgs a{};
     a.dy = dy; a.x = x; a.gamma = gamma; a.mean = mean; a.rstd = rstd; a.dx = dx; a.dres = dres; a.dgamma = dgamma; a.dbeta = dbeta;
     a.rows = rows; a.width = width; a.alpha = 1.0f;
     CHECK_HIP(launch_layernorm_bwd(a, dtype, (hipStream_t)stream));
@@ -381,24 +311,16 @@ int mmhip_op_layernorm_bwd(int dtype, const void* dy, const void* x, const float
 int mmhip_op_attn_fwd(int dtype, const void* qkv, const float* maskbias, void* ctx, float* lse, int posts, int S, int heads,
                       float p_drop, uint64_t seed, uint32_t stream_id, void* stream) {
     if (!qkv || !ctx || posts < 1 || S < 1 || heads < 1) return MMHIP_E_INVALID;
-    AttnArgs a;
-    memset(&a, 0, sizeof(a));
-    a.qkv = qkv; a.maskbias = maskbias; a.ctx = ctx; a.lse = lse; a.posts = posts; a.S = S; a.heads = heads;
-    a.hidden = heads * 64; a.ld_qkv = 3 * a.hidden; a.ld_ctx = a.hidden; a.scale = 0.125f;
-    a.drop = drop_of(p_drop, seed, stream_id);
-    if (dtype == MMHIP_PAIR) { a.pair = 1; a.ld_qkv = 6 * a.hidden; a.lo_qkv = 3 * a.hidden; a.ld_ctx = 2 * a.hidden; a.lo_ctx = a.hidden; dtype = MMHIP_F32; }
+    AttnArgs a = attn_args(qkv, maskbias, ctx, lse, posts, S, heads, heads * 64, make_drop(p_drop, seed, stream_id));
+    if (dtype == MMHIP_PAIR) { attn_pair(a, true); dtype = MMHIP_F32; }
     CHECK_HIP(launch_attn_fwd(a, dtype, (hipStream_t)stream));
     return 0;
 }
 int mmhip_op_attn_bwd(int dtype, const void* qkv, const float* maskbias, const void* ctx, const void* dctx, const float* lse,
                       void* dqkv, int posts, int S, int heads, float p_drop, uint64_t seed, uint32_t stream_id, void* stream) {
     if (!qkv || !ctx || !dctx || !lse || !dqkv || posts < 1 || S < 1 || heads < 1) return MMHIP_E_INVALID;
-    AttnBwdArgs a;
-    memset(&a, 0, sizeof(a));
-    a.qkv = qkv; a.maskbias = maskbias; a.ctx = ctx; a.dctx = dctx; a.lse = lse; a.dqkv = dqkv; a.posts = posts; a.S = S; a.heads = heads;
-    a.hidden = heads * 64; a.ld_qkv = 3 * a.hidden; a.ld_ctx = a.hidden; a.scale = 0.125f;
-    a.drop = drop_of(p_drop, seed, stream_id);
-    if (dtype == MMHIP_PAIR) { a.pair = 1; a.ld_qkv = 6 * a.hidden; a.lo_qkv = 3 * a.hidden; a.ld_ctx = 2 * a.hidden; a.lo_ctx = a.hidden; dtype = MMHIP_F32; }
+    AttnBwdArgs a = attn_bwd_args(qkv, maskbias, ctx, dctx, lse, dqkv, posts, S, heads, heads * 64, make_drop(p_drop, seed, stream_id));
+    if (dtype == MMHIP_PAIR) { attn_pair(a, true); dtype = MMHIP_F32; }
     CHECK_HIP(launch_attn_bwd(a, dtype, (hipStream_t)stream));
     return 0;
 }

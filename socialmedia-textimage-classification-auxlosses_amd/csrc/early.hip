@@ -16,26 +16,12 @@
 //     stages below it still compute (mmhip_early_train_step's callback, the ABI of mmhip_train_step_dp).
 #include <string>
 #include <vector>
-#include <cstring>
-#include <cmath>
 #include <cstdlib>
 #include <cstdio>
 #include "mmhip_common.h"
-#include "mmhip_kernels.h"
-#include "../../include/mmhip.h"
+#include "mmhip_host.h"
 
 using namespace mmhip;
-
-#define CHECK_HIP(expr)                       \
-    do {                                      \
-        hipError_t _e = (expr);               \
-        if (_e != hipSuccess) return (int)_e; \
-    } while (0)
-#define CHECK_RC(expr)          \
-    do {                        \
-        int _r = (expr);        \
-        if (_r) return _r;      \
-    } while (0)
 
 namespace {
 
@@ -190,17 +176,6 @@ hipError_t launch_tn_few_cols(const void* dy, int ldy, const void* x, int ldx, f
 
 inline int cap(size_t work) { size_t g = (work + 255) / 256; return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g)); }
 
-DropCfg drop_cfg(float p, uint64_t seed, uint32_t stream, bool on) {
-    DropCfg d;
-    d.seed = seed;
-    d.stream = stream;
-    uint32_t t = (on && p > 0.f) ? (uint32_t)lrintf(p * 65536.0f) : 0u;
-    if (t > 65535u) t = 65535u;
-    d.thresh16 = t;
-    d.keep_scale = 1.0f / (1.0f - (float)t / 65536.0f);
-    return d;
-}
-
 }  // namespace
 
 struct mmhip_early {
@@ -245,79 +220,60 @@ struct mmhip_early {
 namespace {
 
 // ------------------------------------------------------------------------------------------------ layout
-struct Builder {
-    mmhip_early& e;
-    size_t off = 0;
-    size_t add(const std::string& name, int group, std::initializer_list<int64_t> dims) {
-        mmhip_param_info p;
-        memset(&p, 0, sizeof(p));
-        strncpy(p.name, name.c_str(), sizeof(p.name) - 1);
-        p.ndim = (int)dims.size();
-        size_t n = 1;
-        int i = 0;
-        for (auto d : dims) { p.dims[i++] = d; n *= (size_t)d; }
-        p.buffer = 1;
-        p.group = group;
-        p.offset = off;
-        p.numel = n;
-        e.params.push_back(p);
-        off += (n + 3) & ~(size_t)3;
-        return (size_t)p.offset;
-    }
-};
+// One flat buffer: every parameter goes to buffer 1 of the table (mmhip_host.h ParamTable).
 // HF LxmertAttention + LxmertAttentionOutput (transformers 4.25.1 names): <n>.<inner>.{query,key,value}, <n>.output.dense, <n>.output.LayerNorm.
 // Q / K / V weights adjacent, then their biases: [Wq; Wk; Wv] is one [3H, H] matrix of the flat buffer.
-void add_att(Builder& b, const std::string& n, const char* inner, int H, AttOff& o) {
+void add_att(ParamTable& b, const std::string& n, const char* inner, int H, AttOff& o) {
     const int g = MMHIP_G_ALWAYS;
     const std::string q = n + "." + inner + ".";
-    o.qkv_w = b.add(q + "query.weight", g, {H, H});
-    b.add(q + "key.weight", g, {H, H});
-    b.add(q + "value.weight", g, {H, H});
-    o.qkv_b = b.add(q + "query.bias", g, {H});
-    b.add(q + "key.bias", g, {H});
-    b.add(q + "value.bias", g, {H});
-    o.o_w = b.add(n + ".output.dense.weight", g, {H, H});
-    o.o_b = b.add(n + ".output.dense.bias", g, {H});
-    o.ln_w = b.add(n + ".output.LayerNorm.weight", g, {H});
-    o.ln_b = b.add(n + ".output.LayerNorm.bias", g, {H});
+    o.qkv_w = b.add(q + "query.weight", 1, g, {H, H});
+    b.add(q + "key.weight", 1, g, {H, H});
+    b.add(q + "value.weight", 1, g, {H, H});
+    o.qkv_b = b.add(q + "query.bias", 1, g, {H});
+    b.add(q + "key.bias", 1, g, {H});
+    b.add(q + "value.bias", 1, g, {H});
+    o.o_w = b.add(n + ".output.dense.weight", 1, g, {H, H});
+    o.o_b = b.add(n + ".output.dense.bias", 1, g, {H});
+    o.ln_w = b.add(n + ".output.LayerNorm.weight", 1, g, {H});
+    o.ln_b = b.add(n + ".output.LayerNorm.bias", 1, g, {H});
 }
-void add_ffn(Builder& b, const std::string& inter, const std::string& out, int H, int I, FfnOff& o) {
+void add_ffn(ParamTable& b, const std::string& inter, const std::string& out, int H, int I, FfnOff& o) {
     const int g = MMHIP_G_ALWAYS;
-    o.w1 = b.add(inter + ".dense.weight", g, {I, H});
-    o.b1 = b.add(inter + ".dense.bias", g, {I});
-    o.w2 = b.add(out + ".dense.weight", g, {H, I});
-    o.b2 = b.add(out + ".dense.bias", g, {H});
-    o.ln_w = b.add(out + ".LayerNorm.weight", g, {H});
-    o.ln_b = b.add(out + ".LayerNorm.bias", g, {H});
+    o.w1 = b.add(inter + ".dense.weight", 1, g, {I, H});
+    o.b1 = b.add(inter + ".dense.bias", 1, g, {I});
+    o.w2 = b.add(out + ".dense.weight", 1, g, {H, I});
+    o.b2 = b.add(out + ".dense.bias", 1, g, {H});
+    o.ln_w = b.add(out + ".LayerNorm.weight", 1, g, {H});
+    o.ln_b = b.add(out + ".LayerNorm.bias", 1, g, {H});
 }
 
 void build_layout(mmhip_early& e) {
     const mmhip_early_config& c = e.cfg;
     const int H = c.hidden, I = c.inter, C = c.num_labels;
-    Builder b{e};
+    ParamTable b{e.params};
     // never: the pooler is off the path (mm_early.py:132 takes the CLS row itself); ITC: logit_scale; ITM: linear_tim
-    e.pool_w = b.add("model.pooler.dense.weight", MMHIP_G_NEVER, {H, H});
-    e.pool_b = b.add("model.pooler.dense.bias", MMHIP_G_NEVER, {H});
-    e.heads_begin = b.off;
-    e.logit_scale = b.add("logit_scale", MMHIP_G_ITC, {});
-    e.tim_w = b.add("linear_tim.weight", MMHIP_G_ITM, {2, H});
-    e.tim_b = b.add("linear_tim.bias", MMHIP_G_ITM, {2});
-    e.fus_w = b.add("linear_fusion.weight", MMHIP_G_ALWAYS, {H, H});
-    e.fus_b = b.add("linear_fusion.bias", MMHIP_G_ALWAYS, {H});
-    e.lin_w = b.add("linear.weight", MMHIP_G_ALWAYS, {C, H});
-    e.lin_b = b.add("linear.bias", MMHIP_G_ALWAYS, {C});
-    e.heads_end = b.off;
+    e.pool_w = b.add("model.pooler.dense.weight", 1, MMHIP_G_NEVER, {H, H});
+    e.pool_b = b.add("model.pooler.dense.bias", 1, MMHIP_G_NEVER, {H});
+    e.heads_begin = b.off[1];
+    e.logit_scale = b.add("logit_scale", 1, MMHIP_G_ITC, {});
+    e.tim_w = b.add("linear_tim.weight", 1, MMHIP_G_ITM, {2, H});
+    e.tim_b = b.add("linear_tim.bias", 1, MMHIP_G_ITM, {2});
+    e.fus_w = b.add("linear_fusion.weight", 1, MMHIP_G_ALWAYS, {H, H});
+    e.fus_b = b.add("linear_fusion.bias", 1, MMHIP_G_ALWAYS, {H});
+    e.lin_w = b.add("linear.weight", 1, MMHIP_G_ALWAYS, {C, H});
+    e.lin_b = b.add("linear.bias", 1, MMHIP_G_ALWAYS, {C});
+    e.heads_end = b.off[1];
     e.xl.resize(c.x_layers);
     for (int i = c.x_layers - 1; i >= 0; --i) {
         XLayer& x = e.xl[i];
         const std::string p = "model.encoder.x_layers." + std::to_string(i) + ".";
-        x.begin = b.off;
+        x.begin = b.off[1];
         add_ffn(b, p + "lang_inter", p + "lang_output", H, I, x.lffn);
         add_ffn(b, p + "visn_inter", p + "visn_output", H, I, x.vffn);
         add_att(b, p + "lang_self_att", "self", H, x.lself);
         add_att(b, p + "visn_self_att", "self", H, x.vself);
         add_att(b, p + "visual_attention", "att", H, x.cross);
-        x.end = b.off;
+        x.end = b.off[1];
     }
     e.lang.resize(c.l_layers);
     e.rel.resize(c.r_layers);
@@ -327,46 +283,41 @@ void build_layout(mmhip_early& e) {
         if (li >= 0) {
             PlainLayer& l = e.lang[li];
             const std::string p = "model.encoder.layer." + std::to_string(li) + ".";
-            l.begin = b.off;
+            l.begin = b.off[1];
             add_ffn(b, p + "intermediate", p + "output", H, I, l.ffn);
             add_att(b, p + "attention", "self", H, l.att);
-            l.end = b.off;
+            l.end = b.off[1];
         }
         if (ri >= 0) {
             PlainLayer& l = e.rel[ri];
             const std::string p = "model.encoder.r_layers." + std::to_string(ri) + ".";
-            l.begin = b.off;
+            l.begin = b.off[1];
             add_ffn(b, p + "intermediate", p + "output", H, I, l.ffn);
             add_att(b, p + "attention", "self", H, l.att);
-            l.end = b.off;
+            l.end = b.off[1];
         }
     }
     const std::string v = "model.encoder.visn_fc.";
-    e.vin_begin = b.off;
-    e.visn_fc_w = b.add(v + "visn_fc.weight", MMHIP_G_ALWAYS, {H, c.feat_dim});
-    e.visn_fc_b = b.add(v + "visn_fc.bias", MMHIP_G_ALWAYS, {H});
-    e.visn_ln_w = b.add(v + "visn_layer_norm.weight", MMHIP_G_ALWAYS, {H});
-    e.visn_ln_b = b.add(v + "visn_layer_norm.bias", MMHIP_G_ALWAYS, {H});
-    e.box_fc_w = b.add(v + "box_fc.weight", MMHIP_G_ALWAYS, {H, c.pos_dim});
-    e.box_fc_b = b.add(v + "box_fc.bias", MMHIP_G_ALWAYS, {H});
-    e.box_ln_w = b.add(v + "box_layer_norm.weight", MMHIP_G_ALWAYS, {H});
-    e.box_ln_b = b.add(v + "box_layer_norm.bias", MMHIP_G_ALWAYS, {H});
-    e.vin_end = b.off;
+    e.vin_begin = b.off[1];
+    e.visn_fc_w = b.add(v + "visn_fc.weight", 1, MMHIP_G_ALWAYS, {H, c.feat_dim});
+    e.visn_fc_b = b.add(v + "visn_fc.bias", 1, MMHIP_G_ALWAYS, {H});
+    e.visn_ln_w = b.add(v + "visn_layer_norm.weight", 1, MMHIP_G_ALWAYS, {H});
+    e.visn_ln_b = b.add(v + "visn_layer_norm.bias", 1, MMHIP_G_ALWAYS, {H});
+    e.box_fc_w = b.add(v + "box_fc.weight", 1, MMHIP_G_ALWAYS, {H, c.pos_dim});
+    e.box_fc_b = b.add(v + "box_fc.bias", 1, MMHIP_G_ALWAYS, {H});
+    e.box_ln_w = b.add(v + "box_layer_norm.weight", 1, MMHIP_G_ALWAYS, {H});
+    e.box_ln_b = b.add(v + "box_layer_norm.bias", 1, MMHIP_G_ALWAYS, {H});
+    e.vin_end = b.off[1];
     const std::string em = "model.embeddings.";
-    e.emb_begin = b.off;
-    e.eln_w = b.add(em + "LayerNorm.weight", MMHIP_G_ALWAYS, {H});
-    e.eln_b = b.add(em + "LayerNorm.bias", MMHIP_G_ALWAYS, {H});
-    e.type = b.add(em + "token_type_embeddings.weight", MMHIP_G_ALWAYS, {c.type_vocab, H});
-    e.pos = b.add(em + "position_embeddings.weight", MMHIP_G_ALWAYS, {c.max_pos, H});
-    e.word = b.add(em + "word_embeddings.weight", MMHIP_G_ALWAYS, {c.vocab, H});
-    e.emb_end = b.off;
-    e.n_params = b.off;
+    e.emb_begin = b.off[1];
+    e.eln_w = b.add(em + "LayerNorm.weight", 1, MMHIP_G_ALWAYS, {H});
+    e.eln_b = b.add(em + "LayerNorm.bias", 1, MMHIP_G_ALWAYS, {H});
+    e.type = b.add(em + "token_type_embeddings.weight", 1, MMHIP_G_ALWAYS, {c.type_vocab, H});
+    e.pos = b.add(em + "position_embeddings.weight", 1, MMHIP_G_ALWAYS, {c.max_pos, H});
+    e.word = b.add(em + "word_embeddings.weight", 1, MMHIP_G_ALWAYS, {c.vocab, H});
+    e.emb_end = b.off[1];
+    e.n_params = b.off[1];
 }
-
-struct Carver {
-    size_t off = 0;
-    size_t take(size_t bytes) { size_t r = off; off += (bytes + 255) & ~(size_t)255; return r; }
-};
 
 void build_workspace(mmhip_early& e) {
     const mmhip_early_config& c = e.cfg;
@@ -457,11 +408,7 @@ int refresh(mmhip_early& e, hipStream_t s) {
     for (auto& x : e.xl) { att(x.cross, x.cw); att(x.lself, x.lw); att(x.vself, x.vw); ffn(x.lffn, x.lfw); ffn(x.vffn, x.vfw); }
     add(e.visn_fc_w, e.c_visn_fc, H, c.feat_dim);
     add(e.box_fc_w, e.c_box_fc, H, c.pos_dim);
-    for (size_t i = 0; i < mats.size(); i += CAST_MAX_GROUP) {
-        const int n = (int)(mats.size() - i < (size_t)CAST_MAX_GROUP ? mats.size() - i : (size_t)CAST_MAX_GROUP);
-        CHECK_HIP(launch_cast_group(mats.data() + i, n, e.dt(), s));
-    }
-    return 0;
+    return launch_cast_groups(mats, e.dt(), s);
 }
 
 // dropout seeds: one 64-bit seed per block and call, derived from the call's seed (the block operators use fixed stream ids inside)
@@ -491,16 +438,10 @@ int cross_fwd(mmhip_early& e, const AttOff& o, const AttW& w, CrossAct& a, const
 struct TNQueue {
     std::vector<GemmTNProblem> q;
     void add(const void* dy, int lda, const void* x, int ldb, float* C, int M, int Nn, int Nc, float* colsum) {
-        GemmTNProblem p;
-        memset(&p, 0, sizeof(p));
-        p.A = dy; p.B = x; p.C = C; p.M = M; p.Nn = Nn; p.Nc = Nc; p.lda = lda; p.ldb = ldb; p.ldc = Nc; p.colsum = colsum;
-        q.push_back(p);
+        q.push_back(GemmTNProblem{dy, x, C, M, Nn, Nc, lda, ldb, Nc, 0, colsum});
     }
     int flush(int dtype, int accumulate, hipStream_t s) {
-        for (size_t i = 0; i < q.size(); i += GEMM_TN_MAX_GROUP) {
-            const int n = (int)(q.size() - i < (size_t)GEMM_TN_MAX_GROUP ? q.size() - i : (size_t)GEMM_TN_MAX_GROUP);
-            CHECK_HIP(launch_gemm_tn(q.data() + i, n, accumulate, dtype, 0, s, 1.0f));
-        }
+        CHECK_RC(launch_tn_groups(q, accumulate, dtype, s));
         q.clear();
         return 0;
     }
@@ -557,13 +498,12 @@ int encoder_forward(mmhip_early& e, const float* feats, const float* boxes, hipS
     CHECK_RC(order(e, e.ev_fork, s, sv));
     // ---- language stream: embeddings (word + position 0..T-1 + token type -> LayerNorm -> dropout), key bias from the attention mask
     {
-        EmbedArgs ea;
-        memset(&ea, 0, sizeof(ea));
+        EmbedArgs ea{};
         ea.ids = e.wsp<int64_t>(e.ids_all); ea.mask = e.wsp<int64_t>(e.mask_all); ea.type_ids = e.wsp<int64_t>(e.tt_all);
         ea.word = e.P + e.word; ea.pos = e.P + e.pos; ea.type = e.P + e.type; ea.gamma = e.P + e.eln_w; ea.beta = e.P + e.eln_b;
         ea.x = e.ws + e.x0; ea.xhat = e.ws + e.xhat; ea.rstd = e.wsp<float>(e.rstd_emb); ea.pos_ids = e.wsp<int>(e.pos_ids); ea.maskbias = e.wsp<float>(e.lbias);
         ea.posts = Bt; ea.T = T; ea.H = H; ea.xlmr = 0; ea.pad_id = 0; ea.eps = c.ln_eps;
-        ea.drop = drop_cfg(c.p_hidden, e.seed, 1, e.train);
+        ea.drop = make_drop(c.p_hidden, e.seed, 1, e.train);
         CHECK_HIP(launch_embed_fwd(ea, dt, s));
         if (T < S) {          // key bias of the text at the packed cross-attention length (keys past T masked)
             hipLaunchKernelGGL(pad_bias_kernel, dim3((Bt * S + 255) / 256), dim3(256), 0, s, e.wsp<float>(e.lbias), e.wsp<float>(e.lbias_x), Bt, T, S);
@@ -581,20 +521,13 @@ int encoder_forward(mmhip_early& e, const float* feats, const float* boxes, hipS
             CHECK_HIP(launch_cast(feats, e.ws + e.feats16 + (size_t)half * nf * Z, nf, dt, sv));
             CHECK_HIP(launch_cast(boxes, e.ws + e.boxes16 + (size_t)half * nb * Z, nb, dt, sv));
         }
-        GemmNTArgs a;
-        memset(&a, 0, sizeof(a));
-        a.A = e.ws + e.feats16; a.lda = c.feat_dim; a.B = e.ws + e.c_visn_fc.w; a.ldb = c.feat_dim; a.C = e.ws + e.vf_pre; a.ldc = H; a.M = MV; a.N = H; a.K = c.feat_dim;
-        a.bias = e.P + e.visn_fc_b; a.flags = GEMM_BIAS;
-        CHECK_HIP(launch_gemm_nt(a, dt, sv));
+        CHECK_HIP(launch_gemm_nt(G(e.ws + e.feats16, c.feat_dim, e.ws + e.c_visn_fc.w, c.feat_dim, e.ws + e.vf_pre, H, MV, H, c.feat_dim).bias(e.P + e.visn_fc_b).a, dt, sv));
         LNArgs l1{e.ws + e.vf_pre, e.ws + e.vf, e.P + e.visn_ln_w, e.P + e.visn_ln_b, e.wsp<float>(e.vf_mean), e.wsp<float>(e.vf_rstd), MV, H, H, H, c.ln_eps};
         CHECK_HIP(launch_layernorm_fwd(l1, dt, sv));
-        memset(&a, 0, sizeof(a));
-        a.A = e.ws + e.boxes16; a.lda = c.pos_dim; a.B = e.ws + e.c_box_fc.w; a.ldb = c.pos_dim; a.C = e.ws + e.bx_pre; a.ldc = H; a.M = MV; a.N = H; a.K = c.pos_dim;
-        a.bias = e.P + e.box_fc_b; a.flags = GEMM_BIAS;
-        CHECK_HIP(launch_gemm_nt(a, dt, sv));
+        CHECK_HIP(launch_gemm_nt(G(e.ws + e.boxes16, c.pos_dim, e.ws + e.c_box_fc.w, c.pos_dim, e.ws + e.bx_pre, H, MV, H, c.pos_dim).bias(e.P + e.box_fc_b).a, dt, sv));
         LNArgs l2{e.ws + e.bx_pre, e.ws + e.bx, e.P + e.box_ln_w, e.P + e.box_ln_b, e.wsp<float>(e.bx_mean), e.wsp<float>(e.bx_rstd), MV, H, H, H, c.ln_eps};
         CHECK_HIP(launch_layernorm_fwd(l2, dt, sv));
-        CHECK_HIP(launch_avg_drop(e.ws + e.bx, e.ws + e.vf, e.ws + e.v0, (size_t)MV * H, 0.5f, drop_cfg(c.p_hidden, e.seed, 2, e.train), dt, sv));
+        CHECK_HIP(launch_avg_drop(e.ws + e.bx, e.ws + e.vf, e.ws + e.v0, (size_t)MV * H, 0.5f, make_drop(c.p_hidden, e.seed, 2, e.train), dt, sv));
     }
     const char* lang = e.ws + e.x0;
     const char* visn = e.ws + e.v0;
@@ -636,13 +569,6 @@ int encoder_forward(mmhip_early& e, const float* feats, const float* boxes, hipS
 const char* lang_final(const mmhip_early& e) { return !e.xl.empty() ? e.ws + e.xl.back().fl.y : (!e.lang.empty() ? e.ws + e.lang.back().fa.y : e.ws + e.x0); }
 const char* visn_final(const mmhip_early& e) { return !e.xl.empty() ? e.ws + e.xl.back().fv.y : (!e.rel.empty() ? e.ws + e.rel.back().fa.y : e.ws + e.v0); }
 
-SmallGemmArgs small(const void* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldo, int M, int N, int K, int act = ACT_NONE, int acc = 0) {
-    SmallGemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.A = A; a.W = W; a.bias = bias; a.out = out; a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldw = ldw; a.ldo = ldo; a.act = act; a.accumulate = acc;
-    return a;
-}
-
 // reference models/mm_early.py:128-163: linear_output = linear(dropout(relu(linear_fusion(x_t[:, 0])))); the text / image embeddings of the ITC loss are
 // max-pools over the tokens (masked, detached) and the boxes; out_tim = linear_tim(CLS row of the swapped-text pass)
 int heads_forward(mmhip_early& e, float* out, float* emb_t, float* emb_v, float* out_tim, hipStream_t s) {
@@ -651,7 +577,7 @@ int heads_forward(mmhip_early& e, float* out, float* emb_t, float* emb_v, float*
     float* z = e.wsp<float>(e.h_z);
     CHECK_HIP(launch_gather_rows_f32(lang_final(e), (size_t)T * H, z, H, Bt, H, dt, s));
     CHECK_HIP(launch_small_nt(small(z, H, e.P + e.fus_w, H, e.P + e.fus_b, e.wsp<float>(e.h_fus), H, B, H, H, ACT_RELU), DT_F32, s));
-    CHECK_HIP(launch_elementwise(EW_DROPOUT, e.wsp<float>(e.h_fus), nullptr, e.wsp<float>(e.h_fusd), (size_t)B * H, 0.f, drop_cfg(c.p_head, e.seed, 3, e.train), s));
+    CHECK_HIP(launch_elementwise(EW_DROPOUT, e.wsp<float>(e.h_fus), nullptr, e.wsp<float>(e.h_fusd), (size_t)B * H, 0.f, make_drop(c.p_head, e.seed, 3, e.train), s));
     CHECK_HIP(launch_small_nt(small(e.wsp<float>(e.h_fusd), H, e.P + e.lin_w, H, e.P + e.lin_b, e.wsp<float>(e.h_out), C, B, C, H), DT_F32, s));
     if (e.itm) CHECK_HIP(launch_small_nt(small(z + (size_t)B * H, H, e.P + e.tim_w, H, e.P + e.tim_b, e.wsp<float>(e.h_tim), 2, B, 2, H), DT_F32, s));
     const int grid = (B * (H / 4) + 255) / 256;
@@ -678,14 +604,14 @@ int heads_forward(mmhip_early& e, float* out, float* emb_t, float* emb_v, float*
 int heads_backward(mmhip_early& e, hipStream_t s) {
     const mmhip_early_config& c = e.cfg;
     const int H = c.hidden, C = c.num_labels, B = e.B, Bt = e.Bt, T = e.T, Nb = e.Nb, dt = e.dt();
-    const DropCfg nodrop = drop_cfg(0.f, 0, 0, false);
+    const DropCfg nodrop = make_drop(0.f, 0, 0, false);
     float* z = e.wsp<float>(e.h_z);
     float* dz = e.wsp<float>(e.h_dz);
     float* dfusd = e.wsp<float>(e.h_dfusd);
     float* dfus = e.wsp<float>(e.h_dfus);
     const float* d_out = e.bd_out;
     CHECK_HIP(launch_small_nn(small(d_out, C, e.P + e.lin_w, H, nullptr, dfusd, H, B, H, C), s));
-    CHECK_HIP(launch_elementwise(EW_DROPOUT, dfusd, nullptr, dfusd, (size_t)B * H, 0.f, drop_cfg(c.p_head, e.seed, 3, e.train), s));
+    CHECK_HIP(launch_elementwise(EW_DROPOUT, dfusd, nullptr, dfusd, (size_t)B * H, 0.f, make_drop(c.p_head, e.seed, 3, e.train), s));
     CHECK_HIP(launch_small_tn(small(d_out, C, e.wsp<float>(e.h_fusd), H, nullptr, e.G + e.lin_w, H, B, H, 0, 0, 1), DT_F32, C, s));
     CHECK_HIP(launch_bias_grad_f32(d_out, B, C, C, e.G + e.lin_b, 1, s));
     CHECK_HIP(launch_elementwise(EW_RELU_BWD, dfusd, e.wsp<float>(e.h_fus), dfus, (size_t)B * H, 0.f, nodrop, s));
@@ -738,11 +664,7 @@ int stage_refresh(mmhip_early& e, int stage, hipStream_t s) {
         if (li >= 0) { att(e.lang[li].att, e.lang[li].aw); ffn(e.lang[li].ffn, e.lang[li].fw); }
         if (ri >= 0) { att(e.rel[ri].att, e.rel[ri].aw); ffn(e.rel[ri].ffn, e.rel[ri].fw); }
     }
-    for (size_t i = 0; i < mats.size(); i += CAST_MAX_GROUP) {
-        const int n = (int)(mats.size() - i < (size_t)CAST_MAX_GROUP ? mats.size() - i : (size_t)CAST_MAX_GROUP);
-        CHECK_HIP(launch_cast_group(mats.data() + i, n, e.dt(), s));
-    }
-    return 0;
+    return launch_cast_groups(mats, e.dt(), s);
 }
 
 // stage: 0 heads | 1 .. X cross-modality layers last -> first | X+1 .. X+D language / relational layers by depth below the cross layers | X+D+1 inputs
@@ -822,22 +744,20 @@ int backward_stage(mmhip_early& e, int stage, const char** dlang_io, const char*
     }
     // ---- inputs: embeddings on the language stream, the visual-feature encoder on the vision stream
     {
-        EmbedBwdArgs b;
-        memset(&b, 0, sizeof(b));
+        EmbedBwdArgs b{};
         b.dx = *dlang_io; b.xhat = e.ws + e.xhat; b.rstd = e.wsp<float>(e.rstd_emb); b.gamma = e.P + e.eln_w;
         b.ids = e.wsp<int64_t>(e.ids_all); b.pos_ids = e.wsp<int>(e.pos_ids); b.type_ids = e.wsp<int64_t>(e.tt_all);
         b.dword = e.G + e.word; b.dpos = e.G + e.pos; b.dtype = e.G + e.type; b.dgamma = e.G + e.eln_w; b.dbeta = e.G + e.eln_b;
         b.posts = Bt; b.T = T; b.H = H; b.pad_id = 0; b.pos_pad_id = 0;          // HF LxmertEmbeddings: padding_idx = 0 on all three tables
-        b.drop = drop_cfg(c.p_hidden, e.seed, 1, e.train);
+        b.drop = make_drop(c.p_hidden, e.seed, 1, e.train);
         b.partial = e.wsp<float>(e.g_partial);
         b.alpha = 1.0f;
         CHECK_HIP(launch_embed_bwd(b, dt, s));
     }
     {
         // visn = dropout((f + bx) / 2): d f = d bx = dropout-backward(d visn) / 2
-        CHECK_HIP(launch_avg_drop(*dvisn_io, nullptr, e.ws + e.dv0, (size_t)MV * H, 0.5f, drop_cfg(c.p_hidden, e.seed, 2, e.train), dt, sv));
-        LNBwdArgs b1;
-        memset(&b1, 0, sizeof(b1));
+        CHECK_HIP(launch_avg_drop(*dvisn_io, nullptr, e.ws + e.dv0, (size_t)MV * H, 0.5f, make_drop(c.p_hidden, e.seed, 2, e.train), dt, sv));
+        LNBwdArgs b1{};
         b1.dy = e.ws + e.dv0; b1.x = e.ws + e.vf_pre; b1.gamma = e.P + e.visn_ln_w; b1.mean = e.wsp<float>(e.vf_mean); b1.rstd = e.wsp<float>(e.vf_rstd);
         b1.dx = e.ws + e.dvf_pre; b1.dgamma = e.G + e.visn_ln_w; b1.dbeta = e.G + e.visn_ln_b; b1.rows = MV; b1.width = H; b1.alpha = 1.0f;
         CHECK_HIP(launch_layernorm_bwd(b1, dt, sv));
@@ -1019,8 +939,7 @@ int mmhip_early_loss(mmhip_early_handle h, const int64_t* onehot, const float* c
         e.itc_done = true;
         if (logits_per_text) CHECK_HIP(hipMemcpyAsync(logits_per_text, e.ws + e.h_logits, (size_t)B * B * 4, hipMemcpyDeviceToDevice, s));
     }
-    LossArgs a;
-    memset(&a, 0, sizeof(a));
+    LossArgs a{};
     a.out_cls = e.wsp<float>(e.h_out); a.onehot = onehot; a.class_w = class_w;
     a.logits_per_text = w_itc != 0.f ? e.wsp<float>(e.h_logits) : nullptr;
     a.out_tim = w_itm != 0.f ? e.wsp<float>(e.h_tim) : nullptr; a.lbl_tim = lbl_tim;
@@ -1102,8 +1021,7 @@ int mmhip_early_train_step(mmhip_early_handle h, const int64_t* ids, const int64
     CHECK_RC(forward_impl(h, ids, mask, token_type_ids, feats, boxes, nullptr, nullptr, nullptr, use_itm ? itm_src : nullptr, B, T, Nb, 1, seed, nullptr, nullptr, nullptr,
                           nullptr, stream));
     CHECK_RC(mmhip_early_loss(h, onehot, class_w, use_itm ? lbl_tim : nullptr, w_cls, use_itc ? w_itc : 0.f, use_itm ? w_itm : 0.f, loss, nullptr, stream));
-    AdamWArgs a;
-    memset(&a, 0, sizeof(a));
+    AdamWArgs a{};
     a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = weight_decay;
     a.bc1 = (float)(1.0 - pow((double)beta1, step));
     a.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, step));

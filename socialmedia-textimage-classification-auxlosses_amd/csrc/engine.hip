@@ -3,13 +3,10 @@
 // Everything is enqueued on the caller's stream from this single C++ call path: no per-op host round trip.
 #include <string>
 #include <vector>
-#include <cstring>
-#include <cmath>
 #include <cstdlib>
 #include <cstdio>
 #include "mmhip_common.h"
-#include "mmhip_kernels.h"
-#include "../../include/mmhip.h"
+#include "mmhip_host.h"
 
 using namespace mmhip;
 
@@ -25,13 +22,6 @@ struct TextAct {    // saved activations of one text layer (byte offsets into th
     size_t qkv, ctx, pre1, a1, u, h, pre2, out, mean1, rstd1, mean2, rstd2, lse;
     size_t a1p, outp;      // parity mode with plane pairs: the LayerNorm outputs once more as pairs (the fp32 forms stay the residual inputs)
 };
-struct Stream16 { size_t off; };
-
-#define CHECK_HIP(expr)                       \
-    do {                                      \
-        hipError_t _e = (expr);               \
-        if (_e != hipSuccess) return (int)_e; \
-    } while (0)
 
 }  // namespace
 
@@ -139,28 +129,7 @@ struct mmhip_engine {
 namespace {
 
 // ------------------------------------------------------------------------------------------------ layout
-struct Builder {
-    mmhip_engine& e;
-    size_t off[2] = {0, 0};
-    size_t add(const std::string& name, int buffer, int group, std::initializer_list<int64_t> dims) {
-        mmhip_param_info p;
-        memset(&p, 0, sizeof(p));
-        strncpy(p.name, name.c_str(), sizeof(p.name) - 1);
-        p.ndim = (int)dims.size();
-        size_t n = 1;
-        int i = 0;
-        for (auto d : dims) { p.dims[i++] = d; n *= (size_t)d; }
-        p.buffer = buffer;
-        p.group = group;
-        p.offset = off[buffer];
-        p.numel = n;
-        e.params.push_back(p);
-        off[buffer] += (n + 3) & ~(size_t)3;      // keep every tensor 16-byte aligned
-        return (size_t)p.offset;
-    }
-};
-
-void add_text_layer(Builder& b, const mmhip_config& c, int l, LayerOff& o) {
+void add_text_layer(ParamTable& b, const mmhip_config& c, int l, LayerOff& o) {
     const int H = c.hidden, I = c.inter;
     const std::string p = "dual_encoder.text_model.encoder.layer." + std::to_string(l) + ".";
     const int g = MMHIP_G_ALWAYS;
@@ -185,7 +154,7 @@ void add_text_layer(Builder& b, const mmhip_config& c, int l, LayerOff& o) {
 }
 // CLIP vision layer, transformers 4.25.1 keys (CLIPVisionModel wraps the transformer as `.vision_model`):
 // HF:models/clip/modeling_clip.py (CLIPEncoderLayer: pre-LN, quick-GELU MLP)
-void add_clip_layer(Builder& b, int H, int I, int l, LayerOff& o) {
+void add_clip_layer(ParamTable& b, int H, int I, int l, LayerOff& o) {
     const std::string p = "dual_encoder.vision_model.vision_model.encoder.layers." + std::to_string(l) + ".";
     const int g = MMHIP_G_FROZEN;
     o.begin = b.off[0];
@@ -207,7 +176,7 @@ void add_clip_layer(Builder& b, int H, int I, int l, LayerOff& o) {
     o.ln2_b = b.add(p + "layer_norm2.bias", 0, g, {H});
     o.end = b.off[0];
 }
-void add_vit_layer(Builder& b, const mmhip_config& c, int l, LayerOff& o) {
+void add_vit_layer(ParamTable& b, const mmhip_config& c, int l, LayerOff& o) {
     const int H = c.hidden_img > 0 ? c.hidden_img : c.hidden, I = c.inter_img > 0 ? c.inter_img : c.inter;
     const std::string p = "dual_encoder.vision_model.encoder.layer." + std::to_string(l) + ".";
     const int g = MMHIP_G_FROZEN;
@@ -234,7 +203,7 @@ void add_vit_layer(Builder& b, const mmhip_config& c, int l, LayerOff& o) {
 void build_layout(mmhip_engine& e) {
     const mmhip_config& c = e.cfg;
     const int H = c.hidden, C = c.num_labels, E = c.proj_dim, P = e.P(), Hv = e.Hv();
-    Builder b{e};
+    ParamTable b{e.params};
     // ---- frozen: vision tower (every dual_encoder parameter with 'vision' in its name, mm_late.py:67-69)
     e.vit.resize(c.layers_img);
     if (e.clip()) {
@@ -302,11 +271,6 @@ void build_layout(mmhip_engine& e) {
     e.n_frozen = b.off[0];
     e.n_train = b.off[1];
 }
-
-struct Carver {
-    size_t off = 0;
-    size_t take(size_t bytes) { size_t r = off; off += (bytes + 255) & ~(size_t)255; return r; }
-};
 
 void build_workspace(mmhip_engine& e) {
     const mmhip_config& c = e.cfg;
@@ -386,44 +350,16 @@ void build_workspace(mmhip_engine& e) {
     e.ws_need = w.off;
 }
 
-DropCfg make_drop(float p, uint64_t seed, uint32_t stream, bool on) {
-    DropCfg d;
-    d.seed = seed;
-    d.stream = stream;
-    uint32_t t = on ? (uint32_t)lrintf(p * 65536.0f) : 0u;
-    if (t > 65535u) t = 65535u;
-    d.thresh16 = t;
-    d.keep_scale = 1.0f / (1.0f - (float)t / 65536.0f);
-    return d;
-}
 enum { STREAM_EMBED = 1, STREAM_HEAD = 2 };
 inline uint32_t stream_attn(int l) { return 16 + 4 * l; }
 inline uint32_t stream_attn_out(int l) { return 16 + 4 * l + 1; }
 inline uint32_t stream_ffn_out(int l) { return 16 + 4 * l + 2; }
 
 // ------------------------------------------------------------------------------------------------ GEMM helper
-struct G {
-    GemmNTArgs a;
-    G(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K) {
-        memset(&a, 0, sizeof(a));
-        a.A = A; a.lda = lda; a.B = B; a.ldb = ldb; a.C = C; a.ldc = ldc; a.M = M; a.N = N; a.K = K;
-    }
-    G& bias(const float* b) { a.bias = b; a.flags |= GEMM_BIAS; return *this; }
-    G& gelu() { a.flags |= GEMM_GELU; return *this; }
-    G& qgelu() { a.flags |= GEMM_QGELU; return *this; }
-    G& aux(void* p, int ld) { a.aux = p; a.ldaux = ld; a.flags |= GEMM_AUX_PRE; return *this; }
-    G& residual(const void* p, int ld) { a.residual = p; a.ldres = ld; a.flags |= GEMM_RESIDUAL; return *this; }
-    G& mul_gelu_grad(const void* p, int ld) { a.mul_in = p; a.ldmul = ld; a.flags |= GEMM_MUL_GELU_GRAD; return *this; }
-    G& dropout(const DropCfg& d, int row_mul = 1) { a.drop = d; a.drop_row_mul = row_mul; if (d.thresh16) a.flags |= GEMM_DROPOUT; return *this; }
-    // parity mode with plane pairs: both operands are pairs whose rows hold [hi(W) | lo(W)] -- the leading dimensions given in logical
-    // elements double, the lo planes sit K elements behind; px_out: C as a pair, rows [hi(N) | lo(N)]
-    G& px_in(bool px, int nprod = 0) { if (px) { a.a_pair = a.b_pair = 1; a.lda *= 2; a.ldb *= 2; a.a_lo = a.b_lo = a.K; a.nprod = nprod; } return *this; }
-    G& px_out(bool px, bool hi_only = false) { if (px) { a.flags |= GEMM_OUT_PAIR | (hi_only ? GEMM_OUT_PAIR_HI : 0); a.ldc *= 2; a.c_lo = a.N; } return *this; }
-};
 // forward GEMM of tower `which` (0 text, 1 image) under the CU partition: persistent 256 x 256 tiles on at most cur_part[which] workgroups
 inline void part_gemm(const mmhip_engine& e, G& g, int which) {
     const int n = e.cur_part[which];
-    if (n > 0 && !g.a.tile && g.a.M >= 2048 && g.a.N % 256 == 0 && g.a.K % 64 == 0 && (e.dt() == DT_BF16 || e.dt() == DT_F16)) { g.a.tile = 15; g.a.grid = n; }
+    if (n > 0 && !g.a.tile && g.a.M >= 2048 && g.a.N % 256 == 0 && g.a.K % 64 == 0 && (e.dt() == DT_BF16 || e.dt() == DT_F16)) g.tile(15).grid(n);
 }
 int run_gemm(mmhip_engine& e, G& g, hipStream_t s) {
     // GEMMs of <= 128 rows with K >= 1536 (the CLS-row GEMMs of the last text layer; a tiny image tower) are split along K
@@ -481,14 +417,8 @@ int run_gemm_pair(mmhip_engine& e, G& g0, G& g1, hipStream_t s) {
         }
         return 0;
     }
-    if (int r = run_gemm(e, g0, s)) return r;
+    CHECK_RC(run_gemm(e, g0, s));
     return run_gemm(e, g1, s);
-}
-SmallGemmArgs small(const void* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldo, int M, int N, int K, int act = ACT_NONE, int acc = 0) {
-    SmallGemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.A = A; a.W = W; a.bias = bias; a.out = out; a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldw = ldw; a.ldo = ldo; a.act = act; a.accumulate = acc;
-    return a;
 }
 
 // ------------------------------------------------------------------------------------------------ side stream
@@ -527,16 +457,13 @@ int vit_forward(mmhip_engine& e, const float* pixels, hipStream_t s) {
     const bool clip = e.clip();
     const float* F = e.frozen;
     const bool px = e.px;
-    auto ln_to = [&](LNArgs& ln, size_t pair_buf, int W) {          // parity mode: a LayerNorm output that only GEMMs read goes out as a plane pair only
-        if (px) { ln.y = nullptr; ln.y_pair = e.ws + pair_buf; ln.ld_pair = 2 * W; ln.lo_pair = W; }
-    };
     CHECK_HIP(launch_patchify(pixels, e.ws + e.v_patches, B, c.image, c.patch, Kpp, px ? DT_PAIR : dt, s));
     {
         G g(e.ws + e.v_patches, Kpp, e.ws + e.patch_w16, Kpp, e.ws + e.v_pe, H, B * (P - 1), H, Kpp);
         if (!clip) g.bias(F + e.v_patch_b);           // CLIP's patch conv has no bias
         g.px_in(px);
         part_gemm(e, g, 1);
-        if (int r = run_gemm(e, g, s)) return r;
+        CHECK_RC(run_gemm(e, g, s));
     }
     CHECK_HIP(launch_vit_assemble(e.ws + e.v_pe, F + e.v_cls, F + e.v_pos, e.ws + e.v_x, B, P, H, dt, s));
     char* x = e.ws + e.v_x;
@@ -548,21 +475,18 @@ int vit_forward(mmhip_engine& e, const float* pixels, hipStream_t s) {
         const LayerOff& o = e.vit[l];
         const LayerW16& w = e.vit_w16[l];
         LNArgs ln{x, e.ws + e.v_ln, F + o.ln1_w, F + o.ln1_b, nullptr, nullptr, Mv, H, H, H, c.ln_eps_img};
-        ln_to(ln, e.v_ln, H);
+        ln_pair(ln, px, e.ws + e.v_ln, true);          // only GEMMs read it: the pair alone
         CHECK_HIP(launch_layernorm_fwd(ln, dt, s));
-        { G g(e.ws + e.v_ln, H, e.ws + w.qkv, H, e.ws + e.v_qkv, 3 * H, Mv, 3 * H, H); g.bias(F + o.qkv_b).px_in(px).px_out(px); part_gemm(e, g, 1); if (int r = run_gemm(e, g, s)) return r; }
-        AttnArgs at;
-        memset(&at, 0, sizeof(at));
-        at.qkv = e.ws + e.v_qkv; at.ctx = e.ws + e.v_ctx; at.posts = B; at.S = P; at.heads = e.heads_v(); at.ld_qkv = 3 * H; at.ld_ctx = H; at.hidden = H;
-        if (px) { at.pair = 1; at.ld_qkv = 6 * H; at.lo_qkv = 3 * H; at.ld_ctx = 2 * H; at.lo_ctx = H; }
-        at.scale = 1.0f / sqrtf((float)(H / e.heads_v()));
+        { G g(e.ws + e.v_ln, H, e.ws + w.qkv, H, e.ws + e.v_qkv, 3 * H, Mv, 3 * H, H); g.bias(F + o.qkv_b).px_in(px).px_out(px); part_gemm(e, g, 1); CHECK_RC(run_gemm(e, g, s)); }
+        AttnArgs at = attn_args(e.ws + e.v_qkv, nullptr, e.ws + e.v_ctx, nullptr, B, P, e.heads_v(), H);
+        attn_pair(at, px);
         CHECK_HIP(launch_attn_fwd(at, dt, s));
-        { G g(e.ws + e.v_ctx, H, e.ws + w.ao, H, x, H, Mv, H, H); g.bias(F + o.ao_b).residual(x, H).px_in(px); part_gemm(e, g, 1); if (int r = run_gemm(e, g, s)) return r; }
+        { G g(e.ws + e.v_ctx, H, e.ws + w.ao, H, x, H, Mv, H, H); g.bias(F + o.ao_b).residual(x, H).px_in(px); part_gemm(e, g, 1); CHECK_RC(run_gemm(e, g, s)); }
         LNArgs ln2{x, e.ws + e.v_ln, F + o.ln2_w, F + o.ln2_b, nullptr, nullptr, Mv, H, H, H, c.ln_eps_img};
-        ln_to(ln2, e.v_ln, H);
+        ln_pair(ln2, px, e.ws + e.v_ln, true);          // only GEMMs read it: the pair alone
         CHECK_HIP(launch_layernorm_fwd(ln2, dt, s));
-        { G g(e.ws + e.v_ln, H, e.ws + w.fc1, H, e.ws + e.v_h, I, Mv, I, H); g.bias(F + o.fc1_b); if (clip) g.qgelu(); else g.gelu(); g.px_in(px).px_out(px); part_gemm(e, g, 1); if (int r = run_gemm(e, g, s)) return r; }
-        { G g(e.ws + e.v_h, I, e.ws + w.fc2, I, x, H, Mv, H, I); g.bias(F + o.fc2_b).residual(x, H).px_in(px); part_gemm(e, g, 1); if (int r = run_gemm(e, g, s)) return r; }
+        { G g(e.ws + e.v_ln, H, e.ws + w.fc1, H, e.ws + e.v_h, I, Mv, I, H); g.bias(F + o.fc1_b); if (clip) g.qgelu(); else g.gelu(); g.px_in(px).px_out(px); part_gemm(e, g, 1); CHECK_RC(run_gemm(e, g, s)); }
+        { G g(e.ws + e.v_h, I, e.ws + w.fc2, I, x, H, Mv, H, I); g.bias(F + o.fc2_b).residual(x, H).px_in(px); part_gemm(e, g, 1); CHECK_RC(run_gemm(e, g, s)); }
     }
     if (clip) {
         // last_hidden_state = the encoder output as it is; pooler_output = post_layernorm(CLS row)   (CLIPVisionTransformer.forward)
@@ -585,8 +509,7 @@ int text_forward(mmhip_engine& e, hipStream_t s) {
     const int H = c.hidden, I = c.inter, T = e.T, Bt = e.Bt, Mt = Bt * T, dt = e.dt();
     const float* W = e.train;
     const bool tr = e.train_mode;
-    EmbedArgs ea;
-    memset(&ea, 0, sizeof(ea));
+    EmbedArgs ea{};
     ea.ids = e.wsp<int64_t>(e.ids_all); ea.mask = e.wsp<int64_t>(e.mask_all);
     ea.word = W + e.t_word; ea.pos = W + e.t_pos; ea.type = W + e.t_type; ea.gamma = W + e.t_eln_w; ea.beta = W + e.t_eln_b;
     ea.x = e.ws + e.x0; ea.xhat = e.ws + e.xhat_emb; ea.rstd = e.wsp<float>(e.rstd_emb); ea.pos_ids = e.wsp<int>(e.pos_ids);
@@ -594,7 +517,7 @@ int text_forward(mmhip_engine& e, hipStream_t s) {
     ea.posts = Bt; ea.T = T; ea.H = H; ea.xlmr = c.txt_kind == MMHIP_TXT_XLMR; ea.pad_id = c.pad_id; ea.eps = c.ln_eps_txt;
     ea.drop = make_drop(c.p_hidden, e.seed, STREAM_EMBED, tr);
     const bool px = e.px;
-    if (px) { ea.x_pair = e.ws + e.x0p; ea.ld_pair = 2 * H; ea.lo_pair = H; }
+    embed_pair(ea, px, e.ws + e.x0p);
     CHECK_HIP(launch_embed_fwd(ea, dt, s));
     const char* x = e.ws + e.x0;
     const char* xg = px ? e.ws + e.x0p : x;          // the layer input as the GEMMs read it (parity mode: its plane pair)
@@ -604,35 +527,30 @@ int text_forward(mmhip_engine& e, hipStream_t s) {
         const LayerOff& o = e.txt[l];
         const LayerW16& w = e.txt_w16[l];
         const TextAct& a = e.tact[l];
-        { G g(xg, H, e.ws + w.qkv, H, e.ws + a.qkv, 3 * H, Mt, 3 * H, H); g.bias(W + o.qkv_b).px_in(px).px_out(px); part_gemm(e, g, 0); if (int r = run_gemm(e, g, s)) return r; }
+        { G g(xg, H, e.ws + w.qkv, H, e.ws + a.qkv, 3 * H, Mt, 3 * H, H); g.bias(W + o.qkv_b).px_in(px).px_out(px); part_gemm(e, g, 0); CHECK_RC(run_gemm(e, g, s)); }
         // Only the CLS row of the last layer's output is ever consumed (fusion query and pooler, mm_late.py:111,155-158):
         // its attention needs query tile 0 only and everything after it runs on Bt rows (row stride T*H in the full
         // tensors, compact [Bt, .] outputs).  Dropout indices keep the full-tensor numbering (row_mul = T).
         const bool compact = e.cls_only > 0 && l == c.layers_txt - 1;
         const int Mr = compact ? Bt : Mt, rs = compact ? T * H : H, rmul = compact ? T : 1;
-        AttnArgs at;
-        memset(&at, 0, sizeof(at));
-        at.qkv = e.ws + a.qkv; at.maskbias = e.wsp<float>(e.maskbias); at.ctx = e.ws + a.ctx; at.lse = e.wsp<float>(a.lse);
-        at.posts = Bt; at.S = T; at.heads = c.heads; at.ld_qkv = 3 * H; at.ld_ctx = H; at.hidden = H;
-        if (px) { at.pair = 1; at.ld_qkv = 6 * H; at.lo_qkv = 3 * H; at.ld_ctx = 2 * H; at.lo_ctx = H; }
-        at.scale = 1.0f / sqrtf((float)(H / c.heads));
-        at.drop = make_drop(c.p_attn, e.seed, stream_attn(l), tr);
+        AttnArgs at = attn_args(e.ws + a.qkv, e.wsp<float>(e.maskbias), e.ws + a.ctx, e.wsp<float>(a.lse), Bt, T, c.heads, H, make_drop(c.p_attn, e.seed, stream_attn(l), tr));
+        attn_pair(at, px);
         at.q_tiles = compact ? 1 : 0;
         CHECK_HIP(launch_attn_fwd(at, dt, s));
         { G g(e.ws + a.ctx, rs, e.ws + w.ao, H, e.ws + a.pre1, H, Mr, H, H);
           g.bias(W + o.ao_b).dropout(make_drop(c.p_hidden, e.seed, stream_attn_out(l), tr), rmul).residual(x, rs).px_in(px);
           part_gemm(e, g, 0);
-          if (int r = run_gemm(e, g, s)) return r; }
+          CHECK_RC(run_gemm(e, g, s)); }
         LNArgs ln1{e.ws + a.pre1, e.ws + a.a1, W + o.ln1_w, W + o.ln1_b, e.wsp<float>(a.mean1), e.wsp<float>(a.rstd1), Mr, H, H, H, c.ln_eps_txt};
-        if (px) { ln1.y_pair = e.ws + a.a1p; ln1.ld_pair = 2 * H; ln1.lo_pair = H; }
+        ln_pair(ln1, px, e.ws + a.a1p);
         CHECK_HIP(launch_layernorm_fwd(ln1, dt, s));
-        { G g(e.ws + (px ? a.a1p : a.a1), H, e.ws + w.fc1, H, e.ws + a.h, I, Mr, I, H); g.bias(W + o.fc1_b).aux(e.ws + a.u, I).gelu().px_in(px).px_out(px); part_gemm(e, g, 0); if (int r = run_gemm(e, g, s)) return r; }
+        { G g(e.ws + (px ? a.a1p : a.a1), H, e.ws + w.fc1, H, e.ws + a.h, I, Mr, I, H); g.bias(W + o.fc1_b).aux(e.ws + a.u, I).gelu().px_in(px).px_out(px); part_gemm(e, g, 0); CHECK_RC(run_gemm(e, g, s)); }
         { G g(e.ws + a.h, I, e.ws + w.fc2, I, e.ws + a.pre2, H, Mr, H, I);
           g.bias(W + o.fc2_b).dropout(make_drop(c.p_hidden, e.seed, stream_ffn_out(l), tr), rmul).residual(e.ws + a.a1, H).px_in(px);
           part_gemm(e, g, 0);
-          if (int r = run_gemm(e, g, s)) return r; }
+          CHECK_RC(run_gemm(e, g, s)); }
         LNArgs ln2{e.ws + a.pre2, e.ws + a.out, W + o.ln2_w, W + o.ln2_b, e.wsp<float>(a.mean2), e.wsp<float>(a.rstd2), Mr, H, H, H, c.ln_eps_txt};
-        if (px) { ln2.y_pair = e.ws + a.outp; ln2.ld_pair = 2 * H; ln2.lo_pair = H; }
+        ln_pair(ln2, px, e.ws + a.outp);
         CHECK_HIP(launch_layernorm_fwd(ln2, dt, s));
         e.cls_compact = compact;
         x = e.ws + a.out;
@@ -666,24 +584,20 @@ int towers_forward_lockstep(mmhip_engine& e, const float* pixels, hipStream_t s)
     const float* W = e.train;
     const float* F = e.frozen;
     const bool tr = e.train_mode, px = e.px;
-    auto ln_to = [&](LNArgs& ln, size_t pair_buf, int Wd) {          // parity mode: a LayerNorm output that only GEMMs read goes out as a plane pair only
-        if (px) { ln.y = nullptr; ln.y_pair = e.ws + pair_buf; ln.ld_pair = 2 * Wd; ln.lo_pair = Wd; }
-    };
-    if (int r = e.span(0, s)) return r;
+    CHECK_RC(e.span(0, s));
     // ---- embeddings of both towers
     CHECK_HIP(launch_patchify(pixels, e.ws + e.v_patches, B, c.image, c.patch, Kpp, px ? DT_PAIR : dt, s));
-    { G g(e.ws + e.v_patches, Kpp, e.ws + e.patch_w16, Kpp, e.ws + e.v_pe, H, B * (P - 1), H, Kpp); g.bias(F + e.v_patch_b).px_in(px); if (int r = run_gemm(e, g, s)) return r; }
+    { G g(e.ws + e.v_patches, Kpp, e.ws + e.patch_w16, Kpp, e.ws + e.v_pe, H, B * (P - 1), H, Kpp); g.bias(F + e.v_patch_b).px_in(px); CHECK_RC(run_gemm(e, g, s)); }
     CHECK_HIP(launch_vit_assemble(e.ws + e.v_pe, F + e.v_cls, F + e.v_pos, e.ws + e.v_x, B, P, H, dt, s));
     char* xv = e.ws + e.v_x;
-    EmbedArgs ea;
-    memset(&ea, 0, sizeof(ea));
+    EmbedArgs ea{};
     ea.ids = e.wsp<int64_t>(e.ids_all); ea.mask = e.wsp<int64_t>(e.mask_all);
     ea.word = W + e.t_word; ea.pos = W + e.t_pos; ea.type = W + e.t_type; ea.gamma = W + e.t_eln_w; ea.beta = W + e.t_eln_b;
     ea.x = e.ws + e.x0; ea.xhat = e.ws + e.xhat_emb; ea.rstd = e.wsp<float>(e.rstd_emb); ea.pos_ids = e.wsp<int>(e.pos_ids);
     ea.maskbias = e.wsp<float>(e.maskbias);
     ea.posts = Bt; ea.T = T; ea.H = H; ea.xlmr = c.txt_kind == MMHIP_TXT_XLMR; ea.pad_id = c.pad_id; ea.eps = c.ln_eps_txt;
     ea.drop = make_drop(c.p_hidden, e.seed, STREAM_EMBED, tr);
-    if (px) { ea.x_pair = e.ws + e.x0p; ea.ld_pair = 2 * H; ea.lo_pair = H; }
+    embed_pair(ea, px, e.ws + e.x0p);
     CHECK_HIP(launch_embed_fwd(ea, dt, s));
     const char* xt = e.ws + e.x0;
     const char* xtg = px ? e.ws + e.x0p : xt;          // the text layer input as the GEMMs read it
@@ -696,12 +610,8 @@ int towers_forward_lockstep(mmhip_engine& e, const float* pixels, hipStream_t s)
     auto fork = [&]() -> int { if (sv != s) { CHECK_HIP(hipEventRecord(e.ev_fork, s)); CHECK_HIP(hipStreamWaitEvent(sv, e.ev_fork, 0)); } return 0; };
     auto join = [&]() -> int { if (sv != s) { CHECK_HIP(hipEventRecord(e.ev_vit, sv)); CHECK_HIP(hipStreamWaitEvent(s, e.ev_vit, 0)); } return 0; };
     auto attn = [&](hipStream_t st, const char* qkv, const float* mb, char* ctx, float* lse, int posts, int S, int heads, const DropCfg* d, int q_tiles) -> int {
-        AttnArgs at;
-        memset(&at, 0, sizeof(at));
-        at.qkv = qkv; at.maskbias = mb; at.ctx = ctx; at.lse = lse; at.posts = posts; at.S = S; at.heads = heads; at.ld_qkv = 3 * H; at.ld_ctx = H; at.hidden = H;
-        if (px) { at.pair = 1; at.ld_qkv = 6 * H; at.lo_qkv = 3 * H; at.ld_ctx = 2 * H; at.lo_ctx = H; }
-        at.scale = 1.0f / sqrtf((float)(H / heads));
-        if (d) at.drop = *d;
+        AttnArgs at = attn_args(qkv, mb, ctx, lse, posts, S, heads, H, d ? *d : DropCfg{});
+        attn_pair(at, px);
         at.q_tiles = q_tiles;
         CHECK_HIP(launch_attn_fwd(at, dt, st));
         return 0;
@@ -722,79 +632,79 @@ int towers_forward_lockstep(mmhip_engine& e, const float* pixels, hipStream_t s)
         // ---- QKV (image tower: pre-LN; layer 0's runs here, the later layers' beside the text tower's closing LayerNorm of the layer above)
         if (hv && l == 0) {
             LNArgs ln{xv, e.ws + e.v_ln, F + ov.ln1_w, F + ov.ln1_b, nullptr, nullptr, Mv, H, H, H, c.ln_eps_img};
-            ln_to(ln, e.v_ln, H);
+            ln_pair(ln, px, e.ws + e.v_ln, true);          // only GEMMs read it: the pair alone
             CHECK_HIP(launch_layernorm_fwd(ln, dt, s));
         }
         {
             G gt(xtg, H, e.ws + wt.qkv, H, e.ws + a.qkv, 3 * H, Mt, 3 * H, H); gt.bias(W + ot.qkv_b).px_in(px).px_out(px);
             G gv(e.ws + e.v_ln, H, e.ws + wv.qkv, H, e.ws + e.v_qkv, 3 * H, Mv, 3 * H, H); gv.bias(F + ov.qkv_b).px_in(px).px_out(px);
-            if (int r = both(gt, gv)) return r;
+            CHECK_RC(both(gt, gv));
         }
         // ---- attention
         if (hv) {
-            if (int r = fork()) return r;
-            if (int r = attn(sv, e.ws + e.v_qkv, nullptr, e.ws + e.v_ctx, nullptr, B, P, e.heads_v(), nullptr, 0)) return r;
+            CHECK_RC(fork());
+            CHECK_RC(attn(sv, e.ws + e.v_qkv, nullptr, e.ws + e.v_ctx, nullptr, B, P, e.heads_v(), nullptr, 0));
         }
         if (ht) {
             const DropCfg d = make_drop(c.p_attn, e.seed, stream_attn(l), tr);
-            if (int r = attn(s, e.ws + a.qkv, e.wsp<float>(e.maskbias), e.ws + a.ctx, e.wsp<float>(a.lse), Bt, T, c.heads, &d, compact ? 1 : 0)) return r;
+            CHECK_RC(attn(s, e.ws + a.qkv, e.wsp<float>(e.maskbias), e.ws + a.ctx, e.wsp<float>(a.lse), Bt, T, c.heads, &d, compact ? 1 : 0));
         }
-        if (hv) if (int r = join()) return r;
+        if (hv) CHECK_RC(join());
         // ---- attention output (+ residual)
         {
             G gt(e.ws + a.ctx, rs, e.ws + wt.ao, H, e.ws + a.pre1, H, Mr, H, H);
             gt.bias(W + ot.ao_b).dropout(make_drop(c.p_hidden, e.seed, stream_attn_out(l), tr), rmul).residual(xt, rs).px_in(px);
             G gv(e.ws + e.v_ctx, H, e.ws + wv.ao, H, xv, H, Mv, H, H); gv.bias(F + ov.ao_b).residual(xv, H).px_in(px);
-            if (int r = both(gt, gv)) return r;
+            CHECK_RC(both(gt, gv));
         }
         if (hv) {
-            if (int r = fork()) return r;
+            CHECK_RC(fork());
             LNArgs ln2{xv, e.ws + e.v_ln, F + ov.ln2_w, F + ov.ln2_b, nullptr, nullptr, Mv, H, H, H, c.ln_eps_img};
-            ln_to(ln2, e.v_ln, H);
+            ln_pair(ln2, px, e.ws + e.v_ln, true);          // only GEMMs read it: the pair alone
             CHECK_HIP(launch_layernorm_fwd(ln2, dt, sv));
         }
         if (ht) {
             LNArgs ln1{e.ws + a.pre1, e.ws + a.a1, W + ot.ln1_w, W + ot.ln1_b, e.wsp<float>(a.mean1), e.wsp<float>(a.rstd1), Mr, H, H, H, c.ln_eps_txt};
-            if (px) { ln1.y_pair = e.ws + a.a1p; ln1.ld_pair = 2 * H; ln1.lo_pair = H; }
+            ln_pair(ln1, px, e.ws + a.a1p);
             CHECK_HIP(launch_layernorm_fwd(ln1, dt, s));
         }
-        if (hv) if (int r = join()) return r;
+        if (hv) CHECK_RC(join());
         // ---- feed-forward
         {
             G gt(e.ws + (px ? a.a1p : a.a1), H, e.ws + wt.fc1, H, e.ws + a.h, I, Mr, I, H); gt.bias(W + ot.fc1_b).aux(e.ws + a.u, I).gelu().px_in(px).px_out(px);
             G gv(e.ws + e.v_ln, H, e.ws + wv.fc1, H, e.ws + e.v_h, I, Mv, I, H); gv.bias(F + ov.fc1_b).gelu().px_in(px).px_out(px);
-            if (int r = both(gt, gv)) return r;
+            CHECK_RC(both(gt, gv));
         }
         {
             G gt(e.ws + a.h, I, e.ws + wt.fc2, I, e.ws + a.pre2, H, Mr, H, I);
             gt.bias(W + ot.fc2_b).dropout(make_drop(c.p_hidden, e.seed, stream_ffn_out(l), tr), rmul).residual(e.ws + a.a1, H).px_in(px);
             G gv(e.ws + e.v_h, I, e.ws + wv.fc2, I, xv, H, Mv, H, I); gv.bias(F + ov.fc2_b).residual(xv, H).px_in(px);
-            if (int r = both(gt, gv)) return r;
+            CHECK_RC(both(gt, gv));
         }
         // ---- the text layer's closing LayerNorm beside the image tower's opening one of the next layer
         const bool vnext = l + 1 < c.layers_img;
         if (vnext) {
-            if (int r = fork()) return r;
+            CHECK_RC(fork());
             const LayerOff& on = e.vit[l + 1];
             LNArgs ln{xv, e.ws + e.v_ln, F + on.ln1_w, F + on.ln1_b, nullptr, nullptr, Mv, H, H, H, c.ln_eps_img};
-            ln_to(ln, e.v_ln, H);
+            ln_pair(ln, px, e.ws + e.v_ln, true);          // only GEMMs read it: the pair alone
             CHECK_HIP(launch_layernorm_fwd(ln, dt, sv));
         }
         if (ht) {
             LNArgs ln2{e.ws + a.pre2, e.ws + a.out, W + ot.ln2_w, W + ot.ln2_b, e.wsp<float>(a.mean2), e.wsp<float>(a.rstd2), Mr, H, H, H, c.ln_eps_txt};
-            if (px) { ln2.y_pair = e.ws + a.outp; ln2.ld_pair = 2 * H; ln2.lo_pair = H; }
+            ln_pair(ln2, px, e.ws + a.outp);
             CHECK_HIP(launch_layernorm_fwd(ln2, dt, s));
             e.cls_compact = compact;
             xt = e.ws + a.out;
             xtg = px ? e.ws + a.outp : xt;
         }
-        if (vnext) if (int r = join()) return r;
+        if (vnext) CHECK_RC(join());
     }
     LNArgs lnf{xv, e.ws + e.v_out, F + e.v_ln_w, F + e.v_ln_b, nullptr, nullptr, Mv, H, H, H, c.ln_eps_img};
     CHECK_HIP(launch_layernorm_fwd(lnf, dt, s));
     SmallGemmArgs sp = small(e.ws + e.v_out, P * H, F + e.v_pool_w, H, F + e.v_pool_b, e.wsp<float>(e.h_vpool), H, B, H, H, ACT_TANH);
     CHECK_HIP(launch_small_nt(sp, dt, s));
-    if (int r = e.span(1, s)) return r;
+    CHECK_RC(e.span(1, s));
     return e.span(2, s);
 }
 
@@ -982,7 +892,7 @@ int text_layer_backward(mmhip_engine& e, int l, hipStream_t s) {
     // (the second stage of its dgamma / dbeta reduction is not on the dX chain: it runs with the layer's dW on the side stream)
     LNBwdArgs b2{dx, e.ws + a.pre2, W + o.ln2_w, e.wsp<float>(a.mean2), e.wsp<float>(a.rstd2), dpre2, nullptr, Gd + o.ln2_w, Gd + o.ln2_b, Mr, H,
                  e.wsp<float>(e.g_lnp[set][0]), 1.0f / e.gscale(), d_ffn.thresh16 ? ddrop2 : nullptr, nullptr, d_ffn, rmul, 1};
-    if (px) { b2.pair_out = ddrop2; b2.ld_pair = 2 * H; b2.lo_pair = H; b2.pair_hi_only = hi1; }      // parity mode: the GEMMs' operand (dropped or not) as a plane pair in the ddrop buffer
+    ln_bwd_pair(b2, px, ddrop2, hi1);      // parity mode: the GEMMs' operand (dropped or not) as a plane pair in the ddrop buffer
     CHECK_HIP(launch_layernorm_bwd(b2, dt, s));
     const char* df = (px || d_ffn.thresh16) ? ddrop2 : dpre2;
     // du = (df . W2) * gelu'(u);  d_a1 = du . W1 + dpre2
@@ -990,44 +900,40 @@ int text_layer_backward(mmhip_engine& e, int l, hipStream_t s) {
     static int bwd_mask = -1;
     if (bwd_mask < 0) { const char* v = getenv("MMHIP_PART_BWD_MASK"); bwd_mask = v ? atoi(v) : 15; }
     auto part_bwd = [&](G& g, int bit) {
-        if (e.part_bwd > 0 && (bwd_mask & bit) && side && g.a.M >= 2048 && g.a.N % 256 == 0 && g.a.K % 64 == 0 && (dt == DT_BF16 || dt == DT_F16)) { g.a.tile = 15; g.a.grid = e.part_bwd; }
+        if (e.part_bwd > 0 && (bwd_mask & bit) && side && g.a.M >= 2048 && g.a.N % 256 == 0 && g.a.K % 64 == 0 && (dt == DT_BF16 || dt == DT_F16)) g.tile(15).grid(e.part_bwd);
     };
-    { G g(df, H, e.ws + w.fc2T, H, du, I, Mr, I, H); g.mul_gelu_grad(e.ws + a.u, I).px_in(px, np).px_out(px, hi1); part_bwd(g, 1); if (int r = run_gemm(e, g, s)) return r; }
+    { G g(df, H, e.ws + w.fc2T, H, du, I, Mr, I, H); g.mul_gelu_grad(e.ws + a.u, I).px_in(px, np).px_out(px, hi1); part_bwd(g, 1); CHECK_RC(run_gemm(e, g, s)); }
     // the two long-K activation-gradient GEMMs of the layer (768 wide): one role-specialised 256x96 tile per CU when M gives
     // exactly <= 256 of them -- in isolation 7 % faster than the 192 tiles of 256x128, in the step -0.05 ms (same-box A/B; the
     // same tile in the FORWARD costs +0.3 ms: it leaves no CU to the image tower).  MMHIP_BWD_TILE12=0 turns it off.
     static int bt12 = -1;
     if (bt12 < 0) { const char* v = getenv("MMHIP_BWD_TILE12"); bt12 = v ? atoi(v) : 1; }
     const int nt = (bt12 && Mr >= 4096 && Mr <= 8192 && H % 96 == 0) ? 12 : 0;
-    { G g(du, I, e.ws + w.fc1T, I, dx2, H, Mr, H, I); g.residual(dpre2, H).px_in(px, np); g.a.tile = nt; part_bwd(g, 2); if (int r = run_gemm(e, g, s)) return r; }
+    { G g(du, I, e.ws + w.fc1T, I, dx2, H, Mr, H, I); g.residual(dpre2, H).px_in(px, np); g.tile(nt); part_bwd(g, 2); CHECK_RC(run_gemm(e, g, s)); }
     // ---- a1 = LN1(pre1), pre1 = drop(ao(ctx)) + x_in        (dx2 = d_a1)
     const DropCfg d_ao = make_drop(c.p_hidden, e.seed, stream_attn_out(l), tr);
     LNBwdArgs b1{dx2, e.ws + a.pre1, W + o.ln1_w, e.wsp<float>(a.mean1), e.wsp<float>(a.rstd1), dpre1, nullptr, Gd + o.ln1_w, Gd + o.ln1_b, Mr, H,
                  e.wsp<float>(e.g_lnp[set][1]), 1.0f / e.gscale(), d_ao.thresh16 ? ddrop1 : nullptr, nullptr, d_ao, rmul, 1};
-    if (px) { b1.pair_out = ddrop1; b1.ld_pair = 2 * H; b1.lo_pair = H; b1.pair_hi_only = hi1; }
+    ln_bwd_pair(b1, px, ddrop1, hi1);
     CHECK_HIP(launch_layernorm_bwd(b1, dt, s));
     const char* dout = (px || d_ao.thresh16) ? ddrop1 : dpre1;
     if (compact) {
         // d ctx for the CLS rows only, spread into an otherwise-zero full tensor for the attention backward (parity mode: pair rows of 2 H 16-bit
         // elements are moved as the H 4-byte words they occupy; an all-zero pair is zero)
-        { G g(dout, H, e.ws + w.aoT, H, dx2, H, Mr, H, H); g.px_in(px, np).px_out(px, hi1); if (int r = run_gemm(e, g, s)) return r; }
+        { G g(dout, H, e.ws + w.aoT, H, dx2, H, Mr, H, H); g.px_in(px, np).px_out(px, hi1); CHECK_RC(run_gemm(e, g, s)); }
         CHECK_HIP(hipMemsetAsync(dctx, 0, (size_t)Mt * H * e.esz(), s));
         CHECK_HIP(launch_scatter_rows16(dx2, dctx, Bt, (size_t)T * H, H, 0, dt, s));
         CHECK_HIP(hipMemsetAsync(dqkv, 0, (size_t)Mt * 3 * H * e.esz(), s));      // dQ of the skipped query tiles is zero
     } else {
         G g(dout, H, e.ws + w.aoT, H, dctx, H, Mt, H, H);
         g.px_in(px, np).px_out(px, hi1);
-        g.a.tile = (bt12 & 2) ? nt : 0;
+        g.tile((bt12 & 2) ? nt : 0);
         part_bwd(g, 4);
-        if (int r = run_gemm(e, g, s)) return r;
+        CHECK_RC(run_gemm(e, g, s));
     }
-    AttnBwdArgs ab;
-    memset(&ab, 0, sizeof(ab));
-    ab.qkv = e.ws + a.qkv; ab.maskbias = e.wsp<float>(e.maskbias); ab.ctx = e.ws + a.ctx; ab.dctx = dctx; ab.lse = e.wsp<float>(a.lse);
-    ab.dqkv = dqkv; ab.posts = Bt; ab.S = T; ab.heads = c.heads; ab.ld_qkv = 3 * H; ab.ld_ctx = H; ab.hidden = H;
-    if (px) { ab.pair = 1; ab.ld_qkv = 6 * H; ab.lo_qkv = 3 * H; ab.ld_ctx = 2 * H; ab.lo_ctx = H; ab.nprod = np; }
-    ab.scale = 1.0f / sqrtf((float)(H / c.heads));
-    ab.drop = make_drop(c.p_attn, e.seed, stream_attn(l), tr);
+    AttnBwdArgs ab = attn_bwd_args(e.ws + a.qkv, e.wsp<float>(e.maskbias), e.ws + a.ctx, dctx, e.wsp<float>(a.lse), dqkv, Bt, T, c.heads, H,
+                                   make_drop(c.p_attn, e.seed, stream_attn(l), tr));
+    attn_pair(ab, px, np);
     ab.q_tiles = compact ? 1 : 0;
     CHECK_HIP(launch_attn_bwd(ab, dt, s));
     // ---- parameter gradients of the layer: off the critical path -> side stream: all four weight gradients AND their bias
@@ -1040,14 +946,14 @@ int text_layer_backward(mmhip_engine& e, int l, hipStream_t s) {
     }
     if (compact) {
         // dx_in = dqkv . Wqkv, plus d pre1 on the CLS rows (the residual branch of the CLS rows)
-        { G g(dqkv, 3 * H, e.ws + w.qkvT, 3 * H, dx, H, Mt, H, 3 * H); g.px_in(px, np); if (int r = run_gemm(e, g, s)) return r; }
+        { G g(dqkv, 3 * H, e.ws + w.qkvT, 3 * H, dx, H, Mt, H, 3 * H); g.px_in(px, np); CHECK_RC(run_gemm(e, g, s)); }
         CHECK_HIP(launch_scatter_rows16(dpre1, dx, Bt, (size_t)T * H, H, 1, dt, s));
     } else {
         G g(dqkv, 3 * H, e.ws + w.qkvT, 3 * H, dx, H, Mt, H, 3 * H);
         g.residual(dpre1, H).px_in(px, np);
-        g.a.tile = nt;
+        g.tile(nt);
         part_bwd(g, 8);
-        if (int r = run_gemm(e, g, s)) return r;
+        CHECK_RC(run_gemm(e, g, s));
     }
     GemmTNProblem pr[4];
     CHECK_HIP(launch_layernorm_bwd_reduce(b2, ps));
@@ -1059,7 +965,7 @@ int text_layer_backward(mmhip_engine& e, int l, hipStream_t s) {
     pr[3] = GemmTNProblem{dout, e.ws + a.ctx, Gd + o.ao_w, Mr, H, H, H, rs, H, 0, Gd + o.ao_b};        // dWo[H,H]   = dout^T ctx (CLS rows: stride T*H)
     if (px) {
         pr[1].B = e.ws + a.a1p;
-        for (auto& q : pr) { q.pair = 1; q.lda *= 2; q.ldb *= 2; q.a_lo = q.Nn; q.b_lo = q.Nc; q.nprod = np; }
+        for (auto& q : pr) tn_pair(q, np);
     }
     {
         const int i = e.side && ps == e.side ? 1 : 0;
@@ -1094,8 +1000,7 @@ int embed_backward(mmhip_engine& e, hipStream_t s) {
     const mmhip_config& c = e.cfg;
     const float* W = e.train;
     float* Gd = e.grad;
-    EmbedBwdArgs b;
-    memset(&b, 0, sizeof(b));
+    EmbedBwdArgs b{};
     b.dx = e.ws + e.g_dx; b.xhat = e.ws + e.xhat_emb; b.rstd = e.wsp<float>(e.rstd_emb); b.gamma = W + e.t_eln_w;
     b.ids = e.wsp<int64_t>(e.ids_all); b.pos_ids = e.wsp<int>(e.pos_ids);
     b.dword = Gd + e.t_word; b.dpos = Gd + e.t_pos; b.dtype = Gd + e.t_type; b.dgamma = Gd + e.t_eln_w; b.dbeta = Gd + e.t_eln_b;
@@ -1181,13 +1086,13 @@ int mmhip_refresh_weights(mmhip_handle h, int which, void* stream) {
     mmhip_engine& e = *h;
     if (which & 1) {
         for (int l = 0; l < e.cfg.layers_img; ++l)
-            if (int r = refresh_layer(e, e.frozen, e.vit[l], e.vit_w16[l], false, s, e.Hv(), e.Iv())) return r;
+            CHECK_RC(refresh_layer(e, e.frozen, e.vit[l], e.vit_w16[l], false, s, e.Hv(), e.Iv()));
         // patch-embedding weight [Hv, 3*p*p], rows zero-padded to the GEMM's k-step (14 x 14 patches: 588 -> 640)
         CHECK_HIP(launch_cast_pad(e.frozen + e.v_patch_w, e.ws + e.patch_w16, e.Hv(), e.Kp(), e.Kpp(), e.px ? DT_PAIR : e.dt(), s));
     }
     if (which & 2)
         for (int l = 0; l < e.cfg.layers_txt; ++l)
-            if (int r = refresh_layer(e, e.train, e.txt[l], e.txt_w16[l], true, s, e.cfg.hidden, e.cfg.inter)) return r;
+            CHECK_RC(refresh_layer(e, e.train, e.txt[l], e.txt_w16[l], true, s, e.cfg.hidden, e.cfg.inter));
     return 0;
 }
 
@@ -1213,7 +1118,7 @@ int mmhip_forward(mmhip_handle h, const int64_t* ids, const int64_t* mask, const
         CHECK_HIP(launch_copy_ids_clamped(tim_ids, e.wsp<int64_t>(e.ids_all) + (size_t)B * T, (size_t)B * T, e.cfg.vocab, e.bad_index, s));
         CHECK_HIP(hipMemcpyAsync(e.ws + e.mask_all + nb, tim_mask, nb, hipMemcpyDeviceToDevice, s));
     }
-    if (int r = side_init(e)) return r;
+    CHECK_RC(side_init(e));
     if (e.part[0] < 0) {
         // MMHIP_PART: "txt,vit" forces a split, "0" turns the partition off; default: chosen per forward (choose_partition)
         e.part[0] = e.part[1] = 0; e.part_auto = true;
@@ -1229,35 +1134,34 @@ int mmhip_forward(mmhip_handle h, const int64_t* ids, const int64_t* mask, const
     else if (can_part && e.part[0] > 0) { e.cur_part[0] = e.part[0]; e.cur_part[1] = e.part[1]; }
     if (!imported && lockstep_ok(e)) {
         e.vit_is_long = false;
-        if (int r = towers_forward_lockstep(e, pixels, s)) return r;
+        CHECK_RC(towers_forward_lockstep(e, pixels, s));
     } else if (use_side(e)) {
         // the frozen image tower does not depend on the text tower: run it on the side stream, join before the heads
         CHECK_HIP(hipEventRecord(e.ev_fork, s));
-        if (int r = e.span(0, s)) return r;
+        CHECK_RC(e.span(0, s));
         static int force = -2;
         if (force == -2) { const char* v = getenv("MMHIP_VIT_PRIO"); force = v ? atoi(v) : -1; }
-        const int P = (e.cfg.image / e.cfg.patch) * (e.cfg.image / e.cfg.patch) + 1;
-        const bool vit_longer = (double)e.B * P * e.cfg.layers_img > (double)e.Bt * e.T * e.cfg.layers_txt;     // rows x layers of equal width
+        const bool vit_longer = (double)e.B * e.P() * e.cfg.layers_img > (double)e.Bt * e.T * e.cfg.layers_txt;     // rows x layers of equal width
         e.vit_is_long = vit_longer;
         hipStream_t sv = e.side_vit[force >= 0 ? (force ? 1 : 0) : (vit_longer ? 1 : 0)];
         if (!imported) {
             CHECK_HIP(hipStreamWaitEvent(sv, e.ev_fork, 0));
-            if (int r = vit_forward(e, pixels, sv)) return r;
-            if (int r = e.span(1, sv)) return r;
+            CHECK_RC(vit_forward(e, pixels, sv));
+            CHECK_RC(e.span(1, sv));
             CHECK_HIP(hipEventRecord(e.ev_vit, sv));
         }
-        if (int r = text_forward(e, s)) return r;
-        if (int r = e.span(2, s)) return r;
+        CHECK_RC(text_forward(e, s));
+        CHECK_RC(e.span(2, s));
         if (!imported) CHECK_HIP(hipStreamWaitEvent(s, e.ev_vit, 0));
     } else {
-        if (int r = e.span(0, s)) return r;
-        if (!imported) if (int r = vit_forward(e, pixels, s)) return r;
-        if (int r = e.span(1, s)) return r;
-        if (int r = text_forward(e, s)) return r;
-        if (int r = e.span(2, s)) return r;
+        CHECK_RC(e.span(0, s));
+        if (!imported) CHECK_RC(vit_forward(e, pixels, s));
+        CHECK_RC(e.span(1, s));
+        CHECK_RC(text_forward(e, s));
+        CHECK_RC(e.span(2, s));
     }
-    if (int r = heads_forward(e, out_cls, logits_per_text, out_tim, mm_features, s)) return r;
-    if (int r = e.span(3, s)) return r;
+    CHECK_RC(heads_forward(e, out_cls, logits_per_text, out_tim, mm_features, s));
+    CHECK_RC(e.span(3, s));
     e.fwd_done = true;
     return 0;
 }
@@ -1291,7 +1195,7 @@ int vision_copy(mmhip_engine& e, int to_cache, const int64_t* slots, void* cache
 }  // namespace
 uint64_t mmhip_vision_record_bytes(mmhip_handle h) {
     if (!h) return 0;
-    const uint64_t P = (uint64_t)(h->cfg.image / h->cfg.patch) * (h->cfg.image / h->cfg.patch) + 1;
+    const uint64_t P = (uint64_t)h->P();
     return (P * h->Hv() * h->esz() + (uint64_t)h->Hv() * 4 + 255) & ~255ull;
 }
 int mmhip_vision_export(mmhip_handle h, const int64_t* slots, void* cache, uint64_t cache_records, void* stream) {
@@ -1303,7 +1207,7 @@ int mmhip_vision_import(mmhip_handle h, const int64_t* slots, const void* cache,
     if (!h || !h->ws) return MMHIP_E_STATE;
     if (!slots || !cache || ((uintptr_t)cache & 15) || B < 1) return MMHIP_E_INVALID;
     if (B > h->cfg.max_posts) return MMHIP_E_CAPACITY;
-    if (int r = vision_copy(*h, 0, slots, const_cast<void*>(cache), cache_records, B, (hipStream_t)stream)) return r;
+    CHECK_RC(vision_copy(*h, 0, slots, const_cast<void*>(cache), cache_records, B, (hipStream_t)stream));
     h->vision_ready_B = B;
     return 0;
 }
@@ -1315,8 +1219,7 @@ int mmhip_loss(mmhip_handle h, const int64_t* onehot, const float* class_w, cons
     mmhip_engine& e = *h;
     if (w_itm != 0.f && (!e.itm || !lbl_tim)) return MMHIP_E_INVALID;
     if (w_itc != 0.f && !e.itc_done) return MMHIP_E_STATE;
-    LossArgs a;
-    memset(&a, 0, sizeof(a));
+    LossArgs a{};
     a.out_cls = e.wsp<float>(e.h_out_cls); a.onehot = onehot; a.class_w = class_w;
     a.logits_per_text = w_itc != 0.f ? e.wsp<float>(e.h_logits) : nullptr;
     a.out_tim = w_itm != 0.f ? e.wsp<float>(e.h_out_tim) : nullptr; a.lbl_tim = lbl_tim;
@@ -1386,10 +1289,10 @@ int mmhip_backward_finish(mmhip_handle h, void* stream) {
     return backward_finish(*h, (hipStream_t)stream);
 }
 int mmhip_backward(mmhip_handle h, const float* d_out_cls, const float* d_logits, const float* d_out_tim, const float* d_feats, void* stream) {
-    if (int r = mmhip_backward_begin(h, d_out_cls, d_logits, d_out_tim, d_feats, stream)) return r;
+    CHECK_RC(mmhip_backward_begin(h, d_out_cls, d_logits, d_out_tim, d_feats, stream));
     const int n = mmhip_num_backward_stages(h);
     for (int st = 0; st < n; ++st)
-        if (int r = mmhip_backward_stage(h, st, stream)) return r;
+        CHECK_RC(mmhip_backward_stage(h, st, stream));
     return mmhip_backward_finish(h, stream);
 }
 
@@ -1501,7 +1404,7 @@ static int train_step_impl(mmhip_handle h, const int64_t* ids, const int64_t* ma
                                  nullptr, nullptr, stream);
     e.skip_itc = false;
     if (rf) return rf;
-    if (int r = mmhip_loss(h, onehot, class_w, use_itm ? lbl_tim : nullptr, w_cls, use_itc ? w_itc : 0.f, use_itm ? w_itm : 0.f, loss, n_correct, stream)) return r;
+    CHECK_RC(mmhip_loss(h, onehot, class_w, use_itm ? lbl_tim : nullptr, w_cls, use_itc ? w_itc : 0.f, use_itm ? w_itm : 0.f, loss, n_correct, stream));
     // Backward.  With the side stream on, each text layer's AdamW and 16-bit weight refresh follow its weight-gradient GEMM on the
     // SIDE stream, beside the activation-gradient chain of the layers below (an HBM-bound kernel next to MFMA-bound ones) instead
     // of after the whole backward; the layer's fp32 LayerNorm weights and transposed 16-bit copies are read by its own backward
@@ -1516,7 +1419,7 @@ static int train_step_impl(mmhip_handle h, const int64_t* ids, const int64_t* ma
         static bool told = false;
         if (!told && getenv("MMHIP_VERBOSE")) { fprintf(stderr, "[mmhip] f16 with the step guard armed: every AdamW launch follows the backward (no per-layer optimizer beside it)\n"); told = true; }
     }
-    if (int r = mmhip_backward_begin(h, nullptr, nullptr, nullptr, nullptr, stream)) return r;
+    CHECK_RC(mmhip_backward_begin(h, nullptr, nullptr, nullptr, nullptr, stream));
     const int L = e.cfg.layers_txt;
     // data-parallel form (cb): the callback is told about stage st-1 once stage st is enqueued and st-1's weight gradients are ordered in the
     // caller's stream -- its collective travels while the stages below compute.  The layer optimizers wait for the gradient exchange: PER BUCKET
@@ -1532,9 +1435,9 @@ static int train_step_impl(mmhip_handle h, const int64_t* ids, const int64_t* ma
     std::vector<char> layer_done((size_t)(L > 0 ? L : 1), 0);
     std::vector<int> open_layers;          // text layers whose gradient stage lies in the bucket that is still open
     for (int st = 0; st < L + 2; ++st) {
-        if (int r = mmhip_backward_stage(h, st, stream)) return r;
+        CHECK_RC(mmhip_backward_stage(h, st, stream));
         if (cb && st >= 1) {
-            if (int r = mmhip_backward_join_stage(h, st - 1, stream)) return r;
+            CHECK_RC(mmhip_backward_join_stage(h, st - 1, stream));
             const int r = cb(user, st - 1);
             if (r != 0 && r != MMHIP_CB_BUCKET) return r;
             if (st - 1 >= 1 && st - 1 <= L) open_layers.push_back(L - (st - 1));
@@ -1549,9 +1452,9 @@ static int train_step_impl(mmhip_handle h, const int64_t* ids, const int64_t* ma
                     for (int l : open_layers) {
                         const LayerOff& o = e.txt[l];
                         if (w == 0)
-                            if (int r2 = adamw_impl(e.train + o.begin, e.grad + o.begin, adam_m + o.begin, adam_v + o.begin, o.end - o.begin, lr, beta1, beta2, eps,
-                                                    weight_decay, step, grad_scale, 1, e.side, gc, gf)) return r2;
-                        if (int r2 = refresh_layer(e, e.train, o, e.txt_w16[l], true, e.side, e.cfg.hidden, e.cfg.inter)) return r2;
+                            CHECK_RC(adamw_impl(e.train + o.begin, e.grad + o.begin, adam_m + o.begin, adam_v + o.begin, o.end - o.begin, lr, beta1, beta2, eps,
+                                                    weight_decay, step, grad_scale, 1, e.side, gc, gf));
+                        CHECK_RC(refresh_layer(e, e.train, o, e.txt_w16[l], true, e.side, e.cfg.hidden, e.cfg.inter));
                         layer_done[l] = w == 0 ? 1 : 2;          // 2: stepped by the caller (MMHIP_CB_HANDLED), refreshed here
                     }
                     CHECK_HIP(hipEventRecord(e.ev_opt, e.side));
@@ -1565,25 +1468,25 @@ static int train_step_impl(mmhip_handle h, const int64_t* ids, const int64_t* ma
             const LayerOff& o = e.txt[l];
             CHECK_HIP(hipEventRecord(e.ev_layer[set], s));
             CHECK_HIP(hipStreamWaitEvent(e.side, e.ev_layer[set], 0));
-            if (int r = adamw_impl(e.train + o.begin, e.grad + o.begin, adam_m + o.begin, adam_v + o.begin, o.end - o.begin, lr, beta1, beta2, eps,
-                                   weight_decay, step, grad_scale, 1, e.side, gc, gf)) return r;
-            if (int r = refresh_layer(e, e.train, o, e.txt_w16[l], true, e.side, e.cfg.hidden, e.cfg.inter)) return r;
+            CHECK_RC(adamw_impl(e.train + o.begin, e.grad + o.begin, adam_m + o.begin, adam_v + o.begin, o.end - o.begin, lr, beta1, beta2, eps,
+                                   weight_decay, step, grad_scale, 1, e.side, gc, gf));
+            CHECK_RC(refresh_layer(e, e.train, o, e.txt_w16[l], true, e.side, e.cfg.hidden, e.cfg.inter));
             layer_done[l] = 1;
             CHECK_HIP(hipEventRecord(e.ev_opt, e.side));
             opt_pending = true;
         }
     }
-    if (int r = mmhip_backward_finish(h, stream)) return r;
+    CHECK_RC(mmhip_backward_finish(h, stream));
     if (opt_pending) CHECK_HIP(hipStreamWaitEvent(s, e.ev_opt, 0));
     if (cb) {
-        if (int r = cb(user, L + 1)) return r;                    // embedding stage: dense part + the row-sparse word-table exchange start
+        CHECK_RC(cb(user, L + 1));                    // embedding stage: dense part + the row-sparse word-table exchange start
         // the dense exchanges are ordered before what follows in `stream`; MMHIP_CB_HANDLED: the caller also ran the dense optimizer itself
         // (reduce-scatter -> AdamW on its shard -> all-gather of the parameters: dist.ShardedBuckets) -- the dense AdamW launches below are skipped
         const int r = cb(user, MMHIP_CB_WAIT_DENSE);
         if (r == MMHIP_CB_HANDLED) dense_by_caller = true;
         else if (r) return r;
     }
-    if (int r = e.span(4, s)) return r;
+    CHECK_RC(e.span(4, s));
     // merged [begin, end) ranges of the active gradient groups, in address order (text layers already stepped: skipped)
     bool act[6] = {false, use_itc != 0, use_itm != 0, e.cfg.fusion == MMHIP_FUSION_ATTENTION, true, false};
     const uint64_t w0 = e.t_word, V = (uint64_t)e.cfg.vocab, H = (uint64_t)e.cfg.hidden;
@@ -1594,8 +1497,8 @@ static int train_step_impl(mmhip_handle h, const int64_t* ids, const int64_t* ma
         if (!open || re <= rb) return 0;
         const uint64_t dense_end = re < w0 ? re : w0;
         if (dense_end > rb && !dense_by_caller)
-            if (int r = adamw_impl(e.train + rb, e.grad + rb, adam_m + rb, adam_v + rb, dense_end - rb, lr, beta1, beta2, eps, weight_decay, step,
-                                   grad_scale, 1, stream, gc, gf)) return r;
+            CHECK_RC(adamw_impl(e.train + rb, e.grad + rb, adam_m + rb, adam_v + rb, dense_end - rb, lr, beta1, beta2, eps, weight_decay, step,
+                                   grad_scale, 1, stream, gc, gf));
         if (re > w0) rows_due = true;          // the word table goes last: under data parallelism its rows are still travelling
         return 0;
     };
@@ -1607,17 +1510,17 @@ static int train_step_impl(mmhip_handle h, const int64_t* ids, const int64_t* ma
         if (p.buffer != 1 || !act[p.group] || in_layer(p.offset)) continue;
         const uint64_t b = p.offset, en = p.offset + ((p.numel + 3) & ~(uint64_t)3);
         if (open && b == re) { re = en; continue; }
-        if (int r = flush()) return r;
+        CHECK_RC(flush());
         rb = b; re = en; open = true;
     }
-    if (int r = flush()) return r;
+    CHECK_RC(flush());
     for (int l = 0; l < L; ++l)          // 16-bit GEMM operand copies of the layers stepped just now: no word-table dependence
-        if (!layer_done[l]) if (int r = refresh_layer(e, e.train, e.txt[l], e.txt_w16[l], true, s, e.cfg.hidden, e.cfg.inter)) return r;
+        if (!layer_done[l]) CHECK_RC(refresh_layer(e, e.train, e.txt[l], e.txt_w16[l], true, s, e.cfg.hidden, e.cfg.inter));
     if (rows_due) {
-        if (cb) if (int r = cb(user, MMHIP_CB_FINISH_ROWS)) return r;                 // the exchanged word rows are summed into the gradient
+        if (cb) CHECK_RC(cb(user, MMHIP_CB_FINISH_ROWS));                 // the exchanged word rows are summed into the gradient
         if (!e.word_row_state) return MMHIP_E_STATE;
-        if (int r = adamw_rows_impl(e.train + w0, e.grad + w0, adam_m + w0, adam_v + w0, (int)V, (int)H, e.word_row_state, lr, beta1, beta2, eps,
-                                    weight_decay, step, grad_scale, 1, stream, gc, gf)) return r;
+        CHECK_RC(adamw_rows_impl(e.train + w0, e.grad + w0, adam_m + w0, adam_v + w0, (int)V, (int)H, e.word_row_state, lr, beta1, beta2, eps,
+                                    weight_decay, step, grad_scale, 1, stream, gc, gf));
     }
     return e.span(5, s);
 }

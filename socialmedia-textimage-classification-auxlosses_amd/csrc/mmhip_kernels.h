@@ -1,4 +1,5 @@
-// Internal launcher interface between the kernels (*.hip) and the engine / C ABI (engine.hip, capi.hip).
+// Internal launcher interface between the kernels (*.hip) and their callers: the two engines (engine.hip, early.hip) and the operator entry points
+// (capi_ops.hip).  How the callers fill these argument structs is written once, in mmhip_host.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
