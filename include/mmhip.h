@@ -79,6 +79,21 @@ uint64_t mmhip_buffer_numel(mmhip_handle h, int buffer);        /* fp32 elements
 uint64_t mmhip_workspace_bytes(mmhip_handle h);                 /* activations + 16-bit weight copies */
 /* frozen / train / train_grad are flat fp32 device buffers laid out as mmhip_param_info_at describes */
 int mmhip_bind(mmhip_handle h, float* frozen, float* train, float* train_grad, void* workspace, uint64_t workspace_bytes);
+/* ---- global-batch ITC under data parallelism (opt-in; reference: none, it is single-process -- utils.py:225-231 clip_loss is what is computed,
+ * on the logits of ALL ranks' posts).  With W ranks of B posts each, G = W * B: every rank gathers the L2-normalised text / image embeddings of
+ * all G posts in rank order, takes clip_loss on exp(logit_scale) T_n I_n^T [G, G] as its ITC term and backpropagates through its own B rows
+ * (which collect gradient from both cross-entropy directions and from every rank's rows), seeded with W so that the 1 / W gradient average of the
+ * exchange lands on the gradient one process computes on the concatenated batch.  logits_per_text stays the rank's own [B, B] block; ITM and
+ * evaluation (train = 0) stay rank-local.  Limits: G <= 8192, proj_dim <= 1024.
+ *   mmhip_reserve_itc_global(h, max_world): BEFORE mmhip_bind -- grows mmhip_workspace_bytes by the gathered [max_world * max_posts, proj_dim]
+ *       pairs and the kernels' scratch; 0 or 1 (and never calling it) keep the workspace size exactly.  MMHIP_E_STATE once bound.
+ *   mmhip_set_itc_global(h, world, rank): world 1 restores the rank-local path; world > the reservation: MMHIP_E_CAPACITY.
+ *   mmhip_itc_gather_buffers: device pointers (fp32) of the local normalised rows [B, proj_dim] of the last forward and of the gather buffers
+ *       [world * B, proj_dim] the caller fills (rank r's rows at r * B) between mmhip_forward(train) and mmhip_loss; mmhip_train_step_dp asks
+ *       for the same through on_stage(user, MMHIP_CB_GATHER_ITC). */
+int mmhip_reserve_itc_global(mmhip_handle h, int max_world);
+int mmhip_set_itc_global(mmhip_handle h, int world, int rank);
+int mmhip_itc_gather_buffers(mmhip_handle h, void** txt_local, void** img_local, void** txt_all, void** img_all);
 /* re-derive the 16-bit (and transposed) GEMM operand copies from the fp32 masters: which = 1 frozen, 2 train, 3 both.
  * Call after load_state_dict (models/mm_late.py:343-345) and after every optimizer step. */
 int mmhip_refresh_weights(mmhip_handle h, int which, void* stream);
@@ -228,7 +243,11 @@ int mmhip_train_step(mmhip_handle h, const int64_t* ids, const int64_t* mask, co
  *   on_stage(user, MMHIP_CB_FINISH_ROWS)  after the dense AdamW and the 16-bit weight refresh were enqueued: finish the row-sparse
  *                       word-table exchange (it travelled meanwhile); the row-lazy AdamW of the table follows.
  * A non-zero return aborts the step with that code.  grad_scale = 1 / world.  Everything else as mmhip_train_step. */
-enum { MMHIP_CB_WAIT_DENSE = -1, MMHIP_CB_FINISH_ROWS = -2, MMHIP_CB_WAIT_BUCKET = -3 };
+enum { MMHIP_CB_WAIT_DENSE = -1, MMHIP_CB_FINISH_ROWS = -2, MMHIP_CB_WAIT_BUCKET = -3, MMHIP_CB_GATHER_ITC = -4 };
+/* on_stage(user, MMHIP_CB_GATHER_ITC)  only with mmhip_set_itc_global(world > 1) and use_itc: issued once the forward -- and with it the
+ *                       normalisation of the local embeddings -- is enqueued: gather the rows (mmhip_itc_gather_buffers) and make `stream` wait
+ *                       for the two collectives; the loss and the backward of the heads follow when the callback returns 0.
+ * mmhip_train_step with world > 1 set returns MMHIP_E_STATE (nobody could gather). */
 /* Per-bucket optimizer (round 5).  on_stage(user, st) may return MMHIP_CB_BUCKET instead of 0: "the collective that carries the gradients of every
  * stage since my last MMHIP_CB_BUCKET answer, st included, has been started".  If the library runs the layer optimizers beside the backward (side
  * stream on), it then calls on_stage(user, MMHIP_CB_WAIT_BUCKET): the caller makes the library's SIDE stream (mmhip_side_stream) wait for that
@@ -364,6 +383,26 @@ int mmhip_op_attn_fwd(int dtype, const void* qkv, const float* maskbias, void* c
                       float p_drop, uint64_t seed, uint32_t stream_id, void* stream);
 int mmhip_op_attn_bwd(int dtype, const void* qkv, const float* maskbias, const void* ctx, const void* dctx, const float* lse,
                       void* dqkv, int posts, int S, int heads, float p_drop, uint64_t seed, uint32_t stream_id, void* stream);
+/* global-batch ITC on caller-owned buffers (no engine).  txt_n / img_n fp32 [G, E]: the gathered normalised rows; logit_scale a device scalar.
+ * G <= 8192, E <= 1024, else MMHIP_E_INVALID with nothing written.  ws: scratch of mmhip_op_itc_global_ws_bytes(G, B_local) bytes (forward and
+ * backward may share it).  Every call with the same inputs gives the same bits (ordered partial reductions, one writer per word).
+ *   fwd: logits [G, G] (may be NULL) = exp(logit_scale) txt_n img_n^T; rowlse / collse [G] its row / column log-sum-exps; loss [1] = clip_loss.
+ *   bwd: for the rows [rank_offset, rank_offset + B_local) -- MMHIP_E_INVALID past G -- d_txt_n / d_img_n [B_local, E] = d(seed * loss) / d of the
+ *        local normalised rows, d_logit_scale[0] += the same w.r.t. logit_scale restricted to the local TEXT rows' strip of the logits (the
+ *        strips of all ranks sum to the full derivative); txt_inv / img_inv [B_local] (1 / |e|) with d_txt_e / d_img_e [B_local, E]: the same
+ *        through the normalisation (all four may be NULL). */
+uint64_t mmhip_op_itc_global_ws_bytes(int G, int B_local);
+/* the rank-local ITC pair the engine runs at world 1 (csrc/heads.hip launch_itc_fwd / launch_itc_bwd), for timing beside the global pair
+ * (tools/itc_bench.py): normalisation + logits_per_text [B, B]; its backward from d_logits [B, B] (d_logit_scale accumulated, may be NULL) */
+int mmhip_op_itc_fwd(const float* txt_e, const float* img_e, const float* logit_scale, int B, int E, float* txt_n, float* img_n, float* txt_inv, float* img_inv,
+                     float* logits, void* stream);
+int mmhip_op_itc_bwd(const float* d_logits, const float* logits, const float* txt_n, const float* img_n, const float* txt_inv, const float* img_inv,
+                     const float* logit_scale, int B, int E, float* d_txt_e, float* d_img_e, float* d_logit_scale, void* stream);
+int mmhip_op_itc_global_fwd(const float* txt_n, const float* img_n, const float* logit_scale, int G, int E, float* logits, float* rowlse, float* collse,
+                            float* loss, void* ws, uint64_t ws_bytes, void* stream);
+int mmhip_op_itc_global_bwd(const float* txt_n, const float* img_n, const float* logit_scale, const float* rowlse, const float* collse, int G, int B_local,
+                            int rank_offset, int E, float seed, float* d_txt_n, float* d_img_n, float* d_logit_scale, const float* txt_inv,
+                            const float* img_inv, float* d_txt_e, float* d_img_e, void* ws, uint64_t ws_bytes, void* stream);
 int mmhip_op_colsum(int dtype, const void* x, int rows, int cols, int ld, float* out, void* stream);
 int mmhip_op_cast(int dtype, const float* src, void* dst, uint64_t n, int transpose_rows, int transpose_cols, void* stream);
 /* Which kernel ran: what the GEMM launchers actually launched for the CALLING THREAD's most recent NT (which = 0: mmhip_op_gemm_nt and every NT product

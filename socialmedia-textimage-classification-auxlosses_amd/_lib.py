@@ -51,6 +51,7 @@ class MMHipError(RuntimeError):
 
 EXCHANGE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int)      # include/mmhip.h: mmhip_exchange_cb
 CB_WAIT_DENSE, CB_FINISH_ROWS, CB_WAIT_BUCKET = -1, -2, -3
+CB_GATHER_ITC = -4           # include/mmhip.h MMHIP_CB_GATHER_ITC: gather the normalised ITC rows of all ranks (global-batch ITC)
 CB_HANDLED = 1               # include/mmhip.h MMHIP_CB_HANDLED: the caller ran the dense optimizer itself
 CB_BUCKET = 2                # include/mmhip.h MMHIP_CB_BUCKET: a collective carrying every stage since the last such answer has been started
 _lib = None
@@ -63,6 +64,9 @@ _SIGS = {
     "mmhip_param_info_at": (I, [P, I, C.POINTER(ParamInfo)]),
     "mmhip_buffer_numel": (U64, [P, I]),
     "mmhip_workspace_bytes": (U64, [P]),
+    "mmhip_reserve_itc_global": (I, [P, I]),
+    "mmhip_set_itc_global": (I, [P, I, I]),
+    "mmhip_itc_gather_buffers": (I, [P, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P)]),
     "mmhip_bind": (I, [P, P, P, P, P, U64]),
     "mmhip_refresh_weights": (I, [P, I, P]),
     "mmhip_forward": (I, [P, P, P, P, P, P, I, I, I, U64, P, P, P, P, P]),
@@ -116,6 +120,11 @@ _SIGS = {
     "mmhip_op_layernorm_bwd": (I, [I, P, P, P, P, P, P, P, P, P, I, I, P]),
     "mmhip_op_attn_fwd": (I, [I, P, P, P, P, I, I, I, F, U64, U32, P]),
     "mmhip_op_attn_bwd": (I, [I, P, P, P, P, P, P, I, I, I, F, U64, U32, P]),
+    "mmhip_op_itc_global_ws_bytes": (U64, [I, I]),
+    "mmhip_op_itc_fwd": (I, [P, P, P, I, I, P, P, P, P, P, P]),
+    "mmhip_op_itc_bwd": (I, [P, P, P, P, P, P, P, I, I, P, P, P, P]),
+    "mmhip_op_itc_global_fwd": (I, [P, P, P, I, I, P, P, P, P, P, U64, P]),
+    "mmhip_op_itc_global_bwd": (I, [P, P, P, P, P, I, I, I, I, F, P, P, P, P, P, P, P, P, U64, P]),
     "mmhip_op_colsum": (I, [I, P, I, I, I, P, P]),
     "mmhip_op_cast": (I, [I, P, P, U64, I, I, P]),
     "mmhip_op_probe_layouts": (I, [P, P]),

@@ -336,4 +336,49 @@ int mmhip_op_cast(int dtype, const float* src, void* dst, uint64_t n, int transp
     return 0;
 }
 
+
+// ------------------------------------------------------------------------------------------------ ITC (rank-local pair: timing reference of the global one)
+int mmhip_op_itc_fwd(const float* txt_e, const float* img_e, const float* logit_scale, int B, int E, float* txt_n, float* img_n, float* txt_inv, float* img_inv,
+                     float* logits, void* stream) {
+    if (B < 1 || B > 1024 || E < 1 || E > 1024 || !txt_e || !img_e || !logit_scale || !txt_n || !img_n || !txt_inv || !img_inv || !logits) return MMHIP_E_INVALID;
+    ItcArgs a{txt_e, img_e, logit_scale, txt_n, img_n, txt_inv, img_inv, logits, B, E};
+    CHECK_HIP(launch_itc_fwd(a, (hipStream_t)stream));
+    return 0;
+}
+int mmhip_op_itc_bwd(const float* d_logits, const float* logits, const float* txt_n, const float* img_n, const float* txt_inv, const float* img_inv,
+                     const float* logit_scale, int B, int E, float* d_txt_e, float* d_img_e, float* d_logit_scale, void* stream) {
+    if (B < 1 || B > 1024 || E < 1 || E > 1024 || !d_logits || !logits || !txt_n || !img_n || !txt_inv || !img_inv || !logit_scale || !d_txt_e || !d_img_e) return MMHIP_E_INVALID;
+    ItcBwdArgs a{d_logits, logits, txt_n, img_n, txt_inv, img_inv, logit_scale, d_txt_e, d_img_e, d_logit_scale, B, E};
+    CHECK_HIP(launch_itc_bwd(a, (hipStream_t)stream));
+    return 0;
+}
+// ------------------------------------------------------------------------------------------------ global-batch ITC
+uint64_t mmhip_op_itc_global_ws_bytes(int G, int B_local) {
+    if (G < 1 || G > ITC_GLOBAL_MAX_G || B_local < 1 || B_local > G) return 0;
+    return (uint64_t)itc_global_ws_floats(G, B_local) * 4;
+}
+int mmhip_op_itc_global_fwd(const float* txt_n, const float* img_n, const float* logit_scale, int G, int E, float* logits, float* rowlse, float* collse,
+                            float* loss, void* ws, uint64_t ws_bytes, void* stream) {
+    if (G < 1 || G > ITC_GLOBAL_MAX_G || E < 1 || E > 1024) return MMHIP_E_INVALID;
+    if (!txt_n || !img_n || !logit_scale || !rowlse || !collse || !loss || !ws) return MMHIP_E_INVALID;
+    if (ws_bytes < (uint64_t)itc_global_ws_floats(G, 1) * 4) return MMHIP_E_CAPACITY;
+    ItcGlobalArgs a{txt_n, img_n, logit_scale, logits, rowlse, collse, loss, (float*)ws, G, E};
+    CHECK_HIP(launch_itc_global_fwd(a, (hipStream_t)stream));
+    return 0;
+}
+int mmhip_op_itc_global_bwd(const float* txt_n, const float* img_n, const float* logit_scale, const float* rowlse, const float* collse, int G, int B_local,
+                            int rank_offset, int E, float seed, float* d_txt_n, float* d_img_n, float* d_logit_scale, const float* txt_inv,
+                            const float* img_inv, float* d_txt_e, float* d_img_e, void* ws, uint64_t ws_bytes, void* stream) {
+    if (G < 1 || G > ITC_GLOBAL_MAX_G || E < 1 || E > 1024 || B_local < 1 || rank_offset < 0 || (int64_t)rank_offset + B_local > G) return MMHIP_E_INVALID;
+    if (!txt_n || !img_n || !logit_scale || !rowlse || !collse || !d_txt_n || !d_img_n || !ws) return MMHIP_E_INVALID;
+    if ((d_txt_e && !txt_inv) || (d_img_e && !img_inv)) return MMHIP_E_INVALID;
+    if (ws_bytes < (uint64_t)itc_global_ws_floats(G, B_local) * 4) return MMHIP_E_CAPACITY;
+    ItcGlobalBwdArgs a{};
+    a.txt_n = txt_n; a.img_n = img_n; a.logit_scale = logit_scale; a.rowlse = rowlse; a.collse = collse; a.txt_inv = txt_inv; a.img_inv = img_inv;
+    a.d_txt_n = d_txt_n; a.d_img_n = d_img_n; a.dtxt_e = d_txt_e; a.dimg_e = d_img_e; a.dlogit_scale = d_logit_scale; a.ws = (float*)ws;
+    a.G = G; a.E = E; a.Bl = B_local; a.r0 = rank_offset; a.scale = seed / (2.f * (float)G);
+    CHECK_HIP(launch_itc_global_bwd(a, (hipStream_t)stream));
+    return 0;
+}
+
 }  // extern "C"

@@ -74,6 +74,11 @@ struct mmhip_engine {
     bool skip_itc = false, itc_done = false;   // mmhip_train_step without the ITC loss: the dual-encoder similarity head (text pooler, both projections,
                                                // normalisation, logits: five launches on the critical path between towers and backward) is not run
     uint64_t seed = 0;
+    // global-batch ITC (mmhip_reserve_itc_global / mmhip_set_itc_global): slices behind ws_base, present only after a reservation
+    size_t ws_base = 0;                        // workspace bytes of a handle that never reserved: build_workspace's total
+    int itc_max_world = 0, itc_world = 1, itc_rank = 0;
+    size_t h_g_txt = 0, h_g_img = 0, h_g_rowlse = 0, h_g_collse = 0, h_g_loss = 0, h_g_dtn = 0, h_g_din = 0, h_g_ws = 0;
+    bool bd_itc_global = false; float bd_w_itc = 0.f;      // the last mmhip_loss took the gathered form: heads_backward runs launch_itc_global_bwd
     const float *bd_out_cls = nullptr, *bd_logits = nullptr, *bd_out_tim = nullptr, *bd_feats = nullptr;
     // internal side stream (ViT forward beside the text forward; weight gradients beside the dX chain) -------------
     hipStream_t side = nullptr;          // weight-gradient work of the backward
@@ -347,7 +352,7 @@ void build_workspace(mmhip_engine& e) {
     e.h_d_out_cls = f(Bm * C); e.h_d_logits = f(Bm * Bm); e.h_d_out_tim = f(Bm * 2); e.h_dfeats = f(Bt * H); e.h_dpre = f(Bt * H);
     e.h_dz = f(Bt * (H + Hv)); e.h_dxcls = f(Bt * H); e.h_dxbar = f(Bt * H); e.h_dqk = f(Bt * H); e.h_dq = f(Bt * H);
     e.h_dtxt_e = f(Bm * E); e.h_dimg_e = f(Bm * E); e.h_dtpool = f(Bm * H); e.h_dprepool = f(Bm * H); e.h_loss = f(8);
-    e.ws_need = w.off;
+    e.ws_need = e.ws_base = w.off;
 }
 
 enum { STREAM_EMBED = 1, STREAM_HEAD = 2 };
@@ -840,10 +845,26 @@ int heads_backward(mmhip_engine& e, hipStream_t s) {
         CHECK_HIP(launch_bias_grad_f32(e.wsp<float>(e.h_dq), Bt, H, H, Gd + e.fq_b, 1, s));
         CHECK_HIP(launch_small_nn(small(e.wsp<float>(e.h_dq), H, W + e.fq_w, H, nullptr, dxcls, H, Bt, H, H, ACT_NONE, 1), s));
     }
-    if (d_logits) {
-        ItcBwdArgs ib{d_logits, e.wsp<float>(e.h_logits), e.wsp<float>(e.h_txt_n), e.wsp<float>(e.h_img_n), e.wsp<float>(e.h_txt_inv),
-                      e.wsp<float>(e.h_img_inv), W + e.logit_scale, e.wsp<float>(e.h_dtxt_e), e.wsp<float>(e.h_dimg_e), Gd + e.logit_scale, B, E};
-        CHECK_HIP(launch_itc_bwd(ib, s));
+    if (d_logits || e.bd_itc_global) {
+        if (e.bd_itc_global) {
+            // gathered form: this rank's rows of d T_n / d I_n collect both cross-entropy directions over all G posts.  Seed: the loss is the SAME
+            // global clip_loss on every rank and each rank differentiates it through its own rows only, so the ranks' parameter gradients sum to
+            // the single-process gradient; the exchange then averages (1 / world), hence the factor `world` here
+            const int G = e.itc_world * B;
+            ItcGlobalBwdArgs gb{};
+            gb.txt_n = e.wsp<float>(e.h_g_txt); gb.img_n = e.wsp<float>(e.h_g_img); gb.logit_scale = W + e.logit_scale;
+            gb.rowlse = e.wsp<float>(e.h_g_rowlse); gb.collse = e.wsp<float>(e.h_g_collse);
+            gb.txt_inv = e.wsp<float>(e.h_txt_inv); gb.img_inv = e.wsp<float>(e.h_img_inv);
+            gb.d_txt_n = e.wsp<float>(e.h_g_dtn); gb.d_img_n = e.wsp<float>(e.h_g_din);
+            gb.dtxt_e = e.wsp<float>(e.h_dtxt_e); gb.dimg_e = e.wsp<float>(e.h_dimg_e); gb.dlogit_scale = Gd + e.logit_scale;
+            gb.ws = e.wsp<float>(e.h_g_ws); gb.G = G; gb.E = E; gb.Bl = B; gb.r0 = e.itc_rank * B;
+            gb.scale = e.bd_w_itc * (float)e.itc_world / (2.f * (float)G);
+            CHECK_HIP(launch_itc_global_bwd(gb, s));
+        } else {
+            ItcBwdArgs ib{d_logits, e.wsp<float>(e.h_logits), e.wsp<float>(e.h_txt_n), e.wsp<float>(e.h_img_n), e.wsp<float>(e.h_txt_inv),
+                          e.wsp<float>(e.h_img_inv), W + e.logit_scale, e.wsp<float>(e.h_dtxt_e), e.wsp<float>(e.h_dimg_e), Gd + e.logit_scale, B, E};
+            CHECK_HIP(launch_itc_bwd(ib, s));
+        }
         CHECK_HIP(launch_small_tn(small(e.wsp<float>(e.h_dtxt_e), E, e.wsp<float>(e.h_tpool), H, nullptr, Gd + e.tproj_w, H, B, H, 0, 0, 1), DT_F32, E, s));
         CHECK_HIP(launch_small_tn(small(e.wsp<float>(e.h_dimg_e), E, e.wsp<float>(e.h_vpool), Hv, nullptr, Gd + e.vproj_w, Hv, B, Hv, 0, 0, 1), DT_F32, E, s));
         CHECK_HIP(launch_small_nn(small(e.wsp<float>(e.h_dtxt_e), E, W + e.tproj_w, H, nullptr, e.wsp<float>(e.h_dtpool), H, B, H, E), s));
@@ -1072,6 +1093,38 @@ int mmhip_param_info_at(mmhip_handle h, int i, mmhip_param_info* out) {
 }
 uint64_t mmhip_buffer_numel(mmhip_handle h, int buffer) { return !h ? 0 : (buffer == 0 ? h->n_frozen : h->n_train); }
 uint64_t mmhip_workspace_bytes(mmhip_handle h) { return h ? h->ws_need : 0; }
+int mmhip_reserve_itc_global(mmhip_handle h, int max_world) {
+    if (!h || max_world < 0) return MMHIP_E_INVALID;
+    if (h->ws) return MMHIP_E_STATE;          // the workspace is sized before it is bound
+    mmhip_engine& e = *h;
+    const size_t Bm = e.cfg.max_posts, E = e.cfg.proj_dim, Gm = (size_t)max_world * Bm;
+    if (max_world > 1 && Gm > (size_t)ITC_GLOBAL_MAX_G) return MMHIP_E_INVALID;
+    e.itc_max_world = max_world > 1 ? max_world : 0;
+    e.itc_world = 1; e.itc_rank = 0;
+    e.ws_need = e.ws_base;
+    if (!e.itc_max_world) return 0;
+    Carver w;
+    w.off = e.ws_base;
+    e.h_g_txt = w.take(Gm * E * 4); e.h_g_img = w.take(Gm * E * 4); e.h_g_rowlse = w.take(Gm * 4); e.h_g_collse = w.take(Gm * 4); e.h_g_loss = w.take(16);
+    e.h_g_dtn = w.take(Bm * E * 4); e.h_g_din = w.take(Bm * E * 4); e.h_g_ws = w.take(itc_global_ws_floats((int)Gm, (int)Bm) * 4);
+    e.ws_need = w.off;
+    return 0;
+}
+int mmhip_set_itc_global(mmhip_handle h, int world, int rank) {
+    if (!h || world < 1 || rank < 0 || rank >= world) return MMHIP_E_INVALID;
+    if (world > 1 && world > h->itc_max_world) return MMHIP_E_CAPACITY;
+    h->itc_world = world; h->itc_rank = rank;
+    return 0;
+}
+int mmhip_itc_gather_buffers(mmhip_handle h, void** txt_local, void** img_local, void** txt_all, void** img_all) {
+    if (!h || !h->ws || !h->itc_max_world) return MMHIP_E_STATE;
+    const mmhip_engine& e = *h;
+    if (txt_local) *txt_local = e.ws + e.h_txt_n;
+    if (img_local) *img_local = e.ws + e.h_img_n;
+    if (txt_all) *txt_all = e.ws + e.h_g_txt;
+    if (img_all) *img_all = e.ws + e.h_g_img;
+    return 0;
+}
 int mmhip_bind(mmhip_handle h, float* frozen, float* train, float* train_grad, void* workspace, uint64_t workspace_bytes) {
     if (!h || !frozen || !train || !workspace) return MMHIP_E_INVALID;
     if (workspace_bytes < h->ws_need) return MMHIP_E_CAPACITY;
@@ -1219,21 +1272,31 @@ int mmhip_loss(mmhip_handle h, const int64_t* onehot, const float* class_w, cons
     mmhip_engine& e = *h;
     if (w_itm != 0.f && (!e.itm || !lbl_tim)) return MMHIP_E_INVALID;
     if (w_itc != 0.f && !e.itc_done) return MMHIP_E_STATE;
+    hipStream_t s = (hipStream_t)stream;
+    // global-batch ITC: a training forward whose normalised rows the caller has gathered (MMHIP_CB_GATHER_ITC / mmhip_itc_gather_buffers) takes its
+    // ITC term from the G x G logits of all ranks' posts; evaluation and world 1 keep the rank's own [B, B] block
+    const bool glob = e.itc_world > 1 && e.train_mode && w_itc != 0.f;
     LossArgs a{};
     a.out_cls = e.wsp<float>(e.h_out_cls); a.onehot = onehot; a.class_w = class_w;
-    a.logits_per_text = w_itc != 0.f ? e.wsp<float>(e.h_logits) : nullptr;
+    if (glob) {
+        ItcGlobalArgs ga{e.wsp<float>(e.h_g_txt), e.wsp<float>(e.h_g_img), e.train + e.logit_scale, nullptr, e.wsp<float>(e.h_g_rowlse),
+                         e.wsp<float>(e.h_g_collse), e.wsp<float>(e.h_g_loss), e.wsp<float>(e.h_g_ws), e.itc_world * e.B, e.cfg.proj_dim};
+        CHECK_HIP(launch_itc_global_fwd(ga, s));
+        a.itc_global_loss = ga.loss;
+    }
+    a.logits_per_text = w_itc != 0.f && !glob ? e.wsp<float>(e.h_logits) : nullptr;
     a.out_tim = w_itm != 0.f ? e.wsp<float>(e.h_out_tim) : nullptr; a.lbl_tim = lbl_tim;
     a.w_cls = w_cls; a.w_itc = w_itc; a.w_itm = w_itm;
     a.loss = e.wsp<float>(e.h_loss);
     a.d_out_cls = e.wsp<float>(e.h_d_out_cls);
-    a.d_logits = w_itc != 0.f ? e.wsp<float>(e.h_d_logits) : nullptr;
+    a.d_logits = w_itc != 0.f && !glob ? e.wsp<float>(e.h_d_logits) : nullptr;
     a.d_out_tim = w_itm != 0.f ? e.wsp<float>(e.h_d_out_tim) : nullptr;
     a.n_correct = n_correct;
     a.B = e.B; a.C = e.cfg.num_labels;
-    hipStream_t s = (hipStream_t)stream;
     CHECK_HIP(launch_loss(a, s));
     if (loss) CHECK_HIP(hipMemcpyAsync(loss, a.loss, 16, hipMemcpyDeviceToDevice, s));
     e.bd_out_cls = a.d_out_cls; e.bd_logits = a.d_logits; e.bd_out_tim = a.d_out_tim; e.bd_feats = nullptr;
+    e.bd_itc_global = glob; e.bd_w_itc = w_itc;
     return 0;
 }
 
@@ -1255,6 +1318,7 @@ int mmhip_backward_begin(mmhip_handle h, const float* d_out_cls, const float* d_
     if (d_out_cls || d_logits || d_out_tim || d_feats) {
         if (!d_out_cls) return MMHIP_E_INVALID;
         e.bd_out_cls = d_out_cls; e.bd_logits = d_logits; e.bd_out_tim = d_out_tim; e.bd_feats = d_feats;
+        e.bd_itc_global = false;          // explicit output gradients (autograd binding): d_logits is the rank's own [B, B] block
     } else if (!e.bd_out_cls) {
         return MMHIP_E_STATE;      // no mmhip_loss before, and no explicit gradients
     }
@@ -1404,6 +1468,12 @@ static int train_step_impl(mmhip_handle h, const int64_t* ids, const int64_t* ma
                                  nullptr, nullptr, stream);
     e.skip_itc = false;
     if (rf) return rf;
+    if (e.itc_world > 1 && use_itc) {
+        // global-batch ITC: the local rows are normalised; the caller gathers every rank's (mmhip_itc_gather_buffers) and orders the
+        // collectives before what follows in `stream`.  Without a callback nobody can fill the gathered rows
+        if (!cb) return MMHIP_E_STATE;
+        CHECK_RC(cb(user, MMHIP_CB_GATHER_ITC));
+    }
     CHECK_RC(mmhip_loss(h, onehot, class_w, use_itm ? lbl_tim : nullptr, w_cls, use_itc ? w_itc : 0.f, use_itm ? w_itm : 0.f, loss, n_correct, stream));
     // Backward.  With the side stream on, each text layer's AdamW and 16-bit weight refresh follow its weight-gradient GEMM on the
     // SIDE stream, beside the activation-gradient chain of the layers below (an HBM-bound kernel next to MFMA-bound ones) instead

@@ -223,6 +223,159 @@ __global__ __launch_bounds__(256) void itc_bwd_kernel(ItcBwdArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------ global-batch ITC
+// Data parallelism with gathered embeddings: G = world * B posts, T_n / I_n [G, E] hold every rank's normalised rows in rank order, the logits
+// S = exp(logit_scale) T_n I_n^T are G x G and the loss is clip_loss on S (utils.py:225-231).  G x G does not fit anywhere convenient (8192^2 fp32 =
+// 256 MB), so S is never needed in memory: a workgroup owns one 32 x 32 tile, built like small_gemm_kernel's (exact fp32 on
+// v_mfma_f32_32x32x2_f32, the K range split over the 8 waves, partial tiles summed through LDS in wave order), and leaves
+//   forward   per tile-column tj an online-softmax pair (max, sum exp) of every row over the tile's 32 columns, per tile-row ti the same of every
+//             column over its 32 rows, and the diagonal; itc_global_lse_kernel folds the G / 32 pairs of a row / column IN TILE ORDER into
+//             rowlse / collse -- both log-sum-exps from one pass over S, every word has one writer, no atomics: the same bits on every call;
+//   backward  the rank's strips of dS = scale (softmax_row + softmax_col - 2 I): rows [r0, r0 + Bl) x all columns (-> d T_n of the local texts, and
+//             d logit_scale = sum dS S over that strip: the strips of the ranks tile S exactly once) and all rows x columns [r0, r0 + Bl)
+//             (stored transposed, -> d I_n of the local images), recomputed from the gathered rows; the two [Bl, G] x [G, E] products that follow
+//             are small_gemm launches.
+static constexpr int IG_WAVES = 8, IG_THREADS = IG_WAVES * 64;
+// tile[r][c] = es * T[i0 + r] . I[j0 + c] (rows / columns past G repeat row G - 1: finite, never stored).  Ends with a barrier.
+__device__ __forceinline__ void itc_tile(const float* __restrict__ T, const float* __restrict__ I, int G, int E, int i0, int j0, float es,
+                                         float (*red)[32][32], float (*tile)[33]) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int r = lane & 31, h = lane >> 5;
+    const float* Tp = T + (size_t)min(i0 + r, G - 1) * E;
+    const float* Ip = I + (size_t)min(j0 + r, G - 1) * E;
+    f32x16 acc = f32x16{};
+    for (int k0 = w * 8 + h * 4; k0 < E; k0 += 8 * IG_WAVES) {
+        float av[4], bv[4];
+        if (k0 + 3 < E && ((((uintptr_t)(Tp + k0)) | ((uintptr_t)(Ip + k0))) & 15) == 0) {
+            const f32x4 ta = *reinterpret_cast<const f32x4*>(Tp + k0), tb = *reinterpret_cast<const f32x4*>(Ip + k0);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { av[e] = ta[e]; bv[e] = tb[e]; }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { av[e] = k0 + e < E ? Tp[k0 + e] : 0.f; bv[e] = k0 + e < E ? Ip[k0 + e] : 0.f; }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[e], bv[e], acc, 0, 0, 0);
+    }
+    // D: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) red[w][(reg & 3) + 8 * (reg >> 2) + 4 * h][r] = acc[reg];
+    __syncthreads();
+    for (int i = threadIdx.x; i < 32 * 32; i += IG_THREADS) {
+        const int row = i >> 5, col = i & 31;
+        float v = 0.f;
+#pragma unroll
+        for (int ww = 0; ww < IG_WAVES; ++ww) v += red[ww][row][col];
+        tile[row][col] = v * es;
+    }
+    __syncthreads();
+}
+__global__ __launch_bounds__(IG_THREADS) void itc_global_fwd_kernel(ItcGlobalArgs a, float* row_m, float* row_s, float* col_m, float* col_s, float* diag) {
+    __shared__ float red[IG_WAVES][32][32];
+    __shared__ float tile[32][33];
+    const int tj = blockIdx.x, ti = blockIdx.y, i0 = ti * 32, j0 = tj * 32, G = a.G, t = threadIdx.x;
+    itc_tile(a.txt_n, a.img_n, G, a.E, i0, j0, expf(a.logit_scale[0]), red, tile);
+    const int nr = min(32, G - i0), nc = min(32, G - j0);
+    if (a.logits)
+        for (int i = t; i < 32 * 32; i += IG_THREADS) {
+            const int row = i >> 5, col = i & 31;
+            if (row < nr && col < nc) a.logits[(size_t)(i0 + row) * G + j0 + col] = tile[row][col];
+        }
+    if (t < 32) {                     // row t of the tile over its columns
+        if (t < nr) {
+            float m = -INFINITY, s = 0.f;
+            for (int c = 0; c < nc; ++c) m = fmaxf(m, tile[t][c]);
+            for (int c = 0; c < nc; ++c) s += expf(tile[t][c] - m);
+            row_m[(size_t)tj * G + i0 + t] = m; row_s[(size_t)tj * G + i0 + t] = s;
+        }
+    } else if (t < 64) {              // column t - 32 over its rows
+        const int c = t - 32;
+        if (c < nc) {
+            float m = -INFINITY, s = 0.f;
+            for (int r = 0; r < nr; ++r) m = fmaxf(m, tile[r][c]);
+            for (int r = 0; r < nr; ++r) s += expf(tile[r][c] - m);
+            col_m[(size_t)ti * G + j0 + c] = m; col_s[(size_t)ti * G + j0 + c] = s;
+        }
+    } else if (t < 96 && ti == tj) {
+        if (t - 64 < nr) diag[i0 + t - 64] = tile[t - 64][t - 64];
+    }
+}
+// one thread per index i: rowlse[i], collse[i], term[i] = (rowlse[i] - S_ii) + (collse[i] - S_ii)
+__global__ __launch_bounds__(256) void itc_global_lse_kernel(ItcGlobalArgs a, const float* row_m, const float* row_s, const float* col_m, const float* col_s,
+                                                             const float* diag, float* term) {
+    const int i = blockIdx.x * 256 + threadIdx.x, G = a.G, nt = (G + 31) / 32;
+    if (i >= G) return;
+    float lse[2];
+#pragma unroll
+    for (int d = 0; d < 2; ++d) {
+        const float* pm = d ? col_m : row_m;
+        const float* ps = d ? col_s : row_s;
+        float m = -INFINITY, s = 0.f;
+        for (int t = 0; t < nt; ++t) m = fmaxf(m, pm[(size_t)t * G + i]);
+        for (int t = 0; t < nt; ++t) s += ps[(size_t)t * G + i] * expf(pm[(size_t)t * G + i] - m);
+        lse[d] = m + logf(s);
+    }
+    a.rowlse[i] = lse[0]; a.collse[i] = lse[1];
+    term[i] = (lse[0] - diag[i]) + (lse[1] - diag[i]);
+}
+// loss = sum_i term[i] / (2 G): one block, fixed order
+__global__ __launch_bounds__(256) void itc_global_loss_kernel(const float* term, int G, float* loss) {
+    __shared__ float red[4];
+    float s = 0.f;
+    for (int i = threadIdx.x; i < G; i += 256) s += term[i];
+    s = block_reduce(s, red, false);
+    if (threadIdx.x == 0) loss[0] = s / (2.f * G);
+}
+// blockIdx.z = 0: text rows [r0, r0 + Bl) x image columns tile blockIdx.x -> grow [Bl, G], dls_part;  1: text rows tile blockIdx.x x image columns
+// [r0, r0 + Bl) -> gcol [Bl, G] (transposed).  Entries are dS * es: the factor of d(S)/d(T_n I_n^T)
+__global__ __launch_bounds__(IG_THREADS) void itc_global_grad_kernel(ItcGlobalBwdArgs a, float* grow, float* gcol, float* dls_part) {
+    __shared__ float red[IG_WAVES][32][32];
+    __shared__ float tile[32][33];
+    __shared__ float rsum[IG_WAVES];
+    const bool colside = blockIdx.z != 0;
+    const int G = a.G, t = threadIdx.x, hi = a.r0 + a.Bl;
+    const int i0 = colside ? blockIdx.x * 32 : a.r0 + blockIdx.y * 32, j0 = colside ? a.r0 + blockIdx.y * 32 : blockIdx.x * 32;
+    const float es = expf(a.logit_scale[0]);
+    itc_tile(a.txt_n, a.img_n, G, a.E, i0, j0, es, red, tile);
+    float part = 0.f;
+    for (int i = t; i < 32 * 32; i += IG_THREADS) {
+        // consecutive threads walk the long (all-G) direction of the strip: coalesced stores on both sides
+        const int row = colside ? (i & 31) : (i >> 5), col = colside ? (i >> 5) : (i & 31);
+        const int gi = i0 + row, gj = j0 + col;
+        if (gi >= (colside ? G : hi) || gj >= (colside ? hi : G)) continue;
+        const float s = tile[row][col];
+        const float g = (expf(s - a.rowlse[gi]) + expf(s - a.collse[gj]) - (gi == gj ? 2.f : 0.f)) * a.scale;
+        if (colside) gcol[(size_t)(gj - a.r0) * G + gi] = g * es;
+        else { grow[(size_t)(gi - a.r0) * G + gj] = g * es; part += g * s; }
+    }
+    if (!colside) {
+        part = block_reduce(part, rsum, false);
+        if (t == 0) dls_part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = part;
+    }
+}
+// block b < Bl: text row r0 + b, block Bl + b: image row r0 + b -- d e = (d n - n (d n . n)) / |e|; block 0 adds the ordered sum of dls_part
+__global__ __launch_bounds__(256) void itc_global_normbwd_kernel(ItcGlobalBwdArgs a, const float* dls_part, int n_part) {
+    __shared__ float red[4];
+    const int i = blockIdx.x % a.Bl;
+    const bool img = blockIdx.x >= a.Bl;
+    float* out = img ? a.dimg_e : a.dtxt_e;
+    if (out) {
+        const float* mine = (img ? a.img_n : a.txt_n) + (size_t)(a.r0 + i) * a.E;
+        const float* dn = (img ? a.d_img_n : a.d_txt_n) + (size_t)i * a.E;
+        float dot = 0.f;
+        for (int c = threadIdx.x; c < a.E; c += 256) dot += dn[c] * mine[c];
+        dot = block_reduce(dot, red, false);
+        const float inv = (img ? a.img_inv : a.txt_inv)[i];
+        for (int c = threadIdx.x; c < a.E; c += 256) out[(size_t)i * a.E + c] = (dn[c] - mine[c] * dot) * inv;
+    }
+    if (blockIdx.x == 0 && a.dlogit_scale) {
+        float s = 0.f;
+        for (int k = threadIdx.x; k < n_part; k += 256) s += dls_part[k];
+        s = block_reduce(s, red, false);
+        if (threadIdx.x == 0) a.dlogit_scale[0] += s;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ losses (one block)
 __global__ __launch_bounds__(256) void loss_kernel(LossArgs a) {
     __shared__ float red[4];
@@ -282,6 +435,8 @@ __global__ __launch_bounds__(256) void loss_kernel(LossArgs a) {
                 const float s = S[k];
                 a.d_logits[k] = a.w_itc * (__expf(s - rowlse[i]) + __expf(s - collse[j]) - (i == j ? 2.f : 0.f)) / (2.f * B);
             }
+    } else if (a.itc_global_loss) {
+        li = a.itc_global_loss[0];      // global-batch ITC: the loss over the gathered G x G logits (launch_itc_global_fwd); its gradient is launch_itc_global_bwd's
     }
     // ---- ITM: index-target CE, mean
     float lm = 0.f;
@@ -299,7 +454,7 @@ __global__ __launch_bounds__(256) void loss_kernel(LossArgs a) {
         lm = block_reduce(lm, red, false) / B;
     }
     if (t == 0) {
-        a.loss[0] = a.w_cls * lc + (a.logits_per_text ? a.w_itc * li : 0.f) + (a.out_tim ? a.w_itm * lm : 0.f);
+        a.loss[0] = a.w_cls * lc + ((a.logits_per_text || a.itc_global_loss) ? a.w_itc * li : 0.f) + (a.out_tim ? a.w_itm * lm : 0.f);
         a.loss[1] = lc; a.loss[2] = li; a.loss[3] = lm;
         if (a.n_correct) a.n_correct[0] = (int)(fc + 0.5f);
     }
@@ -407,6 +562,39 @@ hipError_t launch_itc_bwd(const ItcBwdArgs& a, hipStream_t s) {
     if (a.B <= 0) return hipSuccess;
     if (a.E > 1024) return hipErrorInvalidValue;
     hipLaunchKernelGGL(itc_bwd_kernel, dim3(2 * a.B), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+// fp32 words of ItcGlobalArgs::ws / ItcGlobalBwdArgs::ws: forward -- the (max, sum) pairs of both directions per 32-wide tile [4][G / 32][G], the
+// diagonal [G], the loss terms [G]; backward -- the two dS strips [2][Bl][G] and the d logit_scale partial of every tile of the row strip
+static size_t itc_global_fwd_words(int G) { return (size_t)(4 * ((G + 31) / 32) + 2) * G; }
+size_t itc_global_ws_floats(int G, int Bl) { return itc_global_fwd_words(G) + 2 * (size_t)Bl * G + (size_t)((Bl + 31) / 32) * ((G + 31) / 32); }
+static bool itc_global_shape_ok(int G, int E) { return G >= 1 && G <= ITC_GLOBAL_MAX_G && E >= 1 && E <= 1024; }
+hipError_t launch_itc_global_fwd(const ItcGlobalArgs& a, hipStream_t s) {
+    if (!itc_global_shape_ok(a.G, a.E) || !a.txt_n || !a.img_n || !a.logit_scale || !a.rowlse || !a.collse || !a.loss || !a.ws) return hipErrorInvalidValue;
+    const int G = a.G, nt = (G + 31) / 32;
+    const size_t pg = (size_t)nt * G;
+    float *row_m = a.ws, *row_s = row_m + pg, *col_m = row_s + pg, *col_s = col_m + pg, *diag = col_s + pg, *term = diag + G;
+    hipLaunchKernelGGL(itc_global_fwd_kernel, dim3(nt, nt), dim3(IG_THREADS), 0, s, a, row_m, row_s, col_m, col_s, diag);
+    hipLaunchKernelGGL(itc_global_lse_kernel, dim3((G + 255) / 256), dim3(256), 0, s, a, row_m, row_s, col_m, col_s, diag, term);
+    hipLaunchKernelGGL(itc_global_loss_kernel, dim3(1), dim3(256), 0, s, term, G, a.loss);
+    return hipGetLastError();
+}
+hipError_t launch_itc_global_bwd(const ItcGlobalBwdArgs& a, hipStream_t s) {
+    if (!itc_global_shape_ok(a.G, a.E) || a.Bl < 1 || a.r0 < 0 || (long)a.r0 + a.Bl > a.G) return hipErrorInvalidValue;
+    if (!a.txt_n || !a.img_n || !a.logit_scale || !a.rowlse || !a.collse || !a.d_txt_n || !a.d_img_n || !a.ws) return hipErrorInvalidValue;
+    if ((a.dtxt_e && !a.txt_inv) || (a.dimg_e && !a.img_inv)) return hipErrorInvalidValue;
+    const int G = a.G, E = a.E, Bl = a.Bl, nt = (G + 31) / 32, nbl = (Bl + 31) / 32;
+    float *grow = a.ws + itc_global_fwd_words(G), *gcol = grow + (size_t)Bl * G, *dls_part = gcol + (size_t)Bl * G;
+    hipLaunchKernelGGL(itc_global_grad_kernel, dim3(nt, nbl, 2), dim3(IG_THREADS), 0, s, a, grow, gcol, dls_part);
+    // d T_n[local] = grow . I_n, d I_n[local] = gcol . T_n: [Bl, G] x [G, E], exact fp32
+    SmallGemmArgs g{};
+    g.A = grow; g.lda = G; g.W = a.img_n; g.ldw = E; g.out = a.d_txt_n; g.ldo = E; g.M = Bl; g.N = E; g.K = G;
+    hipError_t r = launch_small_nn(g, s);
+    if (r != hipSuccess) return r;
+    g.A = gcol; g.W = a.txt_n; g.out = a.d_img_n;
+    r = launch_small_nn(g, s);
+    if (r != hipSuccess) return r;
+    hipLaunchKernelGGL(itc_global_normbwd_kernel, dim3(2 * Bl), dim3(256), 0, s, a, dls_part, nbl * nt);
     return hipGetLastError();
 }
 hipError_t launch_loss(const LossArgs& a, hipStream_t s) {

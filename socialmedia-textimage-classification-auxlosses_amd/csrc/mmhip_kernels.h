@@ -265,10 +265,36 @@ struct ItcBwdArgs {
 };
 hipError_t launch_itc_fwd(const ItcArgs& a, hipStream_t s);
 hipError_t launch_itc_bwd(const ItcBwdArgs& a, hipStream_t s);
+// Global-batch ITC (data parallelism, heads.hip): G = world * B posts whose normalised rows were gathered in rank order.  Deterministic by
+// construction (ordered partials, one writer per word).  ws: itc_global_ws_floats(G, Bl) floats, shared by the forward and its backward.
+static constexpr int ITC_GLOBAL_MAX_G = 8192;
+struct ItcGlobalArgs {
+    const float* txt_n; const float* img_n;   // [G, E] gathered
+    const float* logit_scale;
+    float* logits;                            // [G, G] logits_per_text of the gathered batch, or null (the engine never stores it)
+    float* rowlse; float* collse;             // [G] log-sum-exp of every row / column (saved for the backward)
+    float* loss;                              // [1] clip_loss of the G x G logits
+    float* ws;
+    int G, E;
+};
+struct ItcGlobalBwdArgs {
+    const float* txt_n; const float* img_n; const float* logit_scale; const float* rowlse; const float* collse;
+    const float* txt_inv; const float* img_inv;   // [Bl] 1 / |e| of the local rows (needed for dtxt_e / dimg_e)
+    float* d_txt_n; float* d_img_n;               // [Bl, E] gradient of the local normalised rows [r0, r0 + Bl)
+    float* dtxt_e; float* dimg_e;                 // [Bl, E] the same through the normalisation, or null
+    float* dlogit_scale;                          // accumulated (may be null): sum of dS * S over the local text rows' strip
+    float* ws;
+    int G, E, Bl, r0;
+    float scale;                                  // dS = scale * (softmax_row + softmax_col - 2 I): w_itc * world / (2 G) under a 1 / world gradient average
+};
+size_t itc_global_ws_floats(int G, int Bl);
+hipError_t launch_itc_global_fwd(const ItcGlobalArgs& a, hipStream_t s);
+hipError_t launch_itc_global_bwd(const ItcGlobalBwdArgs& a, hipStream_t s);
 
 struct LossArgs {
     const float* out_cls; const int64_t* onehot; const float* class_w;   // [B,C], [B,C], [C] or null
     const float* logits_per_text;                                        // [B,B] or null
+    const float* itc_global_loss;                                        // [1] with logits_per_text null: the ITC term computed elsewhere (global-batch ITC)
     const float* out_tim; const int64_t* lbl_tim;                        // [B,2], [B] or null
     float w_cls, w_itc, w_itm;
     float* loss;            // [4]: total, cls, itc, itm

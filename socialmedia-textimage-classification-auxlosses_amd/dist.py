@@ -1,6 +1,7 @@
 """Data parallelism for the late-fusion step: one process per GPU (torchrun), torch.distributed backend "nccl" (= RCCL
 over xGMI on ROCm); "gloo" on CPU for the tests.  The reference has no distributed layer: semantics are
-"the reference run per rank on its own B posts (ITC / ITM stay rank-local), gradients averaged".
+"the reference run per rank on its own B posts (ITC / ITM stay rank-local), gradients averaged"; with itc_global (opt-in, gather_itc below) the
+ITC term is the reference's clip_loss on the concatenated batch of all ranks instead.
 
 Exchange plan:
   * dense all-reduce (sum; AdamW multiplies by 1/world) of each backward stage's parameter range, launched right after
@@ -175,6 +176,29 @@ def sparse_rows_exchange_finish(state, table_grad, row_state=None):
 def sparse_rows_exchange(table_grad, ids, row_state=None):
     """begin + finish in one call"""
     sparse_rows_exchange_finish(sparse_rows_exchange_begin(table_grad, ids), table_grad, row_state)
+
+
+def gather_itc(txt_local, img_local, txt_all, img_all):
+    """global-batch ITC: this rank's normalised rows txt_local / img_local [B, E] into txt_all / img_all [W * B, E] of every rank, rank r's rows
+    at [r * B, (r + 1) * B) -- one all-gather per modality, issued like the gradient collectives (ordered after the kernels already enqueued on
+    the current stream).  RCCL: all_gather_into_tensor, and Work.wait() is a stream-side wait; other backends (gloo): the list form into views
+    of the output and the same host wait the stage exchange uses.  Every rank must bring the same B."""
+    W = world_size()
+    if tuple(txt_all.shape) != (W * txt_local.shape[0], txt_local.shape[1]) or tuple(img_all.shape) != (W * img_local.shape[0], img_local.shape[1]):
+        raise ValueError(f"gather_itc: [{W} * B, E] outputs expected, got {tuple(txt_all.shape)} / {tuple(img_all.shape)} for {tuple(txt_local.shape)} / {tuple(img_local.shape)}")
+    if not (td.is_available() and td.is_initialized()):
+        txt_all.copy_(txt_local)
+        img_all.copy_(img_local)
+        return
+    works = []
+    for loc, all_ in ((txt_local, txt_all), (img_local, img_all)):
+        if td.get_backend() == "nccl":
+            works.append(td.all_gather_into_tensor(all_, loc, async_op=True))
+        else:
+            B = loc.shape[0]
+            works.append(td.all_gather([all_[r * B: (r + 1) * B] for r in range(W)], loc, async_op=True))
+    for w in works:
+        w.wait()
 
 
 BUCKET_BYTES = int(os.environ.get("MMHIP_BUCKET_MB", "48")) << 20

@@ -115,14 +115,17 @@ class MM_Model(nn.Module):
     MM_Model(num_labels, txt_model_name, img_model_name, dropout, fusion_name='concat'); keyword-only extras are
     additive: `arch` overrides (layer counts, vocab ... for tests), `dtype` ('bf16' | 'f16' | 'bf16x3' = strict-parity mode; with it
     `backward_products` = 3 | 2 | 1 bf16 MFMA products in the backward's matrix products, the forward always three), `max_posts` /
-    `max_text_len` (capacity the workspace is sized for), `device`, `seed`.
+    `max_text_len` (capacity the workspace is sized for), `device`, `seed`; `itc_global` (data parallelism only: the training step's ITC term
+    is clip_loss over the gathered embeddings of ALL ranks' posts -- include/mmhip.h mmhip_set_itc_global; every rank must then hold the same
+    number of posts per step; a no-op at world size 1; forward()'s logits_per_text and the autograd path stay the rank's own [B, B] block).
     Weights: loaded from the local directories of config.MODEL_DIR_DICT when they exist (HF layout), else random
     init at the architecture's true shapes (no network in this environment).
     """
 
     def __init__(self, num_labels, txt_model_name, img_model_name, dropout, fusion_name="concat", *, arch=None,
-                 dtype="bf16", max_posts=64, max_text_len=128, device=None, seed=0, backward_products=None):
+                 dtype="bf16", max_posts=64, max_text_len=128, device=None, seed=0, backward_products=None, itc_global=False):
         super().__init__()
+        self.itc_global = bool(itc_global)
         if not torch.cuda.is_available():
             raise _lib.MMHipError("MM_Model needs an MI355X (gfx950) GPU: the HIP path has no CPU fallback")
         if fusion_name not in ("concat", "attention"):
@@ -224,11 +227,18 @@ class MM_Model(nn.Module):
             _lib.check(lib.mmhip_set_backward_products(h, self.backward_products), "set_backward_products")
         self._ws = None
         torch.cuda.empty_cache()
+        # global-batch ITC: the gathered [world * max_posts, proj_dim] rows live in the workspace (reserved before it is sized; nothing at world 1)
+        itc_world = mmdist.world_size() if self.itc_global else 1
+        if itc_world > 1:
+            _lib.check(lib.mmhip_reserve_itc_global(h, itc_world), "reserve_itc_global")
         self._ws = torch.empty(lib.mmhip_workspace_bytes(h), dtype=torch.uint8, device=dev)
         if os.environ.get("MMHIP_POISON_WS"):       # debugging aid: no kernel may read workspace it has not written
             self._ws.fill_(int(os.environ["MMHIP_POISON_WS"], 0))
         _lib.check(lib.mmhip_bind(h, _lib.ptr(self._flat_frozen), _lib.ptr(self._flat_train), _lib.ptr(self._flat_grad),
                                   _lib.ptr(self._ws), self._ws.numel()), "bind")
+        self.itc_global_active = itc_world > 1
+        if itc_world > 1:
+            _lib.check(lib.mmhip_set_itc_global(h, itc_world, mmdist.rank()), "set_itc_global")
         self._stage_ranges = []
         b, e = C.c_uint64(), C.c_uint64()
         for st in range(lib.mmhip_num_backward_stages(h)):
@@ -377,6 +387,15 @@ class MM_Model(nn.Module):
             vc["misses"] += B
         return out_cls, lpt, out_tim, feats
 
+    def _gather_itc(self):
+        """global-batch ITC, between the training forward and the loss: every rank's normalised text / image rows of this step into the engine's
+        gather buffers (include/mmhip.h mmhip_itc_gather_buffers), ordered before what the current stream runs next"""
+        p = [C.c_void_p() for _ in range(4)]
+        _lib.check(_lib.lib().mmhip_itc_gather_buffers(self._handle, *[C.byref(x) for x in p]), "itc_gather_buffers")
+        B, E, W, base = self._last["B"], self.arch["proj_dim"], mmdist.world_size(), self._ws.data_ptr()
+        view = lambda x, rows: self._ws[x.value - base: x.value - base + rows * E * 4].view(torch.float32).view(rows, E)
+        mmdist.gather_itc(view(p[0], B), view(p[1], B), view(p[2], W * B), view(p[3], W * B))
+
     def active_groups(self, use_itc, use_itm):
         g = {_lib.G_ALWAYS}
         if self.fusion_name == "attention":
@@ -463,6 +482,7 @@ class MMLate_Model(object):
         self.max_length = config.max_length
         model_kw.setdefault("max_posts", config.batch_size)
         model_kw.setdefault("max_text_len", config.max_length)
+        model_kw["itc_global"] = bool(model_kw.get("itc_global", False)) and mmdist.world_size() > 1      # inert in a single process
         self.model = MM_Model(self.num_labels, txt_model_name, img_model_name, config.dropout, fusion_name=fusion_name, **model_kw)
         self.device = self.model.device_
         self._opt = None
@@ -543,6 +563,8 @@ class MMLate_Model(object):
             # this process starts / finishes the collectives (dist.py) at the points the staged loop below would
             return self._native_step(ids, mask, pixel_values, tim_ids, tim_mask, lbl_tim, onehot, cw, lr, weight_decay, step, loss, ncorr, exchange=True)
         m._engine_forward(ids, mask, pixel_values, tim_ids, tim_mask, vision_keys=vision_keys)
+        if m.itc_global_active and w_itc != 0.0:
+            m._gather_itc()                                    # the staged form of MMHIP_CB_GATHER_ITC
         _lib.check(lib.mmhip_loss(m._handle, _lib.ptr(onehot), _lib.ptr(cw), _lib.ptr(lbl_tim), w_cls, w_itc, w_itm, _lib.ptr(loss),
                                   _lib.ptr(ncorr), s), "loss")
         _lib.check(lib.mmhip_backward_begin(m._handle, None, None, None, None, s), "backward_begin")
@@ -675,6 +697,8 @@ class MMLate_Model(object):
                     elif st == _lib.CB_FINISH_ROWS:
                         for f in finishers:
                             f()
+                    elif st == _lib.CB_GATHER_ITC:
+                        m._gather_itc()
                     return 0
                 except BaseException as exc:              # a Python exception must not unwind through the C frames
                     failure.append(exc)

@@ -1,6 +1,6 @@
 """Command line of the late-fusion runs -- same flags, defaults, file names and CSV layouts as the reference's
 models/run_mm_late.py:20-191.  Additive flags: --batch_size, --synthetic/--n_synthetic (no dataset on disk),
---dtype, --results_dir, --cpu_preprocess, --num_workers, --cache_vision.  Data parallel: launch with `python -m torch.distributed.run --nproc-per-node N ...`.
+--dtype, --results_dir, --cpu_preprocess, --num_workers, --cache_vision, --itc_global.  Data parallel: launch with `python -m torch.distributed.run --nproc-per-node N ...`.
 
     python -m smtc_amd.run_mm_late --txt_model_name bernice --img_model_name vit --fusion_name attention --task 2 --testing
 """
@@ -67,6 +67,9 @@ def build_parser():
     p.add_argument("--item_tokenize", action="store_true", help="tokenise per item like the reference instead of once per batch in the collate")
     p.add_argument("--cache_vision", type=int, default=0, metavar="POSTS",
                    help="keep the frozen image tower's outputs of up to POSTS posts in HBM (306 KB each): epochs after the first skip the tower")
+    p.add_argument("--itc_global", action="store_true",
+                   help="data parallel: contrast every post against the gathered embeddings of ALL ranks' posts (the single-process objective on the "
+                        "concatenated batch) instead of the rank's own batch; no effect in a single process")
     return p
 
 
@@ -117,7 +120,7 @@ def main(argv=None):
         args.txt_model_name, args.img_model_name, args.task, args.fusion_name, args.testing, args.use_clip_loss, args.use_tim_loss,
         args.beta_itc, args.beta_itm, args.nsamples, args.seed))
     cfg = Config(args)
-    kw = dict(dtype=args.dtype, seed=args.seed)
+    kw = dict(dtype=args.dtype, seed=args.seed, itc_global=args.itc_global)
     if args.arch_layers:
         kw["arch"] = dict(layers_txt=args.arch_layers, layers_img=args.arch_layers)
     trainer = MMLate_Model(cfg, args.txt_model_name, args.img_model_name, args.fusion_name, multilabel=cfg.multilabel, **kw)
