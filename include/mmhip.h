@@ -490,6 +490,59 @@ int mmhip_early_train_step(mmhip_early_handle h, const int64_t* ids, const int64
                            float eps, float weight_decay, int step, float grad_scale, float* loss, void* stream, mmhip_exchange_cb on_stage, void* user);
 
 const char* mmhip_version(void);
+/* ==== text-only handle: the reference's text-only trainer (models/text_only.py BERT / BERNICE, models/run_txt.py) ==========================
+ * The text tower of the late-fusion engine -- the same kernels and launch sequences, all three dtypes, MMHIP_DETERMINISTIC, MMHIP_CLS_ONLY -- under a
+ * fused CLS classifier head (csrc/heads.hip: one launch per direction), without the image tower, pooler / projections, ITC, ITM and the fusion
+ * head; none of their workspace is carved.  One flat fp32 parameter buffer (no frozen one), its gradient, caller-owned moments.
+ * Parameter names are the reference modules' state-dict keys (transformers 4.25.1): bert_model.embeddings.*, bert_model.encoder.layer.N.*,
+ * bert_model.pooler.dense.* (MMHIP_G_NEVER: the reference classifies last_hidden[:, 0, :], its pooler output is never consumed -- never computed
+ * here, no gradient, skipped by AdamW as torch skips `grad is None`), linear.weight, linear.bias.  The position_ids buffer has no storage here.
+ * A text-only handle is an mmhip_handle: the per-handle setters above that do not name the image tower or ITC -- row state, guard, index counter,
+ * loss scale, backward products, side stream, step spans, GEMM timing -- take it; every other late-fusion call answers MMHIP_E_STATE / _INVALID. */
+typedef struct mmhip_txt_config {
+    int hidden, heads, inter, layers;    /* 768, 12, 3072, 12 */
+    int vocab, max_pos, type_vocab;      /* type_vocab 1 (XLM-R / RoBERTa-shaped) or 2 (BERT) */
+    int txt_kind, pad_id;                /* MMHIP_TXT_* */
+    float ln_eps;
+    int num_labels;                      /* <= 16 */
+    float p_hidden, p_attn, p_head;      /* tower dropouts, --dropout of the classifier */
+    int dtype;                           /* MMHIP_BF16 | MMHIP_F16 | MMHIP_BF16X3 */
+    int max_posts, max_text_len;         /* capacity; max_text_len <= 128 */
+    float loss_scale;                    /* as mmhip_config.loss_scale */
+} mmhip_txt_config;
+typedef mmhip_handle mmhip_txt_handle;
+
+int mmhip_txt_create(const mmhip_txt_config* cfg, mmhip_txt_handle* out);
+void mmhip_txt_destroy(mmhip_txt_handle h);
+int mmhip_txt_param_count(mmhip_txt_handle h);
+int mmhip_txt_param_info_at(mmhip_txt_handle h, int index, mmhip_param_info* out);     /* buffer is always 1 */
+uint64_t mmhip_txt_numel(mmhip_txt_handle h);                                          /* fp32 elements of the flat parameter buffer */
+uint64_t mmhip_txt_workspace_bytes(mmhip_txt_handle h);
+int mmhip_txt_bind(mmhip_txt_handle h, float* params, float* grad, void* workspace, uint64_t workspace_bytes);
+int mmhip_txt_refresh_weights(mmhip_txt_handle h, void* stream);
+/* BERT.forward / BERNICE.forward (models/text_only.py:34-39, 48-53): ids / mask / type_ids int64 [B,T] (type_ids NULL: all zero; ignored by a
+ * one-row type table), logits fp32 [B,num_labels] = linear(dropout(last_hidden[:, 0, :])).  Ids are clamped into their tables as in the late-fusion forward. */
+int mmhip_txt_forward(mmhip_txt_handle h, const int64_t* ids, const int64_t* mask, const int64_t* type_ids, int B, int T, int train, uint64_t seed,
+                      float* logits, void* stream);
+/* nn.CrossEntropyLoss(weight) on float one-hot targets of the last forward's logits (run_txt.py: batch mean of -sum_c w_c y_c log p_c): loss [1],
+ * n_correct [1] (either may be NULL); the gradient of the logits stays in the handle for the backward call with d_logits == NULL */
+int mmhip_txt_loss(mmhip_txt_handle h, const int64_t* onehot, const float* class_w, float* loss, int* n_correct, void* stream);
+/* loss.backward(): d_logits fp32 [B,num_labels], or NULL after the loss call.  Gradients are ADDED into `grad` (zero on entry, as for the late-fusion backward). */
+int mmhip_txt_backward(mmhip_txt_handle h, const float* d_logits, void* stream);
+/* one fused step of TextModel.train (models/text_only.py:138-164): forward (train mode) with the loss in the head's launch -> backward -> per-layer
+ * AdamW + operand refresh on the side stream beside the stages below -> remaining dense ranges -> row-lazy word table.  Single process. */
+int mmhip_txt_train_step(mmhip_txt_handle h, const int64_t* ids, const int64_t* mask, const int64_t* type_ids, const int64_t* onehot, const float* class_w,
+                         int B, int T, uint64_t seed, float* adam_m, float* adam_v, float lr, float beta1, float beta2, float eps, float weight_decay,
+                         int step, float* loss, int* n_correct, void* stream);
+/* the head's two launches alone (operator tests).  x: CLS rows, row b at element b * x_stride, x_dtype MMHIP_BF16 | _F16 | _F32 | _PAIR (pair rows count
+ * 4-byte elements); dropout p with the engine's hash (stream 2, element b * H + c).  Limits: C <= 16, H % 64 == 0, H <= 1024.
+ * fwd: logits [B,C]; with onehot also loss [1], n_correct [1], d_logits [B,C] (each optional).  bwd: dW [C,H], db [C] (accumulate != 0: added),
+ * dx rows b * dx_stride = dropout'(d_logits W) * dx_scale as dx_dtype (16-bit or fp32); no atomics, the same bits on every call. */
+int mmhip_op_cls_head_fwd(int x_dtype, const void* x, uint64_t x_stride, const float* W, const float* bias, int B, int C, int H, float p, uint64_t seed,
+                          float* logits, const int64_t* onehot, const float* class_w, float* loss, int32_t* n_correct, float* d_logits, void* stream);
+int mmhip_op_cls_head_bwd(int x_dtype, const void* x, uint64_t x_stride, const float* W, const float* d_logits, int B, int C, int H, float p, uint64_t seed,
+                          float* dW, float* db, int dx_dtype, void* dx, uint64_t dx_stride, float dx_scale, int accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

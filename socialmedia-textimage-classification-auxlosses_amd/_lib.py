@@ -31,6 +31,13 @@ class EarlyConfig(C.Structure):      # include/mmhip.h: mmhip_early_config
                 ("p_head", C.c_float), ("ln_eps", C.c_float)]
 
 
+class TxtConfig(C.Structure):        # include/mmhip.h: mmhip_txt_config
+    _fields_ = [("hidden", C.c_int), ("heads", C.c_int), ("inter", C.c_int), ("layers", C.c_int), ("vocab", C.c_int), ("max_pos", C.c_int),
+                ("type_vocab", C.c_int), ("txt_kind", C.c_int), ("pad_id", C.c_int), ("ln_eps", C.c_float), ("num_labels", C.c_int),
+                ("p_hidden", C.c_float), ("p_attn", C.c_float), ("p_head", C.c_float), ("dtype", C.c_int), ("max_posts", C.c_int),
+                ("max_text_len", C.c_int), ("loss_scale", C.c_float)]
+
+
 class ParamInfo(C.Structure):
     _fields_ = [("name", C.c_char * 192), ("ndim", C.c_int), ("dims", C.c_int64 * 4), ("buffer", C.c_int), ("group", C.c_int),
                 ("offset", C.c_uint64), ("numel", C.c_uint64)]
@@ -142,6 +149,20 @@ _SIGS = {
     "mmhip_early_num_stages": (I, [P]),
     "mmhip_early_stage_grad_range": (I, [P, I, C.POINTER(U64), C.POINTER(U64)]),
     "mmhip_early_train_step": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, U64, I, I, F, F, F, P, P, F, F, F, F, F, I, F, P, P, P, P]),
+    "mmhip_txt_create": (I, [C.POINTER(TxtConfig), C.POINTER(P)]),
+    "mmhip_txt_destroy": (None, [P]),
+    "mmhip_txt_param_count": (I, [P]),
+    "mmhip_txt_param_info_at": (I, [P, I, C.POINTER(ParamInfo)]),
+    "mmhip_txt_numel": (U64, [P]),
+    "mmhip_txt_workspace_bytes": (U64, [P]),
+    "mmhip_txt_bind": (I, [P, P, P, P, U64]),
+    "mmhip_txt_refresh_weights": (I, [P, P]),
+    "mmhip_txt_forward": (I, [P, P, P, P, I, I, I, U64, P, P]),
+    "mmhip_txt_loss": (I, [P, P, P, P, P, P]),
+    "mmhip_txt_backward": (I, [P, P, P]),
+    "mmhip_txt_train_step": (I, [P, P, P, P, P, P, I, I, U64, P, P, F, F, F, F, F, I, P, P, P]),
+    "mmhip_op_cls_head_fwd": (I, [I, P, U64, P, P, I, I, I, F, U64, P, P, P, P, P, P, P]),
+    "mmhip_op_cls_head_bwd": (I, [I, P, U64, P, P, I, I, I, F, U64, P, P, I, P, U64, F, I, P]),
     "mmhip_version": (C.c_char_p, []),
 }
 EXPORTS = tuple(_SIGS)

@@ -24,6 +24,7 @@ CLASSES = {2: ["image adds and text is represented", "image adds and text is not
 metric_names = ["f1_weighted", "f1_macro", "precision_weighted", "precision_macro", "recall_weighted", "recall_macro", "loss"]
 RES_PATH = "../results/"
 results_dir_mm_late = RES_PATH + "mm_late/"
+results_dir_txt = RES_PATH + "txt_only/"
 MODEL_DIR_DICT = {"bert": "../../../BERT-base/", "bertweet": "../../../BERTWEET-base/", "roberta": "../../../RoBERTa-base/",
                   "bernice": "../../../BERNICE/", "vit": "../../../ViT/", "beit": "../../../BEiT/", "deit": "../../../DEiT/",
                   "clip": "../../../CLIP-ViT-L-14/", "clip336": "../../../CLIP-ViT-L-14-336/",

@@ -381,4 +381,22 @@ int mmhip_op_itc_global_bwd(const float* txt_n, const float* img_n, const float*
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------ fused CLS classifier head (text-only model)
+int mmhip_op_cls_head_fwd(int x_dtype, const void* x, uint64_t x_stride, const float* W, const float* bias, int B, int C, int H, float p, uint64_t seed,
+                          float* logits, const int64_t* onehot, const float* class_w, float* loss, int32_t* n_correct, float* d_logits, void* stream) {
+    if (!x || !W || !bias || !logits || !(p >= 0.f) || p >= 1.f) return MMHIP_E_INVALID;
+    ClsHeadArgs a = cls_head(x, (size_t)x_stride, x_dtype, W, B, C, H, make_drop(p, seed, STREAM_HEAD));
+    a.bias = bias; a.logits = logits; a.onehot = onehot; a.class_w = class_w; a.loss = loss; a.n_correct = n_correct; a.d_logits_out = d_logits;
+    const hipError_t r = launch_cls_head_fwd(a, (hipStream_t)stream);
+    return r == hipErrorInvalidValue ? MMHIP_E_INVALID : (int)r;
+}
+int mmhip_op_cls_head_bwd(int x_dtype, const void* x, uint64_t x_stride, const float* W, const float* d_logits, int B, int C, int H, float p, uint64_t seed,
+                          float* dW, float* db, int dx_dtype, void* dx, uint64_t dx_stride, float dx_scale, int accumulate, void* stream) {
+    if (!x || !W || !d_logits || !(p >= 0.f) || p >= 1.f) return MMHIP_E_INVALID;
+    ClsHeadArgs a = cls_head(x, (size_t)x_stride, x_dtype, W, B, C, H, make_drop(p, seed, STREAM_HEAD));
+    a.d_logits = d_logits; a.dW = dW; a.db = db; a.dx = dx; a.dx_stride = (size_t)dx_stride; a.dx_dtype = dx_dtype; a.dx_scale = dx_scale; a.accumulate = accumulate;
+    const hipError_t r = launch_cls_head_bwd(a, (hipStream_t)stream);
+    return r == hipErrorInvalidValue ? MMHIP_E_INVALID : (int)r;
+}
+
 }  // extern "C"

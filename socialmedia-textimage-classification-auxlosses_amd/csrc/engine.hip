@@ -88,6 +88,12 @@ struct mmhip_engine {
     hipEvent_t ev_fork = nullptr, ev_vit = nullptr, ev_ready[2] = {nullptr, nullptr}, ev_tn[2] = {nullptr, nullptr};
     hipEvent_t ev_layer[2] = {nullptr, nullptr}, ev_opt = nullptr;      // mmhip_train_step: per-layer AdamW on the side stream
     bool tn_pending[2] = {false, false};
+    // text-only handle (mmhip_txt_create): the text tower and the fused CLS classifier head alone -- no image tower, pooler, ITC / ITM or fusion head,
+    // none of their workspace; parameters under the reference's text_only.py keys (bert_model.*, linear.*)
+    bool txt_only = false;
+    std::string tm_prefix = "dual_encoder.text_model.";      // state-dict prefix of the text tower
+    size_t lin_w = 0, lin_b = 0;                             // text-only classifier
+    size_t tt_all = 0; bool has_tt = false;                  // the engine's clamped copy of the token type ids; the last forward was given some
     int cls_only = -1;         // -1 = read MMHIP_CLS_ONLY on first use; 1: the last text layer runs its post-attention part on CLS rows only
     bool cls_compact = false;  // state of the last forward
     int overlap = -1;          // -1 = read MMHIP_OVERLAP on first use
@@ -134,9 +140,9 @@ struct mmhip_engine {
 namespace {
 
 // ------------------------------------------------------------------------------------------------ layout
-void add_text_layer(ParamTable& b, const mmhip_config& c, int l, LayerOff& o) {
+void add_text_layer(ParamTable& b, const mmhip_config& c, const std::string& tm, int l, LayerOff& o) {
     const int H = c.hidden, I = c.inter;
-    const std::string p = "dual_encoder.text_model.encoder.layer." + std::to_string(l) + ".";
+    const std::string p = tm + "encoder.layer." + std::to_string(l) + ".";
     const int g = MMHIP_G_ALWAYS;
     o.begin = b.off[1];
     o.qkv_w = b.add(p + "attention.self.query.weight", 1, g, {H, H});
@@ -205,6 +211,22 @@ void add_vit_layer(ParamTable& b, const mmhip_config& c, int l, LayerOff& o) {
     o.end = b.off[0];
 }
 
+// text layers last -> first, then the embeddings: the tail of the trainable buffer in both layouts (the word table closes it)
+void add_text_layers_and_embeddings(mmhip_engine& e, ParamTable& b) {
+    const mmhip_config& c = e.cfg;
+    const int H = c.hidden;
+    e.txt.resize(c.layers_txt);
+    for (int l = c.layers_txt - 1; l >= 0; --l) add_text_layer(b, c, e.tm_prefix, l, e.txt[l]);
+    const std::string tm = e.tm_prefix + "embeddings.";
+    e.emb_begin = b.off[1];
+    e.t_eln_w = b.add(tm + "LayerNorm.weight", 1, MMHIP_G_ALWAYS, {H});
+    e.t_eln_b = b.add(tm + "LayerNorm.bias", 1, MMHIP_G_ALWAYS, {H});
+    e.t_type = b.add(tm + "token_type_embeddings.weight", 1, MMHIP_G_ALWAYS, {c.type_vocab, H});
+    e.t_pos = b.add(tm + "position_embeddings.weight", 1, MMHIP_G_ALWAYS, {c.max_pos, H});
+    e.t_word = b.add(tm + "word_embeddings.weight", 1, MMHIP_G_ALWAYS, {c.vocab, H});
+    e.emb_end = b.off[1];
+}
+
 void build_layout(mmhip_engine& e) {
     const mmhip_config& c = e.cfg;
     const int H = c.hidden, C = c.num_labels, E = c.proj_dim, P = e.P(), Hv = e.Hv();
@@ -263,25 +285,36 @@ void build_layout(mmhip_engine& e) {
     e.cls_w = b.add("linear_cls.weight", 1, MMHIP_G_ALWAYS, {C, H});
     e.cls_b = b.add("linear_cls.bias", 1, MMHIP_G_ALWAYS, {C});
     e.heads_end = b.off[1];
-    e.txt.resize(c.layers_txt);
-    for (int l = c.layers_txt - 1; l >= 0; --l) add_text_layer(b, c, l, e.txt[l]);
-    const std::string tm = "dual_encoder.text_model.embeddings.";
-    e.emb_begin = b.off[1];
-    e.t_eln_w = b.add(tm + "LayerNorm.weight", 1, MMHIP_G_ALWAYS, {H});
-    e.t_eln_b = b.add(tm + "LayerNorm.bias", 1, MMHIP_G_ALWAYS, {H});
-    e.t_type = b.add(tm + "token_type_embeddings.weight", 1, MMHIP_G_ALWAYS, {c.type_vocab, H});
-    e.t_pos = b.add(tm + "position_embeddings.weight", 1, MMHIP_G_ALWAYS, {c.max_pos, H});
-    e.t_word = b.add(tm + "word_embeddings.weight", 1, MMHIP_G_ALWAYS, {c.vocab, H});
-    e.emb_end = b.off[1];
+    add_text_layers_and_embeddings(e, b);
     e.n_frozen = b.off[0];
     e.n_train = b.off[1];
 }
+
+// the reference's text_only.py modules (BERT / BERNICE): bert_model.* + linear.*.  They classify last_hidden[:, 0, :]; the pooler is computed there
+// and never consumed, so its parameters exist (checkpoint keys), sit in MMHIP_G_NEVER, get no gradient and no optimizer step.
+// Order: [never: pooler | always: classifier, layers last -> first, embeddings]
+void build_layout_txt(mmhip_engine& e) {
+    const mmhip_config& c = e.cfg;
+    const int H = c.hidden, C = c.num_labels;
+    ParamTable b{e.params};
+    e.t_pool_w = b.add(e.tm_prefix + "pooler.dense.weight", 1, MMHIP_G_NEVER, {H, H});
+    e.t_pool_b = b.add(e.tm_prefix + "pooler.dense.bias", 1, MMHIP_G_NEVER, {H});
+    e.heads_begin = b.off[1];
+    e.lin_w = b.add("linear.weight", 1, MMHIP_G_ALWAYS, {C, H});
+    e.lin_b = b.add("linear.bias", 1, MMHIP_G_ALWAYS, {C});
+    e.heads_end = b.off[1];
+    add_text_layers_and_embeddings(e, b);
+    e.n_frozen = 0;
+    e.n_train = b.off[1];
+}
+
 
 void build_workspace(mmhip_engine& e) {
     const mmhip_config& c = e.cfg;
     const size_t H = c.hidden, I = c.inter, E = c.proj_dim, C = c.num_labels;
     const size_t Bm = c.max_posts, Tm = c.max_text_len, P = e.P(), Hv = e.Hv(), Iv = e.Iv(), Kpp = e.Kpp();
-    const size_t Mt = 2 * Bm * Tm, Mv = Bm * P, Bt = 2 * Bm;
+    const bool mm = !e.txt_only;      // a text-only handle carves the text tower's share alone, for B (not 2 B: no ITM posts) rows of posts
+    const size_t Bt = (mm ? 2 : 1) * Bm, Mt = Bt * Tm, Mv = Bm * P;
     const size_t Z = e.esz();      // bytes per activation / GEMM-operand element: 2 (bf16, f16) or 4 (bf16x3 parity mode)
     Carver w;
     auto w16 = [&](std::vector<LayerW16>& v, int n, bool transposed, size_t H, size_t I) {
@@ -291,9 +324,10 @@ void build_workspace(mmhip_engine& e) {
             if (transposed) { L.qkvT = w.take(3 * H * H * Z); L.aoT = w.take(H * H * Z); L.fc1T = w.take(I * H * Z); L.fc2T = w.take(H * I * Z); }
         }
     };
-    w16(e.vit_w16, c.layers_img, false, Hv, Iv);
+    w16(e.vit_w16, mm ? c.layers_img : 0, false, Hv, Iv);
     w16(e.txt_w16, c.layers_txt, true, H, I);
-    e.patch_w16 = w.take(Hv * Kpp * Z);
+    if (mm) e.patch_w16 = w.take(Hv * Kpp * Z);
+    else e.tt_all = w.take(Bt * Tm * 8);
     e.ids_all = w.take(Bt * Tm * 8); e.mask_all = w.take(Bt * Tm * 8); e.pos_ids = w.take(Bt * Tm * 4); e.maskbias = w.take(Bt * Tm * 4);
     e.x0 = w.take(Mt * H * Z); e.xhat_emb = w.take(Mt * H * Z); e.rstd_emb = w.take(Mt * 4);
     if (e.px) e.x0p = w.take(Mt * H * Z);
@@ -306,9 +340,11 @@ void build_workspace(mmhip_engine& e) {
         a.mean1 = w.take(Mt * 4); a.rstd1 = w.take(Mt * 4); a.mean2 = w.take(Mt * 4); a.rstd2 = w.take(Mt * 4);
         a.lse = w.take(Bt * c.heads * Tm * 4);
     }
-    e.v_patches = w.take(Bm * (P - 1) * Kpp * Z); e.v_pe = w.take(Bm * (P - 1) * Hv * Z);
-    e.v_x = w.take(Mv * Hv * Z); e.v_ln = w.take(Mv * Hv * Z); e.v_qkv = w.take(Mv * 3 * Hv * Z); e.v_ctx = w.take(Mv * Hv * Z);
-    e.v_h = w.take(Mv * Iv * Z); e.v_out = w.take(Mv * Hv * Z);
+    if (mm) {
+        e.v_patches = w.take(Bm * (P - 1) * Kpp * Z); e.v_pe = w.take(Bm * (P - 1) * Hv * Z);
+        e.v_x = w.take(Mv * Hv * Z); e.v_ln = w.take(Mv * Hv * Z); e.v_qkv = w.take(Mv * 3 * Hv * Z); e.v_ctx = w.take(Mv * Hv * Z);
+        e.v_h = w.take(Mv * Iv * Z); e.v_out = w.take(Mv * Hv * Z);
+    }
     e.g_dx = w.take(Mt * H * Z); e.g_dx2 = w.take(Mt * H * Z); e.g_dpre = w.take(Mt * H * Z); e.g_ddrop = w.take(Mt * H * Z); e.g_dpre1 = w.take(Mt * H * Z); e.g_ddrop1 = w.take(Mt * H * Z);
     e.g_dqkv = w.take(Mt * 3 * H * Z); e.g_dctx = w.take(Mt * H * Z); e.g_du = w.take(Mt * I * Z);
     e.g_det_rows = w.take(Mt * H * 4);       // per-slot embedding gradient rows of the deterministic mode (MMHIP_DETERMINISTIC=1)
@@ -317,7 +353,8 @@ void build_workspace(mmhip_engine& e) {
     e.g_set[1][3] = w.take(Mt * H * Z); e.g_set[1][4] = w.take(Mt * H * Z); e.g_set[1][5] = w.take(Mt * 3 * H * Z);
     {
         size_t pf = partial_floats_rows((int)Mt, (int)H, 3), pc = partial_floats_colsum((int)Mt, (int)(3 * H > I ? 3 * H : I));
-        const size_t pe = partial_floats_embed((int)Bt, (int)Tm, (int)H);
+        // (a two-row token type table -- text-only BERT -- reduces a fourth vector: EmbedBwdArgs::type_rows)
+        const size_t pe = partial_floats_embed((int)Bt, (int)Tm, (int)H) / 3 * (!mm && c.type_vocab > 1 ? 4 : 3);
         if (pe > pf) pf = pe;
         e.g_partial = w.take((pf > pc ? pf : pc) * 4);
         e.g_partial_side = w.take((pf > pc ? pf : pc) * 4);
@@ -325,27 +362,43 @@ void build_workspace(mmhip_engine& e) {
             for (int j = 0; j < 2; ++j) e.g_lnp[i][j] = w.take(partial_floats_rows((int)Mt, (int)H, 2) * 4);
     }
     auto f = [&](size_t n) { return w.take(n * 4); };
+    // sizing shared by both handle kinds.  Split-K scratch of the <= 128-row GEMMs of a tower; parity mode without plane pairs: split planes of the
+    // operands of one GEMM call at a time per stream (x3.hip) -- the widest NT problem of a tower, or the four weight-gradient problems of a
+    // text layer together
+    auto splitk_floats = [](size_t H, size_t I) { return (size_t)(I / 384 + 1) * 128 * (size_t)(I > 3 * H ? I : 3 * H); };
+    auto x3_nt = [](size_t M, size_t H, size_t I) {
+        size_t b = 0;
+        const size_t nk[5][2] = {{3 * H, H}, {H, H}, {I, H}, {H, I}, {H, 3 * H}};
+        for (auto& q : nk) { const size_t v = x3_nt_scratch_bytes((int)M, (int)q[0], (int)q[1]); if (v > b) b = v; }
+        return b;
+    };
+    auto x3_txt = [&]() {
+        const size_t tn = x3_tn_scratch_bytes((int)Mt, (int)H, (int)I) + x3_tn_scratch_bytes((int)Mt, (int)I, (int)H) + x3_tn_scratch_bytes((int)Mt, (int)(3 * H), (int)H) +
+                          x3_tn_scratch_bytes((int)Mt, (int)H, (int)H);
+        const size_t nt = x3_nt(Mt, H, I);
+        return tn > nt ? tn : nt;
+    };
+    const bool x3_split = c.dtype == MMHIP_BF16X3 && !e.px;
+    if (!mm) {          // the fused CLS head: logits, their gradient, the loss word, and d CLS rows when the last layer ran on full rows
+        e.h_out_cls = f(Bm * C); e.h_d_out_cls = f(Bm * C); e.h_dxcls = f(Bm * H); e.h_loss = f(8);
+        e.splitk_ws = f(splitk_floats(H, I)); e.has_splitk = true;
+        if (x3_split) {
+            e.x3_bytes[0] = e.x3_bytes[1] = x3_txt(); e.x3_bytes[2] = 0;
+            for (int i = 0; i < 2; ++i) e.x3_ws[i] = w.take(e.x3_bytes[i]);
+        }
+        e.ws_need = e.ws_base = w.off;
+        return;
+    }
     e.h_vpool = f(Bm * Hv); e.h_tpool = f(Bm * H); e.h_txt_e = f(Bm * E); e.h_img_e = f(Bm * E); e.h_txt_n = f(Bm * E); e.h_img_n = f(Bm * E);
     e.h_txt_inv = f(Bm); e.h_img_inv = f(Bm); e.h_logits = f(Bm * Bm);
     e.h_q = f(Bt * H); e.h_qk = f(Bt * H); e.h_prob = f(Bt * P); e.h_xbar = f(Bt * H); e.h_z = f(Bt * (H + Hv)); e.h_feats = f(Bt * H);
     e.h_featd = f(Bm * H); e.h_out_cls = f(Bm * C); e.h_out_tim = f(Bm * 2);
-    e.splitk_ws = f((size_t)(I / 384 + 1) * 128 * (size_t)(I > 3 * H ? I : 3 * H)); e.has_splitk = true;
-    e.splitk_ws_vit = f((size_t)(Iv / 384 + 1) * 128 * (size_t)(Iv > 3 * Hv ? Iv : 3 * Hv));
-    if (c.dtype == MMHIP_BF16X3 && !e.px) {
-        // split planes of the operands of one GEMM call at a time per stream (x3.hip): the widest NT problem of a tower, or the four
-        // weight-gradient problems of a text layer together
-        auto nt = [](size_t M, size_t H, size_t I) {
-            size_t b = 0;
-            const size_t nk[5][2] = {{3 * H, H}, {H, H}, {I, H}, {H, I}, {H, 3 * H}};
-            for (auto& q : nk) { const size_t v = x3_nt_scratch_bytes((int)M, (int)q[0], (int)q[1]); if (v > b) b = v; }
-            return b;
-        };
-        const size_t tn = x3_tn_scratch_bytes((int)Mt, (int)H, (int)I) + x3_tn_scratch_bytes((int)Mt, (int)I, (int)H) + x3_tn_scratch_bytes((int)Mt, (int)(3 * H), (int)H) +
-                          x3_tn_scratch_bytes((int)Mt, (int)H, (int)H);
-        size_t vit = nt(Mv, Hv, Iv);
+    e.splitk_ws = f(splitk_floats(H, I)); e.has_splitk = true;
+    e.splitk_ws_vit = f(splitk_floats(Hv, Iv));
+    if (x3_split) {
+        size_t vit = x3_nt(Mv, Hv, Iv);
         { const size_t pe = x3_nt_scratch_bytes((int)(Bm * (P - 1)), (int)Hv, (int)Kpp); if (pe > vit) vit = pe; }
-        size_t txt = nt(Mt, H, I);
-        if (tn > txt) txt = tn;
+        const size_t txt = x3_txt();
         e.x3_bytes[0] = txt > vit ? txt : vit; e.x3_bytes[1] = txt; e.x3_bytes[2] = vit;
         for (int i = 0; i < 3; ++i) e.x3_ws[i] = w.take(e.x3_bytes[i]);
     }
@@ -355,7 +408,6 @@ void build_workspace(mmhip_engine& e) {
     e.ws_need = e.ws_base = w.off;
 }
 
-enum { STREAM_EMBED = 1, STREAM_HEAD = 2 };
 inline uint32_t stream_attn(int l) { return 16 + 4 * l; }
 inline uint32_t stream_attn_out(int l) { return 16 + 4 * l + 1; }
 inline uint32_t stream_ffn_out(int l) { return 16 + 4 * l + 2; }
@@ -521,6 +573,7 @@ int text_forward(mmhip_engine& e, hipStream_t s) {
     ea.maskbias = e.wsp<float>(e.maskbias);
     ea.posts = Bt; ea.T = T; ea.H = H; ea.xlmr = c.txt_kind == MMHIP_TXT_XLMR; ea.pad_id = c.pad_id; ea.eps = c.ln_eps_txt;
     ea.drop = make_drop(c.p_hidden, e.seed, STREAM_EMBED, tr);
+    if (e.has_tt) ea.type_ids = e.wsp<int64_t>(e.tt_all);
     const bool px = e.px;
     embed_pair(ea, px, e.ws + e.x0p);
     CHECK_HIP(launch_embed_fwd(ea, dt, s));
@@ -879,6 +932,42 @@ int heads_backward(mmhip_engine& e, hipStream_t s) {
     return 0;
 }
 
+// ---- text-only handle: the fused CLS classifier head (heads.hip), one launch per direction
+ClsHeadArgs txt_head_args(const mmhip_engine& e) {
+    const mmhip_config& c = e.cfg;
+    // parity mode keeps the fp32 form of the last hidden state beside its plane pair: the head reads that
+    return cls_head(text_last(e), e.cls_compact ? (size_t)c.hidden : (size_t)e.T * c.hidden, e.dt(), e.train + e.lin_w, e.B, c.num_labels, c.hidden,
+                    make_drop(c.p_head, e.seed, STREAM_HEAD, e.train_mode));
+}
+// logits (and, with labels, loss / correct count / d logits kept in the handle for the backward)
+int txt_head_forward(mmhip_engine& e, const int64_t* onehot, const float* class_w, float* logits, float* loss, int* n_correct, hipStream_t s) {
+    ClsHeadArgs a = txt_head_args(e);
+    a.bias = e.train + e.lin_b; a.logits = e.wsp<float>(e.h_out_cls);
+    if (onehot) {
+        a.onehot = onehot; a.class_w = class_w; a.loss = e.wsp<float>(e.h_loss); a.n_correct = n_correct; a.d_logits_out = e.wsp<float>(e.h_d_out_cls);
+    }
+    CHECK_HIP(launch_cls_head_fwd(a, s));
+    if (logits) CHECK_HIP(hipMemcpyAsync(logits, a.logits, (size_t)e.B * e.cfg.num_labels * 4, hipMemcpyDeviceToDevice, s));
+    if (onehot && loss) CHECK_HIP(hipMemcpyAsync(loss, a.loss, 4, hipMemcpyDeviceToDevice, s));
+    if (onehot) e.bd_out_cls = a.d_logits_out;
+    return 0;
+}
+int txt_head_backward(mmhip_engine& e, hipStream_t s) {
+    const int H = e.cfg.hidden;
+    ClsHeadArgs a = txt_head_args(e);
+    a.d_logits = e.bd_out_cls; a.dW = e.grad + e.lin_w; a.db = e.grad + e.lin_b; a.accumulate = 1;
+    if (e.cls_compact) {          // straight into the compact CLS-row gradient the last layer's backward consumes
+        a.dx = e.ws + e.g_dx; a.dx_stride = H; a.dx_dtype = e.dt(); a.dx_scale = e.gscale();
+        CHECK_HIP(launch_cls_head_bwd(a, s));
+        return 0;
+    }
+    // MMHIP_CLS_ONLY=0 (or no layer): fp32 rows, spread into the otherwise-zero full gradient tensor
+    a.dx = e.wsp<float>(e.h_dxcls); a.dx_stride = H; a.dx_dtype = DT_F32; a.dx_scale = 1.f;
+    CHECK_HIP(launch_cls_head_bwd(a, s));
+    CHECK_HIP(launch_scatter_cls_rows(e.wsp<float>(e.h_dxcls), e.ws + e.g_dx, e.Bt, e.T, H, e.dt(), s, e.gscale()));
+    return 0;
+}
+
 // one text layer; on entry g_dx holds the gradient of the layer's output, on exit of its input
 int text_layer_backward(mmhip_engine& e, int l, hipStream_t s) {
     const mmhip_config& c = e.cfg;
@@ -1031,6 +1120,7 @@ int embed_backward(mmhip_engine& e, hipStream_t s) {
     b.partial = e.wsp<float>(e.g_partial);
     b.alpha = 1.0f / e.gscale();
     b.row_state = e.word_row_state;
+    if (e.has_tt) { b.type_ids = e.wsp<int64_t>(e.tt_all); b.type_rows = 2; }      // BERT's two-row table: both rows take their tokens' gradient
     if (deterministic()) { b.det_rows = e.wsp<float>(e.g_det_rows); b.max_pos = c.max_pos; }
     b.status = guard_flag(e) ? guard_counter(e) : nullptr;
     CHECK_HIP(launch_embed_bwd(b, e.dt(), s));
@@ -1095,7 +1185,7 @@ uint64_t mmhip_buffer_numel(mmhip_handle h, int buffer) { return !h ? 0 : (buffe
 uint64_t mmhip_workspace_bytes(mmhip_handle h) { return h ? h->ws_need : 0; }
 int mmhip_reserve_itc_global(mmhip_handle h, int max_world) {
     if (!h || max_world < 0) return MMHIP_E_INVALID;
-    if (h->ws) return MMHIP_E_STATE;          // the workspace is sized before it is bound
+    if (h->ws || h->txt_only) return MMHIP_E_STATE;          // the workspace is sized before it is bound
     mmhip_engine& e = *h;
     const size_t Bm = e.cfg.max_posts, E = e.cfg.proj_dim, Gm = (size_t)max_world * Bm;
     if (max_world > 1 && Gm > (size_t)ITC_GLOBAL_MAX_G) return MMHIP_E_INVALID;
@@ -1112,12 +1202,13 @@ int mmhip_reserve_itc_global(mmhip_handle h, int max_world) {
 }
 int mmhip_set_itc_global(mmhip_handle h, int world, int rank) {
     if (!h || world < 1 || rank < 0 || rank >= world) return MMHIP_E_INVALID;
+    if (h->txt_only) return MMHIP_E_STATE;
     if (world > 1 && world > h->itc_max_world) return MMHIP_E_CAPACITY;
     h->itc_world = world; h->itc_rank = rank;
     return 0;
 }
 int mmhip_itc_gather_buffers(mmhip_handle h, void** txt_local, void** img_local, void** txt_all, void** img_all) {
-    if (!h || !h->ws || !h->itc_max_world) return MMHIP_E_STATE;
+    if (!h || !h->ws || !h->itc_max_world || h->txt_only) return MMHIP_E_STATE;
     const mmhip_engine& e = *h;
     if (txt_local) *txt_local = e.ws + e.h_txt_n;
     if (img_local) *img_local = e.ws + e.h_img_n;
@@ -1126,7 +1217,7 @@ int mmhip_itc_gather_buffers(mmhip_handle h, void** txt_local, void** img_local,
     return 0;
 }
 int mmhip_bind(mmhip_handle h, float* frozen, float* train, float* train_grad, void* workspace, uint64_t workspace_bytes) {
-    if (!h || !frozen || !train || !workspace) return MMHIP_E_INVALID;
+    if (!h || !frozen || !train || !workspace || h->txt_only) return MMHIP_E_INVALID;
     if (workspace_bytes < h->ws_need) return MMHIP_E_CAPACITY;
     if (((uintptr_t)frozen | (uintptr_t)train | (uintptr_t)train_grad | (uintptr_t)workspace) & 255) return MMHIP_E_INVALID;
     h->frozen = frozen; h->train = train; h->grad = train_grad; h->ws = (char*)workspace; h->ws_bytes = workspace_bytes;
@@ -1137,6 +1228,7 @@ int mmhip_refresh_weights(mmhip_handle h, int which, void* stream) {
     if (!h || !h->ws) return MMHIP_E_STATE;
     hipStream_t s = (hipStream_t)stream;
     mmhip_engine& e = *h;
+    if ((which & 1) && e.txt_only) return MMHIP_E_STATE;          // no image tower, no frozen buffer (mmhip_txt_refresh_weights refreshes the text tower)
     if (which & 1) {
         for (int l = 0; l < e.cfg.layers_img; ++l)
             CHECK_RC(refresh_layer(e, e.frozen, e.vit[l], e.vit_w16[l], false, s, e.Hv(), e.Iv()));
@@ -1152,7 +1244,7 @@ int mmhip_refresh_weights(mmhip_handle h, int which, void* stream) {
 int mmhip_forward(mmhip_handle h, const int64_t* ids, const int64_t* mask, const float* pixels, const int64_t* tim_ids,
                   const int64_t* tim_mask, int B, int T, int train, uint64_t seed, float* out_cls, float* logits_per_text,
                   float* out_tim, float* mm_features, void* stream) {
-    if (!h || !h->ws) return MMHIP_E_STATE;
+    if (!h || !h->ws || h->txt_only) return MMHIP_E_STATE;          // (a text-only handle has mmhip_txt_forward)
     if (!ids || !mask || B < 1 || T < 1) return MMHIP_E_INVALID;
     if ((tim_ids == nullptr) != (tim_mask == nullptr)) return MMHIP_E_INVALID;
     mmhip_engine& e = *h;
@@ -1252,12 +1344,12 @@ uint64_t mmhip_vision_record_bytes(mmhip_handle h) {
     return (P * h->Hv() * h->esz() + (uint64_t)h->Hv() * 4 + 255) & ~255ull;
 }
 int mmhip_vision_export(mmhip_handle h, const int64_t* slots, void* cache, uint64_t cache_records, void* stream) {
-    if (!h || !h->ws || !h->fwd_done) return MMHIP_E_STATE;
+    if (!h || !h->ws || !h->fwd_done || h->txt_only) return MMHIP_E_STATE;
     if (!slots || !cache || ((uintptr_t)cache & 15)) return MMHIP_E_INVALID;
     return vision_copy(*h, 1, slots, cache, cache_records, h->B, (hipStream_t)stream);
 }
 int mmhip_vision_import(mmhip_handle h, const int64_t* slots, const void* cache, uint64_t cache_records, int B, void* stream) {
-    if (!h || !h->ws) return MMHIP_E_STATE;
+    if (!h || !h->ws || h->txt_only) return MMHIP_E_STATE;
     if (!slots || !cache || ((uintptr_t)cache & 15) || B < 1) return MMHIP_E_INVALID;
     if (B > h->cfg.max_posts) return MMHIP_E_CAPACITY;
     CHECK_RC(vision_copy(*h, 0, slots, const_cast<void*>(cache), cache_records, B, (hipStream_t)stream));
@@ -1267,7 +1359,7 @@ int mmhip_vision_import(mmhip_handle h, const int64_t* slots, const void* cache,
 
 int mmhip_loss(mmhip_handle h, const int64_t* onehot, const float* class_w, const int64_t* lbl_tim, float w_cls, float w_itc,
                float w_itm, float* loss, int* n_correct, void* stream) {
-    if (!h || !h->fwd_done) return MMHIP_E_STATE;
+    if (!h || !h->fwd_done || h->txt_only) return MMHIP_E_STATE;
     if (!onehot) return MMHIP_E_INVALID;
     mmhip_engine& e = *h;
     if (w_itm != 0.f && (!e.itm || !lbl_tim)) return MMHIP_E_INVALID;
@@ -1331,7 +1423,7 @@ int mmhip_backward_stage(mmhip_handle h, int stage, void* stream) {
     mmhip_engine& e = *h;
     hipStream_t s = (hipStream_t)stream;
     const int L = e.cfg.layers_txt;
-    if (stage == 0) return heads_backward(e, s);
+    if (stage == 0) return e.txt_only ? txt_head_backward(e, s) : heads_backward(e, s);
     if (stage >= 1 && stage <= L) return text_layer_backward(e, L - stage, s);
     if (stage == L + 1) return embed_backward(e, s);
     return MMHIP_E_INVALID;
@@ -1451,6 +1543,9 @@ int mmhip_adamw_rows_guarded(float* p, float* g, float* m, float* v, int rows, i
                            guard_words2 ? guard_words2 + 1 : nullptr);
 }
 
+static int step_backward_update(mmhip_handle h, int use_itc, int use_itm, float* adam_m, float* adam_v, float lr, float beta1, float beta2, float eps,
+                                float weight_decay, int step, float grad_scale, void* stream, mmhip_exchange_cb cb, void* user);
+
 // One fused training step, enqueued natively (no per-stage host round trips): forward (train mode) -> loss -> backward ->
 // AdamW over the ranges that receive gradients for this flag set (torch skips `grad is None` tensors) ->
 // 16-bit weight refresh.  Single-rank form of MMLate_Model.train_step; a data-parallel caller keeps the staged calls.
@@ -1475,6 +1570,14 @@ static int train_step_impl(mmhip_handle h, const int64_t* ids, const int64_t* ma
         CHECK_RC(cb(user, MMHIP_CB_GATHER_ITC));
     }
     CHECK_RC(mmhip_loss(h, onehot, class_w, use_itm ? lbl_tim : nullptr, w_cls, use_itc ? w_itc : 0.f, use_itm ? w_itm : 0.f, loss, n_correct, stream));
+    return step_backward_update(h, use_itc, use_itm, adam_m, adam_v, lr, beta1, beta2, eps, weight_decay, step, grad_scale, stream, cb, user);
+}
+
+// second half of a fused step, shared by the late-fusion and the text-only handle: backward, per-layer AdamW + operand refresh beside it, the
+// remaining dense ranges, the row-lazy word table.  On entry the forward has run and the output gradients are in the handle.
+static int step_backward_update(mmhip_handle h, int use_itc, int use_itm, float* adam_m, float* adam_v, float lr, float beta1, float beta2, float eps,
+                                float weight_decay, int step, float grad_scale, void* stream, mmhip_exchange_cb cb, void* user) {
+    mmhip_engine& e = *h;
     // Backward.  With the side stream on, each text layer's AdamW and 16-bit weight refresh follow its weight-gradient GEMM on the
     // SIDE stream, beside the activation-gradient chain of the layers below (an HBM-bound kernel next to MFMA-bound ones) instead
     // of after the whole backward; the layer's fp32 LayerNorm weights and transposed 16-bit copies are read by its own backward
@@ -1685,6 +1788,104 @@ int mmhip_gemm_timing_by_shape(mmhip_handle h, char* out, uint64_t capacity) {
     }
     out[pos < capacity ? pos : capacity - 1] = 0;
     return 0;
+}
+
+// ================================================================================================ text-only handle (mmhip_txt_*)
+// The reference's text-only trainer (models/text_only.py: BERT / BERNICE + TextModel.train): the text tower of this engine -- the same layer launch
+// sequences, forward and backward -- under the fused CLS classifier head, without the image tower and the dual-encoder heads.
+int mmhip_txt_create(const mmhip_txt_config* cfg, mmhip_txt_handle* out) {
+    if (!cfg || !out) return MMHIP_E_INVALID;
+    const mmhip_txt_config& t = *cfg;
+    if (t.hidden <= 0 || t.hidden % 128 || t.hidden > 1024 || t.heads * 64 != t.hidden || t.inter <= 0 || t.inter % 128 || t.layers < 0) return MMHIP_E_INVALID;
+    if (t.max_text_len > 128 || t.max_text_len < 1 || t.max_posts < 1 || t.max_posts > 1024) return MMHIP_E_INVALID;
+    if (t.dtype != MMHIP_BF16 && t.dtype != MMHIP_F16 && t.dtype != MMHIP_BF16X3) return MMHIP_E_INVALID;
+    if (t.num_labels < 1 || t.num_labels > CLS_HEAD_MAX_C || t.vocab < 1 || t.type_vocab < 1 || t.type_vocab > 2) return MMHIP_E_INVALID;
+    if (t.txt_kind != MMHIP_TXT_XLMR && t.txt_kind != MMHIP_TXT_BERT) return MMHIP_E_INVALID;
+    if (t.txt_kind == MMHIP_TXT_XLMR && t.max_pos < t.max_text_len + t.pad_id + 1) return MMHIP_E_INVALID;
+    if (t.txt_kind == MMHIP_TXT_BERT && t.max_pos < t.max_text_len) return MMHIP_E_INVALID;
+    if (t.pad_id < 0 || t.pad_id >= t.vocab || !(t.p_hidden >= 0.f) || !(t.p_attn >= 0.f) || !(t.p_head >= 0.f) || !(t.loss_scale >= 0.f)) return MMHIP_E_INVALID;
+    mmhip_engine* e = new (std::nothrow) mmhip_engine();
+    if (!e) return MMHIP_E_INVALID;
+    mmhip_config& c = e->cfg;
+    c = mmhip_config{};
+    c.hidden = t.hidden; c.heads = t.heads; c.inter = t.inter; c.layers_txt = t.layers; c.layers_img = 0;
+    c.vocab = t.vocab; c.max_pos = t.max_pos; c.type_vocab = t.type_vocab; c.txt_kind = t.txt_kind; c.pad_id = t.pad_id;
+    // image-tower and dual-encoder fields: placeholders that only keep the shared struct's geometry helpers (P(), Hv(), Kpp()) defined -- a text-only
+    // handle never launches, carves or lays out anything from them (build_layout_txt, the `mm` branches of build_workspace)
+    c.ln_eps_txt = c.ln_eps_img = t.ln_eps; c.image = c.patch = 16; c.proj_dim = 1; c.num_labels = t.num_labels; c.fusion = MMHIP_FUSION_CONCAT;
+    c.p_hidden = t.p_hidden; c.p_attn = t.p_attn; c.p_head = t.p_head; c.dtype = t.dtype; c.max_posts = t.max_posts; c.max_text_len = t.max_text_len;
+    c.loss_scale = t.loss_scale; c.img_kind = MMHIP_IMG_VIT;
+    e->txt_only = true;
+    e->tm_prefix = "bert_model.";
+    if (c.dtype == MMHIP_BF16X3) { const char* v = getenv("MMHIP_X3_PAIRS"); e->px = v ? atoi(v) != 0 : true; }
+    if (c.dtype == MMHIP_BF16X3) { const char* v = getenv("MMHIP_X3_BWD"); const int n = v ? atoi(v) : 3; e->bwd_np = n >= 1 && n <= 3 ? n : 3; }
+    build_layout_txt(*e);
+    build_workspace(*e);
+    *out = e;
+    return 0;
+}
+void mmhip_txt_destroy(mmhip_txt_handle h) { if (h && h->txt_only) mmhip_destroy(h); }
+int mmhip_txt_param_count(mmhip_txt_handle h) { return h && h->txt_only ? (int)h->params.size() : MMHIP_E_INVALID; }
+int mmhip_txt_param_info_at(mmhip_txt_handle h, int i, mmhip_param_info* out) { return h && h->txt_only ? mmhip_param_info_at(h, i, out) : MMHIP_E_INVALID; }
+uint64_t mmhip_txt_numel(mmhip_txt_handle h) { return h && h->txt_only ? h->n_train : 0; }
+uint64_t mmhip_txt_workspace_bytes(mmhip_txt_handle h) { return h && h->txt_only ? h->ws_need : 0; }
+int mmhip_txt_bind(mmhip_txt_handle h, float* params, float* grad, void* workspace, uint64_t workspace_bytes) {
+    if (!h || !h->txt_only || !params || !workspace) return MMHIP_E_INVALID;
+    if (workspace_bytes < h->ws_need) return MMHIP_E_CAPACITY;
+    if (((uintptr_t)params | (uintptr_t)grad | (uintptr_t)workspace) & 255) return MMHIP_E_INVALID;
+    h->frozen = nullptr; h->train = params; h->grad = grad; h->ws = (char*)workspace; h->ws_bytes = workspace_bytes;
+    h->fwd_done = false;
+    return 0;
+}
+int mmhip_txt_refresh_weights(mmhip_txt_handle h, void* stream) {
+    if (!h || !h->txt_only) return MMHIP_E_INVALID;
+    return mmhip_refresh_weights(h, 2, stream);
+}
+// forward of the tower and the head; onehot != NULL: the head also leaves loss / correct count / d logits (fused step and mmhip_txt_loss)
+static int txt_forward_impl(mmhip_txt_handle h, const int64_t* ids, const int64_t* mask, const int64_t* type_ids, int B, int T, int train, uint64_t seed,
+                            const int64_t* onehot, const float* class_w, float* logits, float* loss, int* n_correct, void* stream) {
+    if (!h || !h->txt_only || !h->ws) return MMHIP_E_STATE;
+    if (!ids || !mask || B < 1 || T < 1) return MMHIP_E_INVALID;
+    mmhip_engine& e = *h;
+    if (B > e.cfg.max_posts || T > e.cfg.max_text_len) return MMHIP_E_CAPACITY;
+    hipStream_t s = (hipStream_t)stream;
+    e.B = e.Bt = B; e.T = T; e.itm = false; e.train_mode = train != 0; e.seed = seed;
+    e.fwd_done = false; e.bwd_begun = false; e.bd_out_cls = nullptr; e.bd_logits = e.bd_out_tim = e.bd_feats = nullptr; e.bd_itc_global = false;
+    CHECK_HIP(launch_copy_ids_clamped(ids, e.wsp<int64_t>(e.ids_all), (size_t)B * T, e.cfg.vocab, e.bad_index, s));
+    CHECK_HIP(hipMemcpyAsync(e.ws + e.mask_all, mask, (size_t)B * T * 8, hipMemcpyDeviceToDevice, s));
+    // a one-row type table has nothing to select: every token takes row 0 whatever the caller passes (RoBERTa-shaped checkpoints)
+    e.has_tt = type_ids != nullptr && e.cfg.type_vocab > 1;
+    if (e.has_tt) CHECK_HIP(launch_copy_ids_clamped(type_ids, e.wsp<int64_t>(e.tt_all), (size_t)B * T, e.cfg.type_vocab, e.bad_index, s));
+    CHECK_RC(side_init(e));
+    e.cur_part[0] = e.cur_part[1] = 0;
+    CHECK_RC(e.span(0, s));
+    CHECK_RC(text_forward(e, s));
+    CHECK_RC(e.span(2, s));
+    CHECK_RC(txt_head_forward(e, onehot, class_w, logits, loss, n_correct, s));
+    CHECK_RC(e.span(3, s));
+    e.fwd_done = true;
+    return 0;
+}
+int mmhip_txt_forward(mmhip_txt_handle h, const int64_t* ids, const int64_t* mask, const int64_t* type_ids, int B, int T, int train, uint64_t seed,
+                      float* logits, void* stream) {
+    return txt_forward_impl(h, ids, mask, type_ids, B, T, train, seed, nullptr, nullptr, logits, nullptr, nullptr, stream);
+}
+int mmhip_txt_loss(mmhip_txt_handle h, const int64_t* onehot, const float* class_w, float* loss, int* n_correct, void* stream) {
+    if (!h || !h->txt_only || !h->fwd_done) return MMHIP_E_STATE;
+    if (!onehot) return MMHIP_E_INVALID;
+    return txt_head_forward(*h, onehot, class_w, nullptr, loss, n_correct, (hipStream_t)stream);
+}
+int mmhip_txt_backward(mmhip_txt_handle h, const float* d_logits, void* stream) {
+    if (!h || !h->txt_only) return MMHIP_E_STATE;
+    return mmhip_backward(h, d_logits, nullptr, nullptr, nullptr, stream);
+}
+int mmhip_txt_train_step(mmhip_txt_handle h, const int64_t* ids, const int64_t* mask, const int64_t* type_ids, const int64_t* onehot, const float* class_w,
+                         int B, int T, uint64_t seed, float* adam_m, float* adam_v, float lr, float beta1, float beta2, float eps, float weight_decay,
+                         int step, float* loss, int* n_correct, void* stream) {
+    if (!h || !h->txt_only || !h->ws || !h->grad) return MMHIP_E_STATE;
+    if (!adam_m || !adam_v || !onehot || step < 1) return MMHIP_E_INVALID;
+    CHECK_RC(txt_forward_impl(h, ids, mask, type_ids, B, T, 1, seed, onehot, class_w, nullptr, loss, n_correct, stream));
+    return step_backward_update(h, 0, 0, adam_m, adam_v, lr, beta1, beta2, eps, weight_decay, step, 1.0f, stream, nullptr, nullptr);
 }
 
 }  // extern "C"

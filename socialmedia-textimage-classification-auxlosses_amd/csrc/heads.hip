@@ -688,4 +688,170 @@ hipError_t launch_adamw(const AdamWArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------ fused CLS classifier head (text-only model)
+// Latency-bound: B x C x H is a few hundred thousand multiply-adds.  The late-fusion head spends ~20 launches here; this is one per direction.
+// element c of CLS row b, any of the storage forms the text tower leaves its last hidden state in (wave-uniform branch)
+__device__ __forceinline__ float cls_head_load(const ClsHeadArgs& a, int b, int c) {
+    const size_t off = (size_t)b * a.x_stride;
+    if (a.x_dtype == DT_BF16) return (float)reinterpret_cast<const bf16_t*>(a.x)[off + c];
+    if (a.x_dtype == DT_F16) return (float)reinterpret_cast<const f16_t*>(a.x)[off + c];
+    if (a.x_dtype == DT_F32) return reinterpret_cast<const float*>(a.x)[off + c];
+    const bf16_t* p = reinterpret_cast<const bf16_t*>(a.x) + 2 * off;          // plane pair: [hi(H) | lo(H)]
+    return (float)p[c] + (float)p[a.H + c];
+}
+// Forward: one wave per post, 16 waves per block.  A lane keeps its H / 64 elements of the dropped row in registers and walks the C rows of W.
+// With labels the launch is ONE block: its waves sum their posts' loss terms in post order, thread 0 adds the 16 wave sums in wave order.
+static constexpr int CLS_HEAD_WAVES = 16;
+__global__ __launch_bounds__(1024) void cls_head_fwd_kernel(ClsHeadArgs a) {
+    __shared__ float s_loss[CLS_HEAD_WAVES];
+    __shared__ int s_corr[CLS_HEAD_WAVES];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int H = a.H, C = a.C;
+    float lsum = 0.f;
+    int corr = 0;
+    for (int b = blockIdx.x * CLS_HEAD_WAVES + w; b < a.B; b += gridDim.x * CLS_HEAD_WAVES) {
+        float xv[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int c = lane + 64 * j;
+            float v = 0.f;
+            if (c < H) {
+                v = cls_head_load(a, b, c);
+                if (a.drop.thresh16) v = mm_keep((uint32_t)b * (uint32_t)H + (uint32_t)c, a.drop) ? v * a.drop.keep_scale : 0.f;
+            }
+            xv[j] = v;
+        }
+        float z[CLS_HEAD_MAX_C];
+#pragma unroll
+        for (int k = 0; k < CLS_HEAD_MAX_C; ++k) {
+            z[k] = 0.f;
+            if (k < C) {
+                const float* wr = a.W + (size_t)k * H;
+                float acc = 0.f;
+#pragma unroll
+                for (int j = 0; j < 16; ++j) {
+                    const int c = lane + 64 * j;
+                    if (c < H) acc = fmaf(xv[j], wr[c], acc);
+                }
+                z[k] = wave_sum(acc) + a.bias[k];
+                if (lane == 0) a.logits[(size_t)b * C + k] = z[k];
+            }
+        }
+        if (a.onehot) {          // every lane holds all logits: the post's loss term, wave-uniform
+            float mx = -INFINITY;
+            int am = 0, ay = 0;
+            long ymax = -1;
+#pragma unroll
+            for (int k = 0; k < CLS_HEAD_MAX_C; ++k)
+                if (k < C) {
+                    if (z[k] > mx) { mx = z[k]; am = k; }
+                    const long y = a.onehot[(size_t)b * C + k];
+                    if (y > ymax) { ymax = y; ay = k; }
+                }
+            float se = 0.f;
+#pragma unroll
+            for (int k = 0; k < CLS_HEAD_MAX_C; ++k) if (k < C) se += __expf(z[k] - mx);
+            const float lse = mx + __logf(se);
+            float wy = 0.f, lc = 0.f;
+#pragma unroll
+            for (int k = 0; k < CLS_HEAD_MAX_C; ++k)
+                if (k < C) {
+                    const float cw = a.class_w ? a.class_w[k] : 1.f;
+                    const float y = (float)a.onehot[(size_t)b * C + k];
+                    lc -= cw * y * (z[k] - lse);
+                    wy += cw * y;
+                }
+            if (a.d_logits_out && lane == 0) {
+#pragma unroll
+                for (int k = 0; k < CLS_HEAD_MAX_C; ++k)
+                    if (k < C) {
+                        const float cw = a.class_w ? a.class_w[k] : 1.f;
+                        const float y = (float)a.onehot[(size_t)b * C + k];
+                        a.d_logits_out[(size_t)b * C + k] = (__expf(z[k] - lse) * wy - cw * y) / (float)a.B;
+                    }
+            }
+            lsum += lc;
+            corr += (am == ay);
+        }
+    }
+    if (!a.onehot) return;
+    if (lane == 0) { s_loss[w] = lsum; s_corr[w] = corr; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = 0.f;
+        int n = 0;
+        for (int i = 0; i < CLS_HEAD_WAVES; ++i) { t += s_loss[i]; n += s_corr[i]; }
+        if (a.loss) a.loss[0] = t / (float)a.B;
+        if (a.n_correct) a.n_correct[0] = n;
+    }
+}
+// Backward: a block owns 64 columns of H; its four waves take the posts b = w, w + 4, ... and a thread one column: dW[:, h] in registers
+// (x dropped again from the hash), dx[b, h] written as it goes; the four partial dW columns are added through LDS in wave order.
+__global__ __launch_bounds__(256) void cls_head_bwd_kernel(ClsHeadArgs a) {
+    __shared__ float red[4][CLS_HEAD_MAX_C][64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int H = a.H, C = a.C, h = blockIdx.x * 64 + lane;
+    float acc[CLS_HEAD_MAX_C], wr[CLS_HEAD_MAX_C];
+#pragma unroll
+    for (int k = 0; k < CLS_HEAD_MAX_C; ++k) { acc[k] = 0.f; wr[k] = k < C ? a.W[(size_t)k * H + h] : 0.f; }
+    for (int b = w; b < a.B; b += 4) {
+        float xd = cls_head_load(a, b, h);
+        bool keep = true;
+        if (a.drop.thresh16) {
+            keep = mm_keep((uint32_t)b * (uint32_t)H + (uint32_t)h, a.drop);
+            xd = keep ? xd * a.drop.keep_scale : 0.f;
+        }
+        float dxv = 0.f;
+#pragma unroll
+        for (int k = 0; k < CLS_HEAD_MAX_C; ++k)
+            if (k < C) {
+                const float dl = a.d_logits[(size_t)b * C + k];
+                acc[k] = fmaf(dl, xd, acc[k]);
+                dxv = fmaf(dl, wr[k], dxv);
+            }
+        if (a.drop.thresh16) dxv = keep ? dxv * a.drop.keep_scale : 0.f;
+        dxv *= a.dx_scale;
+        if (a.dx) {
+            const size_t o = (size_t)b * a.dx_stride + h;
+            if (a.dx_dtype == DT_BF16) reinterpret_cast<bf16_t*>(a.dx)[o] = (bf16_t)dxv;
+            else if (a.dx_dtype == DT_F16) reinterpret_cast<f16_t*>(a.dx)[o] = (f16_t)dxv;
+            else reinterpret_cast<float*>(a.dx)[o] = dxv;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < CLS_HEAD_MAX_C; ++k) red[w][k][lane] = acc[k];
+    __syncthreads();
+    if (w == 0 && a.dW) {
+#pragma unroll
+        for (int k = 0; k < CLS_HEAD_MAX_C; ++k)
+            if (k < C) {
+                const float v = ((red[0][k][lane] + red[1][k][lane]) + red[2][k][lane]) + red[3][k][lane];
+                float* dst = a.dW + (size_t)k * H + h;
+                *dst = a.accumulate ? *dst + v : v;
+            }
+    }
+    if (blockIdx.x == 0 && w == 1 && lane < C && a.db) {
+        float sb = 0.f;
+        for (int b = 0; b < a.B; ++b) sb += a.d_logits[(size_t)b * C + lane];
+        a.db[lane] = a.accumulate ? a.db[lane] + sb : sb;
+    }
+}
+static bool cls_head_shape_ok(const ClsHeadArgs& a) {
+    return a.B >= 1 && a.C >= 1 && a.C <= CLS_HEAD_MAX_C && a.H >= 64 && a.H <= 1024 && a.H % 64 == 0 && a.x && a.W && a.x_stride >= (size_t)a.H &&
+           (a.x_dtype == DT_BF16 || a.x_dtype == DT_F16 || a.x_dtype == DT_F32 || a.x_dtype == DT_PAIR);
+}
+hipError_t launch_cls_head_fwd(const ClsHeadArgs& a, hipStream_t s) {
+    if (!cls_head_shape_ok(a) || !a.bias || !a.logits) return hipErrorInvalidValue;
+    if (!a.onehot && (a.loss || a.n_correct || a.d_logits_out)) return hipErrorInvalidValue;
+    const int blocks = (a.B + CLS_HEAD_WAVES - 1) / CLS_HEAD_WAVES;
+    hipLaunchKernelGGL(cls_head_fwd_kernel, dim3(a.onehot ? 1 : (blocks > 256 ? 256 : blocks)), dim3(64 * CLS_HEAD_WAVES), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t launch_cls_head_bwd(const ClsHeadArgs& a, hipStream_t s) {
+    if (!cls_head_shape_ok(a) || !a.d_logits) return hipErrorInvalidValue;
+    if (a.dx && (a.dx_stride < (size_t)a.H || (a.dx_dtype != DT_BF16 && a.dx_dtype != DT_F16 && a.dx_dtype != DT_F32))) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cls_head_bwd_kernel, dim3(a.H / 64), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 }  // namespace mmhip

@@ -39,6 +39,9 @@ inline DropCfg make_drop(float p, uint64_t seed, uint32_t stream, bool on = true
     return d;
 }
 
+// dropout streams every engine shares (oracle/mm_oracle.py STREAM_*); the per-layer ones are each engine's own
+enum { STREAM_EMBED = 1, STREAM_HEAD = 2 };
+
 // ------------------------------------------------------------------------------------------------ NT GEMM
 // C[M,N] = epilogue(A[M,K] B[N,K]^T): every setter that takes an operand also raises its flag, so no caller writes a.flags
 struct G {
@@ -70,6 +73,14 @@ inline void tn_pair(GemmTNProblem& p, int nprod) { p.pair = 1; p.lda *= 2; p.ldb
 inline SmallGemmArgs small(const void* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldo, int M, int N, int K, int act = ACT_NONE, int acc = 0) {
     SmallGemmArgs a{};
     a.A = A; a.W = W; a.bias = bias; a.out = out; a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldw = ldw; a.ldo = ldo; a.act = act; a.accumulate = acc;
+    return a;
+}
+
+// ------------------------------------------------------------------------------------------------ fused CLS classifier head
+// the part both launches share: the CLS rows (x_stride: H compact, T * H inside the full tensor), the classifier and the head dropout
+inline ClsHeadArgs cls_head(const void* x, size_t x_stride, int x_dtype, const float* W, int B, int C, int H, const DropCfg& drop) {
+    ClsHeadArgs a{};
+    a.x = x; a.x_stride = x_stride; a.x_dtype = x_dtype; a.W = W; a.B = B; a.C = C; a.H = H; a.drop = drop;
     return a;
 }
 

@@ -209,6 +209,8 @@ struct EmbedBwdArgs {
                           // backward's 16-bit chain, so an overflow anywhere upstream arrives here as inf / NaN -- counts and raises the flag
     const int64_t* type_ids;   // optional [rows]: with it the token-type gradient goes to row 1 of dtype from the tokens of type 1 only -- the
                                // early-fusion LXMERT tables are nn.Embedding(padding_idx = 0): type 0 gets no gradient (two-row table)
+    int type_rows;             // 2 (with type_ids): BERT's token type table, no padding_idx -- row 0 also collects its tokens' gradient; `partial`
+                               // then holds FOUR vectors (partial_floats_embed / 3 * 4 floats)
 };
 bool deterministic();     // MMHIP_DETERMINISTIC=1
 hipError_t launch_embed_fwd(const EmbedArgs& a, int dtype, hipStream_t s);
@@ -307,6 +309,32 @@ hipError_t launch_loss(const LossArgs& a, hipStream_t s);
 hipError_t launch_elementwise(int op, const float* a, const float* b, float* out, size_t n, float alpha, const DropCfg& drop, hipStream_t s);
 enum { EW_TANH_BWD = 0, EW_RELU_BWD = 1, EW_DROPOUT = 2, EW_ADD = 3, EW_COPY = 4 };
 hipError_t launch_bias_grad_f32(const float* d, int rows, int cols, int ld, float* out, int accumulate, hipStream_t s);
+
+// Fused CLS classifier head of the text-only model: logits = dropout(x[:, 0]) W^T + b in two launches (forward [+ loss], backward).
+// x: the CLS rows of the last hidden state, row b at element b * x_stride (x_stride = H for compact rows, T * H inside the full tensor); x_dtype
+// DT_BF16 | DT_F16 | DT_F32 | DT_PAIR (a pair row is [hi(H) | lo(H)] bf16 in the bytes of the fp32 row: its stride counts 4-byte elements).
+// Dropout: the engines' hash, element index b * H + c.  Limits: 1 <= C <= 16, H % 64 == 0, H <= 1024, B >= 1.  fp32 accumulation, no atomics:
+// every output word has one writer and every sum a fixed order, so two calls give the same bits.
+static constexpr int CLS_HEAD_MAX_C = 16;
+struct ClsHeadArgs {
+    const void* x; size_t x_stride; int x_dtype;
+    const float* W; const float* bias;            // [C, H], [C] (bias: forward only)
+    DropCfg drop;
+    int B, C, H;
+    // forward
+    float* logits;                                // [B, C]
+    const int64_t* onehot; const float* class_w;  // optional labels [B, C] (+ optional class weights [C]): with them the three outputs below
+    float* loss;                                  // [1] batch mean of -sum_c w_c y_c log softmax(logits)_c
+    int* n_correct;                               // [1] argmax(logits) == argmax(onehot)
+    float* d_logits_out;                          // [B, C] gradient of loss (any of the three may be null)
+    // backward
+    const float* d_logits;                        // [B, C]
+    float* dW; float* db;                         // [C, H], [C]; accumulate != 0: added to what is there (still one writer per word)
+    void* dx; size_t dx_stride; int dx_dtype;     // rows b * dx_stride of dropout'(d_logits W) * dx_scale as DT_BF16 | DT_F16 | DT_F32
+    float dx_scale; int accumulate;
+};
+hipError_t launch_cls_head_fwd(const ClsHeadArgs& a, hipStream_t s);
+hipError_t launch_cls_head_bwd(const ClsHeadArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------- optimizer
 struct AdamWArgs {

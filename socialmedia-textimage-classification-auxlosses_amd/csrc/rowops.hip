@@ -348,7 +348,8 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(EmbedArgs a) {
 // version).  Word rows are scattered with lane-dense atomics (each wave instruction covers 256 contiguous bytes)
 // staged through a wave-private LDS row.
 static constexpr int EMB_POSTS_PER_BLOCK = 16;
-template <typename T>
+// TT2 (EmbedBwdArgs::type_rows == 2 with type ids): a second accumulator collects the type-0 tokens for row 0 of the type table
+template <typename T, bool TT2 = false>
 __global__ __launch_bounds__(256) void embed_bwd_kernel(EmbedBwdArgs a) {
     __shared__ __attribute__((aligned(16))) float red[3][4][1024];
     float (*rowbuf)[1024] = red[0];          // wave-private staging rows while the posts are walked; reductions afterwards
@@ -358,10 +359,11 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(EmbedBwdArgs a) {
     const int tok = blockIdx.x, blk = blockIdx.y * gridDim.x + blockIdx.x, nblk = gridDim.x * gridDim.y;
     const float al = a.alpha == 0.f ? 1.f : a.alpha;
     float dg[MAXC][4], db[MAXC][4], dt[MAXC][4], gam[MAXC][4], pacc[MAXC][4];
+    float dt0[TT2 ? MAXC : 1][4];
 #pragma unroll
     for (int t = 0; t < MAXC; ++t) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { dg[t][e] = 0.f; db[t][e] = 0.f; dt[t][e] = 0.f; gam[t][e] = 0.f; pacc[t][e] = 0.f; }
+        for (int e = 0; e < 4; ++e) { dg[t][e] = 0.f; db[t][e] = 0.f; dt[t][e] = 0.f; gam[t][e] = 0.f; pacc[t][e] = 0.f; if (TT2) dt0[TT2 ? t : 0][e] = 0.f; }
         if (lane + 64 * t < nch) load4<float>(a.gamma + (lane + 64 * t) * 4, gam[t]);
     }
     int pid0 = -1;
@@ -421,6 +423,7 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(EmbedBwdArgs a) {
                 for (int e = 0; e < 4; ++e) {
                     const float o = rstd * (g[t][e] - c1 - xh[t][e] * c2);
                     if (type_on) dt[t][e] += o;
+                    else if (TT2) dt0[TT2 ? t : 0][e] += o;
                     if (pos_reg) pacc[t][e] += o;
                     ov[e] = o * al;
                 }
@@ -490,6 +493,20 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(EmbedBwdArgs a) {
     if (seen_bad && a.status && lane == 0) {
         atomicAdd(a.status, 1u);
         atomicOr(a.status + 1, 1u);
+    }
+    if (TT2) {          // row 0 of the type table: the same reduction once more, through the (now free) staging rows
+        __syncthreads();
+#pragma unroll
+        for (int t = 0; t < MAXC; ++t)
+            if (lane + 64 * t < nch)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) rowbuf[w][(lane + 64 * t) * 4 + e] = dt0[TT2 ? t : 0][e];
+        __syncthreads();
+        for (int c = threadIdx.x; c < a.H; c += 256) {
+            const float st0 = rowbuf[0][c] + rowbuf[1][c] + rowbuf[2][c] + rowbuf[3][c];
+            if (a.partial) a.partial[((size_t)3 * nblk + blk) * a.H + c] = st0;
+            else atomicAdd(a.dtype + c, st0 * al);
+        }
     }
 }
 
@@ -873,11 +890,17 @@ hipError_t launch_embed_bwd(const EmbedBwdArgs& a, int dtype, hipStream_t s) {
     if (a.posts <= 0) return hipSuccess;
     if (a.H % 4 || a.H > 1024) return hipErrorInvalidValue;
     const dim3 grid(a.T, (a.posts + EMB_POSTS_PER_BLOCK - 1) / EMB_POSTS_PER_BLOCK);
-    if (dtype == DT_BF16) hipLaunchKernelGGL(embed_bwd_kernel<bf16_t>, grid, dim3(256), 0, s, a);
+    const bool tt2 = a.type_ids && a.type_rows == 2;
+    if (tt2) {
+        if (dtype == DT_BF16) hipLaunchKernelGGL((embed_bwd_kernel<bf16_t, true>), grid, dim3(256), 0, s, a);
+        else if (dtype == DT_F16) hipLaunchKernelGGL((embed_bwd_kernel<f16_t, true>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((embed_bwd_kernel<float, true>), grid, dim3(256), 0, s, a);
+    } else if (dtype == DT_BF16) hipLaunchKernelGGL(embed_bwd_kernel<bf16_t>, grid, dim3(256), 0, s, a);
     else if (dtype == DT_F16) hipLaunchKernelGGL(embed_bwd_kernel<f16_t>, grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL(embed_bwd_kernel<float>, grid, dim3(256), 0, s, a);
     if (a.partial) {
         launch_reduce_partials(a.partial, (int)(grid.x * grid.y), a.H, a.dgamma, s, a.alpha == 0.f ? 1.f : a.alpha, a.dbeta, a.dtype + (a.type_ids ? a.H : 0));
+        if (tt2) launch_reduce_partials(a.partial + (size_t)3 * grid.x * grid.y * a.H, (int)(grid.x * grid.y), a.H, a.dtype, s, a.alpha == 0.f ? 1.f : a.alpha);
     }
     if (a.det_rows)
         hipLaunchKernelGGL(embed_scatter_det_kernel, dim3(a.posts * a.T + a.max_pos), dim3(64), 0, s, a.ids, a.pos_ids, a.det_rows, a.dword, a.dpos,

@@ -164,6 +164,37 @@ class Lxmert_Dataset(torch.utils.data.Dataset):
                 "labels": torch.as_tensor(self.labels[index], dtype=torch.long), "data_id": torch.tensor(int(self.data_ids_num[index]), dtype=torch.long)}
 
 
+class TxtOnly_Dataset(torch.utils.data.Dataset):
+    """Item layout of the reference's TxtOnly_Dataset (models/datasets.py:11-75): the normalised tweet tokenised per item to max_length -- `ids`,
+    `mask`, `token_type_ids` for the models that have them (everything but roberta / bernice), one-hot `target`, `data_id`.  All [T] int64."""
+
+    def __init__(self, model_name, data_ids, text, labels, tokenizer, max_length, task_name, normalization=True):
+        self.model_name, self.data_ids, self.text, self.labels = model_name, data_ids, text, labels
+        self.task_name = task_name
+        if task_name == "poi":
+            self.data_ids_num = [float(str(x).split("_")[0]) for x in data_ids]
+        elif task_name in {"polid", "poladv"}:
+            self.data_ids_num = [float(str(x)[2:]) for x in data_ids]
+        else:
+            self.data_ids_num = data_ids
+        self.tokenizer, self.max_length, self.normalization = tokenizer, max_length, normalization
+
+    def __len__(self):
+        return len(self.labels)
+
+    def __getitem__(self, index):
+        text = normalize_tweet(self.text[index]) if self.normalization else self.text[index]
+        with_types = self.model_name not in {"roberta", "bernice"}
+        enc = self.tokenizer(text, padding="max_length", max_length=self.max_length, truncation=True, add_special_tokens=True,
+                             return_attention_mask=True, return_token_type_ids=with_types)
+        item = {"ids": torch.tensor(enc["input_ids"], dtype=torch.long), "mask": torch.tensor(enc["attention_mask"], dtype=torch.long)}
+        if with_types:
+            item["token_type_ids"] = torch.tensor(enc["token_type_ids"], dtype=torch.long)
+        item["target"] = torch.as_tensor(self.labels[index], dtype=torch.long)
+        item["data_id"] = torch.tensor(int(self.data_ids_num[index]), dtype=torch.long)
+        return item
+
+
 def lxmert_loaders_from_data_key(cfg, args, tokenizer, data_path=None):
     """reference MMEarly_Model.load_data, LXMERT branch (models/mm_early.py:228-258): prepare_data -> three Lxmert_Datasets -> loaders
     (train shuffled).  Data parallel: the training set is sharded by a DistributedSampler, validation / test stay whole."""
