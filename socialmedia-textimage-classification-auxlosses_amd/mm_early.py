@@ -15,24 +15,19 @@ query length discarded.  S <= 128 (the attention backward's limit) covers the re
 State-dict keys are the reference module's (`model.*` = HF LxmertModel 4.25.1 naming, `linear_fusion`, `linear`, `linear_tim`,
 `logit_scale`).  Parity: tests/test_gpu_early.py against tests/golden/lxmert_small.npz (the reference's own module) and the oracle.
 """
-import ctypes as C
 import os
 
 import numpy as np
 import torch
-import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
 from . import dist as mmdist
 from .utils import clip_loss, agg_metrics_val
 from .config import metric_names
+from .engine_module import EngineModule, FlatTrainer, merge_ranges
 
 _DT = {"bf16": _lib.BF16, "f16": _lib.F16, "bf16x3": _lib.BF16X3}
-
-
-class _Node(nn.Module):
-    pass
 
 
 class _EarlyFunction(torch.autograd.Function):
@@ -57,11 +52,15 @@ class _EarlyFunction(torch.autograd.Function):
         return (None,) * 7 + tuple(grads)
 
 
-class Lxmert(nn.Module):
+class Lxmert(EngineModule):
     """reference models/mm_early.py:105-172.  `arch`: l_layers / r_layers / x_layers / vocab / max_pos / type_vocab (defaults: HF
     lxmert-base-uncased: 9 / 5 / 5 / 30522 / 512 / 2); weights are random-init unless `model_dir` holds a saved LxmertModel.
     Additive keywords: `dtype` ('bf16' | 'f16' | 'bf16x3' = strict parity), `max_posts` / `max_text_len` / `max_boxes` (capacity the
     workspace is sized for; it grows on demand), `seed`."""
+
+    _ABI = dict(create="mmhip_early_create", destroy="mmhip_early_destroy", param_count="mmhip_early_param_count",
+                param_info_at="mmhip_early_param_info_at", workspace_bytes="mmhip_early_workspace_bytes", num_stages="mmhip_early_num_stages",
+                stage_grad_range="mmhip_early_stage_grad_range")
 
     def __init__(self, model_dir, num_labels, max_length=None, dropout=0.1, logit_scale_init_value=2.6592, arch=None, dtype="bf16", seed=0,
                  max_posts=8, max_boxes=36):
@@ -78,9 +77,8 @@ class Lxmert(nn.Module):
         self._cfg_kw = dict(hidden=a["hidden"], heads=a["heads"], inter=a["inter"], l_layers=a["l_layers"], r_layers=a["r_layers"], x_layers=a["x_layers"],
                             vocab=a["vocab"], max_pos=a["max_pos"], type_vocab=a["type_vocab"], feat_dim=a["feat_dim"], pos_dim=a["pos_dim"], num_labels=num_labels,
                             dtype=_DT[dtype], p_hidden=a["p_hidden"], p_attn=a["p_attn"], p_head=dropout, ln_eps=a["ln_eps"])
-        self._handle, self._ws, self._capacity = None, None, (0, 0, 0)
-        self._seed_base, self._calls, self._fwd_token, self._weights_version, self._grad_dirty = 0x5DEECE66D + seed, 0, 0, None, False
-        self._create_engine(max_posts, min(128, max(int(max_length or 16), 16)), max_boxes, first=True)
+        self._init_engine(0x5DEECE66D + seed)
+        self._create_engine(max_posts, min(128, max(int(max_length or 16), 16)), max_boxes)
         g = torch.Generator(device="cpu").manual_seed(seed)
         with torch.no_grad():
             for inf in self._infos:
@@ -98,59 +96,27 @@ class Lxmert(nn.Module):
             self._load_hf(model_dir)
 
     # ------------------------------------------------------------------ engine plumbing
-    def _create_engine(self, max_posts, max_text_len, max_boxes, first=False):
-        lib = _lib.lib()
-        cfg = _lib.EarlyConfig(max_posts=int(max_posts), max_text_len=int(max_text_len), max_boxes=int(max_boxes), **self._cfg_kw)
-        h = C.c_void_p()
-        _lib.check(lib.mmhip_early_create(C.byref(cfg), C.byref(h)), "early_create")
-        if self._handle is not None:
-            lib.mmhip_early_destroy(self._handle)
-        self._handle = h
-        self._capacity = (int(max_posts), int(max_text_len), int(max_boxes))
-        dev = self.device_
-        if first:
-            n = int(lib.mmhip_early_numel(h))
-            self._flat = torch.zeros(n, dtype=torch.float32, device=dev)
-            self._flat_grad = torch.zeros(n, dtype=torch.float32, device=dev)
-            self._infos, self._offs, self._shapes = [], {}, {}
-            pi = _lib.ParamInfo()
-            for i in range(lib.mmhip_early_param_count(h)):
-                _lib.check(lib.mmhip_early_param_info_at(h, i, C.byref(pi)), "early_param_info")
-                inf = dict(name=pi.name.decode(), shape=tuple(pi.dims[: pi.ndim]), group=pi.group, offset=int(pi.offset), numel=int(pi.numel))
-                view = self._flat[inf["offset"]: inf["offset"] + inf["numel"]].view(inf["shape"])
-                p = nn.Parameter(view)
-                node, parts = self, inf["name"].split(".")
-                for part in parts[:-1]:
-                    if part not in node._modules:
-                        node.add_module(part, _Node())
-                    node = node._modules[part]
-                node.register_parameter(parts[-1], p)
-                inf["param"] = p
-                self._infos.append(inf)
-                self._offs[inf["name"]], self._shapes[inf["name"]] = inf["offset"], inf["shape"]
-            self._attach_grads()
-        if first:
-            # include/mmhip.h mmhip_early_set_index_counter: token ids / token types that had to be clamped into their tables (the reference's
-            # nn.Embedding raises IndexError for them; MMEarly_Model.check_indices does, at the end of an epoch / an evaluation loop)
-            self._bad_index = torch.zeros(1, dtype=torch.int32, device=dev)
-        _lib.check(lib.mmhip_early_set_index_counter(h, _lib.ptr(self._bad_index)), "early_set_index_counter")
-        self._ws = None
-        torch.cuda.empty_cache()
-        self._ws = torch.empty(int(lib.mmhip_early_workspace_bytes(h)), dtype=torch.uint8, device=dev)
-        _lib.check(lib.mmhip_early_bind(h, _lib.ptr(self._flat), _lib.ptr(self._flat_grad), _lib.ptr(self._ws), self._ws.numel(), _lib.stream_ptr()), "early_bind")
-        self._stage_ranges = []
-        b, e = C.c_uint64(), C.c_uint64()
-        for st in range(lib.mmhip_early_num_stages(h)):
-            _lib.check(lib.mmhip_early_stage_grad_range(h, st, C.byref(b), C.byref(e)), "early_stage_grad_range")
-            self._stage_ranges.append((int(b.value), int(e.value)))
-        self._weights_version = None
+    def _config(self, max_posts, max_text_len, max_boxes):
+        return _lib.EarlyConfig(max_posts=int(max_posts), max_text_len=int(max_text_len), max_boxes=int(max_boxes), **self._cfg_kw)
 
-    def __del__(self):
-        try:
-            if self._handle is not None:
-                _lib.lib().mmhip_early_destroy(self._handle)
-        except Exception:
-            pass
+    def _allocate_flats(self, h):
+        n = int(_lib.lib().mmhip_early_numel(h))
+        self._flat = torch.zeros(n, dtype=torch.float32, device=self.device_)
+        self._flat_grad = torch.zeros(n, dtype=torch.float32, device=self.device_)
+        return {1: self._flat}
+
+    def _on_registered(self):
+        self._offs, self._shapes = {i["name"]: i["offset"] for i in self._infos}, {i["name"]: i["shape"] for i in self._infos}
+        self._attach_grads()
+        # include/mmhip.h mmhip_early_set_index_counter: token ids / token types that had to be clamped into their tables (the reference's
+        # nn.Embedding raises IndexError for them; MMEarly_Model.check_indices does, at the end of an epoch / an evaluation loop)
+        self._bad_index = torch.zeros(1, dtype=torch.int32, device=self.device_)
+
+    def _apply_setters(self, h):
+        _lib.check(_lib.lib().mmhip_early_set_index_counter(h, _lib.ptr(self._bad_index)), "early_set_index_counter")
+
+    def _bind(self, h):
+        _lib.check(_lib.lib().mmhip_early_bind(h, _lib.ptr(self._flat), _lib.ptr(self._flat_grad), _lib.ptr(self._ws), self._ws.numel(), _lib.stream_ptr()), "early_bind")
 
     def _attach_grads(self):
         """every parameter's .grad is its slice of the flat gradient buffer the engine writes"""
@@ -190,14 +156,7 @@ class Lxmert(nn.Module):
         pooler (mm_early.py:132 takes the CLS row itself), linear_tim only with ITM, logit_scale only with ITC -- torch's AdamW skips
         `grad is None` tensors.  (The engine's step walks the same ranges.)"""
         groups = {_lib.G_ALWAYS} | ({_lib.G_ITC} if use_itc else set()) | ({_lib.G_ITM} if use_itm else set())
-        spans = sorted((i["offset"], i["offset"] + ((i["numel"] + 3) & ~3)) for i in self._infos if i["group"] in groups)
-        out = []
-        for b, e in spans:
-            if out and out[-1][1] == b:
-                out[-1][1] = e
-            else:
-                out.append([b, e])
-        return out
+        return [list(r) for r in merge_ranges((i["offset"], i["numel"]) for i in self._infos if i["group"] in groups)]
 
     def _load_hf(self, model_dir):
         """a saved LxmertModel directory (LxmertModel.from_pretrained layout): safetensors or pytorch_model.bin"""
@@ -218,10 +177,6 @@ class Lxmert(nn.Module):
                     own[k].copy_(v.to(own[k].device, torch.float32))
 
     # ------------------------------------------------------------------ engine calls
-    def _next_seed(self):
-        self._calls += 1
-        return (self._seed_base * 0x9E3779B97F4A7C15 + self._calls) & 0xFFFFFFFFFFFFFFFF
-
     def _inputs(self, ids, mask, tt, feats, boxes):
         dev = self.device_
         i64 = lambda t: None if t is None else t.to(dev, torch.int64).contiguous()
@@ -265,11 +220,6 @@ class Lxmert(nn.Module):
         self._grad_dirty = True          # the fused step finds its entry condition (zero gradient) re-established by _clean_grad
         return [None] * len(self._infos)          # (already in place: nothing for autograd to accumulate)
 
-    def _clean_grad(self):
-        if self._grad_dirty:
-            self._flat_grad.zero_()
-            self._grad_dirty = False
-
     # ------------------------------------------------------------------ reference interface
     def forward(self, ids, mask, token_type_ids, features, normalized_boxes, tim_inputs=None):
         """reference :121-163 -> (linear_output, max_embeddings_t, max_embeddings_v, out_tim), fp32"""
@@ -286,7 +236,7 @@ class Lxmert(nn.Module):
         return torch.matmul(text_embeds, image_embeds.t()) * self._P("logit_scale").exp()
 
 
-class MMEarly_Model(object):
+class MMEarly_Model(FlatTrainer):
     """reference models/mm_early.py:175-520, LXMERT branch: loss mixing :366-379, ITM sampling (same numpy stream as mm_late),
     AdamW over every parameter that received a gradient (the pooler never does: torch skips `grad is None`)."""
 
@@ -402,19 +352,12 @@ class MMEarly_Model(object):
                     src[idx] = j if j < idx else j + 1
         return src, labels
 
-    def load_saved_model(self, model_path):
-        self.model.load_state_dict(torch.load(model_path, map_location=self.device))
-
-    def save_model(self, model_path):
-        torch.save(self.model.state_dict(), model_path)
-
     def train(self, dataloader, val_dataloader, epochs, loss_fn=None, lr=1e-5, weight_decay=0.00025, tim_loss_fn=None, te_dataloader=None,
               model_path=None, val_filename=None, te_filename=None, class_weight=None, log_every=50):
         """reference :332-428 (LXMERT branch): epochs of train steps, validation / test metrics CSVs every even epoch and at the end,
         checkpoint = plain state_dict with the reference's keys"""
         import pandas as pd
-        if class_weight is None and loss_fn is not None and getattr(loss_fn, "weight", None) is not None:
-            class_weight = loss_fn.weight
+        class_weight = self._class_weight(loss_fn, class_weight)
         res_val, res_te, step = [], [], 0
         for epoch in range(epochs):
             if mmdist.rank() == 0:
@@ -443,8 +386,7 @@ class MMEarly_Model(object):
     def eval(self, batches, loss_fn=None, tim_loss_fn=None, class_weight=None):
         """reference :430-520 for the LXMERT branch: eval-mode forward, loss mix with re-sampled ITM negatives, argmax"""
         m = self.model
-        if class_weight is None and loss_fn is not None and getattr(loss_fn, "weight", None) is not None:
-            class_weight = loss_fn.weight
+        class_weight = self._class_weight(loss_fn, class_weight)
         m.eval()
         preds, labels, ids_all, losses = [], [], [], []
         sq = lambda t: t.squeeze(1) if t.dim() == 3 else t
@@ -465,11 +407,6 @@ class MMEarly_Model(object):
         return {"data_id": torch.cat(ids_all).numpy() if ids_all else np.zeros(0, dtype=np.int64), "loss": float(np.mean(losses)),
                 "predictions": torch.cat(preds).numpy(), "labels": torch.cat(labels).numpy()}
 
-    def check_indices(self):
-        """the engine clamps token ids / token types into their tables and counts them (include/mmhip.h mmhip_early_set_index_counter): the
-        reference raises IndexError for such an index, so does this -- at the end of an epoch or an evaluation loop (synchronises)"""
-        n, seen = int(self.model._bad_index.item()), getattr(self, "_bad_seen", 0)
-        if n > seen:
-            self._bad_seen = n
-            raise IndexError(f"index out of range in self: {n - seen} token id(s) / token type(s) outside their embedding tables reached the encoder; "
-                             "the engine clamped them to a valid row instead of following them")
+    def _clamped_message(self, n):
+        return (f"index out of range in self: {n} token id(s) / token type(s) outside their embedding tables reached the encoder; "
+                "the engine clamped them to a valid row instead of following them")

@@ -8,7 +8,6 @@
 There is no CPU / eager fallback: without the built library (or without a GPU) construction raises.
 """
 import ctypes as C
-import json
 import logging
 import math
 import os
@@ -20,6 +19,7 @@ import torch.nn as nn
 from . import _lib
 from . import dist as mmdist
 from .config import MODEL_DIR_DICT, TEXT_ARCH, IMAGE_ARCH, metric_names
+from .engine_module import FlatTrainer, WordTableEngineModule, _read_hf_dir, merge_ranges
 from .utils import agg_metrics_val
 
 logger = logging.getLogger(__name__)
@@ -37,10 +37,6 @@ class Scaled_Dot_Product_Attention(nn.Module):
         return torch.matmul(attention, V), scores
 
 
-class _Node(nn.Module):
-    """name-space node so that parameters carry the reference checkpoint's dotted keys"""
-
-
 def default_arch(txt_model_name, img_model_name):
     if txt_model_name not in TEXT_ARCH:
         raise ValueError(f"text model {txt_model_name!r}: late-fusion path supports {sorted(TEXT_ARCH)}")
@@ -51,22 +47,6 @@ def default_arch(txt_model_name, img_model_name):
     a.update(TEXT_ARCH[txt_model_name])
     a.update(IMAGE_ARCH[img_model_name])
     return a
-
-
-def _read_hf_dir(path):
-    """(config dict, state dict) of a local HuggingFace model directory, or (None, None)"""
-    cfg_file = os.path.join(path, "config.json")
-    if not os.path.isfile(cfg_file):
-        return None, None
-    with open(cfg_file) as f:
-        cfg = json.load(f)
-    sd = None
-    if os.path.isfile(os.path.join(path, "model.safetensors")):
-        from safetensors.torch import load_file
-        sd = load_file(os.path.join(path, "model.safetensors"))
-    elif os.path.isfile(os.path.join(path, "pytorch_model.bin")):
-        sd = torch.load(os.path.join(path, "pytorch_model.bin"), map_location="cpu")
-    return cfg, sd
 
 
 def _clip_key_to_ref(k):
@@ -109,7 +89,7 @@ class _MMFunction(torch.autograd.Function):
         return (None,) * 6 + tuple(grads)
 
 
-class MM_Model(nn.Module):
+class MM_Model(WordTableEngineModule):
     """reference models/mm_late.py:50-193.
 
     MM_Model(num_labels, txt_model_name, img_model_name, dropout, fusion_name='concat'); keyword-only extras are
@@ -121,6 +101,10 @@ class MM_Model(nn.Module):
     Weights: loaded from the local directories of config.MODEL_DIR_DICT when they exist (HF layout), else random
     init at the architecture's true shapes (no network in this environment).
     """
+
+    _ABI = dict(create="mmhip_create", destroy="mmhip_destroy", param_count="mmhip_param_count", param_info_at="mmhip_param_info_at",
+                workspace_bytes="mmhip_workspace_bytes", num_stages="mmhip_num_backward_stages", stage_grad_range="mmhip_stage_grad_range")
+    _embeddings = ("dual_encoder", "text_model", "embeddings")
 
     def __init__(self, num_labels, txt_model_name, img_model_name, dropout, fusion_name="concat", *, arch=None,
                  dtype="bf16", max_posts=64, max_text_len=128, device=None, seed=0, backward_products=None, itc_global=False):
@@ -170,14 +154,8 @@ class MM_Model(nn.Module):
                             img_kind=_lib.IMG_CLIP if a["img_kind"] == "clip" else _lib.IMG_VIT, hidden_img=int(a["hidden_img"]),
                             heads_img=int(a["heads_img"]), inter_img=int(a["inter_img"]),
                             dtype={"bf16": _lib.BF16, "f16": _lib.F16, "bf16x3": _lib.BF16X3}[dtype])
-        self._handle = None
-        self._capacity = (0, 0)
-        self._fwd_token = 0
-        self._seed_base = int(seed) if seed is not None else int(torch.initial_seed())
-        self._calls = 0
-        self._ws = None
-        self._last = {}
-        self._create_engine(max_posts, max_text_len, first=True)
+        self._init_engine(int(seed) if seed is not None else int(torch.initial_seed()))
+        self._create_engine(max_posts, max_text_len)
         self._init_weights()
         if txt_sd is not None:
             self._load_tower(txt_sd, "dual_encoder.text_model.", lambda k: k)
@@ -186,93 +164,34 @@ class MM_Model(nn.Module):
         self._refresh_weights(3)
 
     # ------------------------------------------------------------------ engine / buffers
-    def _create_engine(self, max_posts, max_text_len, first=False):
-        lib = _lib.lib()
-        cfg = _lib.Config(max_posts=int(max_posts), max_text_len=int(max_text_len), **self._cfg_kw)
-        h = C.c_void_p()
-        _lib.check(lib.mmhip_create(C.byref(cfg), C.byref(h)), "create")
-        if self._handle is not None:
-            lib.mmhip_destroy(self._handle)
-        self._handle = h
-        self._capacity = (int(max_posts), int(max_text_len))
-        dev = self.device_
-        if first:
-            n_frozen, n_train = lib.mmhip_buffer_numel(h, 0), lib.mmhip_buffer_numel(h, 1)
-            self._flat_frozen = torch.zeros(n_frozen, dtype=torch.float32, device=dev)
-            self._flat_train = torch.zeros(n_train, dtype=torch.float32, device=dev)
-            self._flat_grad = torch.zeros(n_train, dtype=torch.float32, device=dev)
-            self._infos = []
-            pi = _lib.ParamInfo()
-            for i in range(lib.mmhip_param_count(h)):
-                _lib.check(lib.mmhip_param_info_at(h, i, C.byref(pi)), "param_info")
-                self._infos.append(dict(name=pi.name.decode(), shape=tuple(pi.dims[: pi.ndim]), buffer=pi.buffer, group=pi.group,
-                                        offset=int(pi.offset), numel=int(pi.numel)))
-            self._register_parameters()
-            # word-table row flags shared by the backward pass and the row-lazy AdamW (include/mmhip.h: mmhip_adamw_rows)
-            self._word_info = next(i for i in self._train_params if i["name"].endswith("word_embeddings.weight"))
-            self._word_row_state = torch.zeros((self._word_info["shape"][0] + 3) // 4 * 4, dtype=torch.uint8, device=dev)
-        _lib.check(lib.mmhip_set_row_state(h, _lib.ptr(self._word_row_state)), "set_row_state")
-        if first:
-            # device words of this handle: [0:2] include/mmhip.h mmhip_set_guard {non-finite counter, void-step flag}; [2] mmhip_set_index_counter
-            # (token ids that had to be clamped into the word table: the reference raises IndexError for them)
-            self._guard4 = torch.zeros(4, dtype=torch.int32, device=dev)
-            self._nonfinite = self._guard4[:2]
-            self._bad_index = self._guard4[2:3]
-            self._loss_scale = 0.0
-        _lib.check(lib.mmhip_set_guard(h, _lib.ptr(self._nonfinite)), "set_guard")
-        _lib.check(lib.mmhip_set_index_counter(h, _lib.ptr(self._bad_index)), "set_index_counter")
-        if self._loss_scale > 0:
-            _lib.check(lib.mmhip_set_loss_scale(h, self._loss_scale), "set_loss_scale")
-        if self.backward_products is not None:
-            _lib.check(lib.mmhip_set_backward_products(h, self.backward_products), "set_backward_products")
-        self._ws = None
-        torch.cuda.empty_cache()
+    def _config(self, max_posts, max_text_len):
+        return _lib.Config(max_posts=int(max_posts), max_text_len=int(max_text_len), **self._cfg_kw)
+
+    def _allocate_flats(self, h):
+        lib, dev = _lib.lib(), self.device_
+        n_frozen, n_train = lib.mmhip_buffer_numel(h, 0), lib.mmhip_buffer_numel(h, 1)
+        self._flat_frozen = torch.zeros(n_frozen, dtype=torch.float32, device=dev)
+        self._flat_train = torch.zeros(n_train, dtype=torch.float32, device=dev)
+        self._flat_grad = torch.zeros(n_train, dtype=torch.float32, device=dev)
+        return {0: self._flat_frozen, 1: self._flat_train}
+
+    def _on_registered(self):
+        super()._on_registered()
+        self._train_params = [i for i in self._infos if i["buffer"] == 1]
+
+    def _before_workspace(self, h):
         # global-batch ITC: the gathered [world * max_posts, proj_dim] rows live in the workspace (reserved before it is sized; nothing at world 1)
-        itc_world = mmdist.world_size() if self.itc_global else 1
-        if itc_world > 1:
-            _lib.check(lib.mmhip_reserve_itc_global(h, itc_world), "reserve_itc_global")
-        self._ws = torch.empty(lib.mmhip_workspace_bytes(h), dtype=torch.uint8, device=dev)
-        if os.environ.get("MMHIP_POISON_WS"):       # debugging aid: no kernel may read workspace it has not written
-            self._ws.fill_(int(os.environ["MMHIP_POISON_WS"], 0))
+        self._itc_world = mmdist.world_size() if self.itc_global else 1
+        if self._itc_world > 1:
+            _lib.check(_lib.lib().mmhip_reserve_itc_global(h, self._itc_world), "reserve_itc_global")
+
+    def _bind(self, h):
+        lib = _lib.lib()
         _lib.check(lib.mmhip_bind(h, _lib.ptr(self._flat_frozen), _lib.ptr(self._flat_train), _lib.ptr(self._flat_grad),
                                   _lib.ptr(self._ws), self._ws.numel()), "bind")
-        self.itc_global_active = itc_world > 1
-        if itc_world > 1:
-            _lib.check(lib.mmhip_set_itc_global(h, itc_world, mmdist.rank()), "set_itc_global")
-        self._stage_ranges = []
-        b, e = C.c_uint64(), C.c_uint64()
-        for st in range(lib.mmhip_num_backward_stages(h)):
-            _lib.check(lib.mmhip_stage_grad_range(h, st, C.byref(b), C.byref(e)), "stage_grad_range")
-            self._stage_ranges.append((int(b.value), int(e.value)))
-        self._weights_version = None
-
-    def _register_parameters(self):
-        """nn.Parameters are views into the flat fp32 buffers, registered under the reference checkpoint's keys."""
-        self._train_params = []
-        for inf in self._infos:
-            flat = self._flat_frozen if inf["buffer"] == 0 else self._flat_train
-            view = flat[inf["offset"]: inf["offset"] + inf["numel"]].view(inf["shape"])
-            p = nn.Parameter(view, requires_grad=inf["buffer"] == 1)     # 'vision' parameters frozen, mm_late.py:67-69
-            node = self
-            parts = inf["name"].split(".")
-            for part in parts[:-1]:
-                if part not in node._modules:
-                    node.add_module(part, _Node())
-                node = node._modules[part]
-            node.register_parameter(parts[-1], p)
-            inf["param"] = p
-            if inf["buffer"] == 1:
-                self._train_params.append(inf)
-        # transformers 4.25.1 checkpoints carry this buffer (SURVEY.md 8b)
-        emb = self._modules["dual_encoder"]._modules["text_model"]._modules["embeddings"]
-        emb.register_buffer("position_ids", torch.arange(self.arch["max_pos"], device=self.device_).unsqueeze(0))
-
-    def __del__(self):
-        try:
-            if self._handle is not None:
-                _lib.lib().mmhip_destroy(self._handle)
-        except Exception:
-            pass
+        self.itc_global_active = self._itc_world > 1
+        if self._itc_world > 1:
+            _lib.check(lib.mmhip_set_itc_global(h, self._itc_world, mmdist.rank()), "set_itc_global")
 
     def _init_weights(self):
         """HF initializer_range 0.02 for the towers, nn.Linear defaults for the heads (reference: from_pretrained + nn.Linear)."""
@@ -369,8 +288,7 @@ class MM_Model(nn.Module):
             tim_ids = tim_ids.to(dev, torch.int64).contiguous()
             tim_mask = tim_mask.to(dev, torch.int64).contiguous()
         if seed is None:
-            self._calls += 1
-            seed = (self._seed_base * 0x9E3779B97F4A7C15 + self._calls) & 0xFFFFFFFFFFFFFFFF
+            seed = self._next_seed()
         out_cls = torch.empty(B, self.num_labels, device=dev)
         lpt = torch.empty(B, B, device=dev)
         out_tim = torch.empty(B, 2, device=dev) if tim_ids is not None else None
@@ -409,20 +327,12 @@ class MM_Model(nn.Module):
     def active_ranges(self, use_itc, use_itm):
         """merged [begin, end) element ranges of the trainable flat buffer that receive gradients"""
         groups = self.active_groups(use_itc, use_itm)
-        spans = sorted((i["offset"], i["offset"] + ((i["numel"] + 3) & ~3)) for i in self._train_params if i["group"] in groups)
-        out = []
-        for b, e in spans:
-            if out and out[-1][1] == b:
-                out[-1][1] = e
-            else:
-                out.append([b, e])
-        return [tuple(x) for x in out]
+        return merge_ranges((i["offset"], i["numel"]) for i in self._train_params if i["group"] in groups)
 
     def _engine_backward_autograd(self, d_cls, d_lpt, d_tim, d_feats):
         B = self._last["B"]
         dev = self.device_
-        self._flat_grad.zero_()
-        self._word_row_state.bitwise_and_(0xFE)
+        self._zero_grad_state()
         f = lambda t: None if t is None else t.to(dev, torch.float32).contiguous()
         d_cls = f(d_cls) if d_cls is not None else torch.zeros(B, self.num_labels, device=dev)
         d_lpt, d_tim, d_feats = f(d_lpt), f(d_tim), f(d_feats)
@@ -435,16 +345,8 @@ class MM_Model(nn.Module):
                 out.append(self._flat_grad[inf["offset"]: inf["offset"] + inf["numel"]].view(inf["shape"]).clone())
             else:
                 out.append(None)
-        # _flat_grad keeps this call's gradient (tests and callers inspect it); the fused step re-establishes the entry condition
-        # of include/mmhip.h's backward contract (zero gradient, no "row has a gradient" flags) when it finds this mark
-        self._grad_dirty = True
+        self._grad_dirty = True          # _flat_grad keeps this call's gradient until the fused step's _clean_grad
         return out
-
-    def _clean_grad(self):
-        if getattr(self, "_grad_dirty", False):
-            self._flat_grad.zero_()
-            self._word_row_state.bitwise_and_(0xFE)
-            self._grad_dirty = False
 
     # ------------------------------------------------------------------ reference interface
     def forward(self, ids, mask, pixel_values, tim_inputs=None, iadds_task=False):
@@ -465,7 +367,7 @@ class MM_Model(nn.Module):
 
 
 # =====================================================================================================================
-class MMLate_Model(object):
+class MMLate_Model(FlatTrainer):
     """reference models/mm_late.py:298-739 (late-fusion branch).  `train()`/`eval()` keep the reference's semantics
     (loss mixing :473-487, ITM sampling :389-414 with the same numpy RNG call order, metrics CSVs every even epoch);
     the step itself is fused: engine loss + backward + AdamW over flat buffers, gradients all-reduced per backward stage
@@ -490,13 +392,6 @@ class MMLate_Model(object):
         # MMHIP_DP_OPT=shard: reduce-scatter -> sharded AdamW -> all-gather for the dense ranges instead of all-reduce + replicated AdamW (dist.ShardedBuckets)
         self.sharded_optimizer = os.environ.get("MMHIP_DP_OPT", "allreduce") == "shard"
         self.image_processor = None          # GpuImageProcessor when the loaders yield raw images (datasets.py)
-
-    # ---- checkpoints (reference :343-345, :529-531): plain state_dict with the reference's keys
-    def load_saved_model(self, model_path):
-        self.model.load_state_dict(torch.load(model_path, map_location=self.device))
-
-    def save_model(self, model_path):
-        torch.save(self.model.state_dict(), model_path)
 
     # ---- ITM negative sampling, reference :389-414 (same numpy RNG stream: one choice([True, False]) per row and one
     # choice(list(others)) per swapped row; sources are read from the original ids, so swaps do not chain)
@@ -622,13 +517,6 @@ class MMLate_Model(object):
             m._flat_train.copy_(before)
             m._refresh_weights(2)
 
-    def _moments(self):
-        m = self.model
-        if self._opt is None:
-            self._opt = (torch.zeros_like(m._flat_train), torch.zeros_like(m._flat_train))
-            m._word_row_state.bitwise_and_(1)                      # fresh moments: no row has any yet
-        return self._opt
-
     def _native_step(self, ids, mask, pixels, tim_ids, tim_mask, lbl_tim, onehot, cw, lr, weight_decay, step, loss, ncorr, exchange=False):
         m = self.model
         dev = self.device
@@ -641,8 +529,7 @@ class MMLate_Model(object):
         m._ensure(B, T)
         sharded = exchange and self.sharded_optimizer
         em, ev = self._row_moments() if sharded else self._moments()
-        m._calls += 1
-        seed = (m._seed_base * 0x9E3779B97F4A7C15 + m._calls) & 0xFFFFFFFFFFFFFFFF
+        seed = m._next_seed()
         w_cls, w_itc, w_itm = self.loss_weights()
         if tim_ids is not None:
             tim_ids = tim_ids.to(dev, torch.int64).contiguous()
@@ -757,21 +644,7 @@ class MMLate_Model(object):
         buckets.gather_params(m._flat_train, plan)
 
     def _adamw(self, lr, weight_decay, step, dense=True, rows=True):
-        m, lib = self.model, _lib.lib()
-        em, ev = self._moments()
-        at = lambda t, el: C.c_void_p(t.data_ptr() + el * 4)
-        V, H = m._word_info["shape"]
-        w0 = m._word_info["offset"]                                 # the word table closes the trainable buffer
-        for b, e in m.active_ranges(self.use_clip_loss, self.use_tim_loss):
-            dense_end = min(e, w0)
-            if dense and dense_end > b:
-                _lib.check(lib.mmhip_adamw_guarded(at(m._flat_train, b), at(m._flat_grad, b), at(em, b), at(ev, b), dense_end - b, lr, 0.9, 0.999,
-                                                   1e-8, weight_decay, step, 1.0 / self.world, 1, _lib.stream_ptr(), _lib.ptr(m._nonfinite)), "adamw")
-            if rows and e > w0:
-                # rows without gradient and without moments only decay: same values as the dense update, 1/4 of its traffic
-                _lib.check(lib.mmhip_adamw_rows_guarded(at(m._flat_train, w0), at(m._flat_grad, w0), at(em, w0), at(ev, w0), V, H,
-                                                        _lib.ptr(m._word_row_state), lr, 0.9, 0.999, 1e-8, weight_decay, step,
-                                                        1.0 / self.world, 1, _lib.stream_ptr(), _lib.ptr(m._nonfinite)), "adamw_rows")
+        self._adamw_ranges(self.model.active_ranges(self.use_clip_loss, self.use_tim_loss), lr, weight_decay, step, 1.0 / self.world, dense, rows)
 
     # ---- overflow guard, host side.  The device skips a void step by itself (include/mmhip.h: mmhip_set_step_guard); the host only adapts
     # the f16 loss scale, from a pinned copy of the counter taken at the end of the previous step -- no synchronisation in the step loop.
@@ -824,18 +697,10 @@ class MMLate_Model(object):
         _lib.check(_lib.lib().mmhip_set_loss_scale(m._handle, m._loss_scale), "set_loss_scale")
         logger.warning("f16 gradient overflow (%d sightings; the steps were skipped on the device): loss scale %g -> %g", n, cur, m._loss_scale)
 
-    def _raise_on_clamped_indices(self, count):
-        """token ids outside [0, vocab) were clamped by the engine (include/mmhip.h mmhip_set_index_counter): the reference's nn.Embedding raises
-        IndexError for them -- so does this, one step late (the count comes from the pinned copy of the guard words) or at the end of a loop"""
-        seen = getattr(self, "_bad_seen", 0)
-        if count > seen:
-            self._bad_seen = count
-            raise IndexError(f"index out of range in self: {count - seen} token id(s) outside [0, {self.model.arch['vocab']}) reached the text tower "
-                             "(a tokenizer that does not match the checkpoint?); the engine clamped them to a valid row instead of following them")
-
-    def check_indices(self):
-        """synchronising form of the check above (end of an evaluation / feature loop)"""
-        self._raise_on_clamped_indices(int(self.model._bad_index.item()))
+    def _clamped_message(self, n):
+        """(the trainer raises one step late -- the count comes from the pinned copy of the guard words -- or at the end of a loop)"""
+        return (f"index out of range in self: {n} token id(s) outside [0, {self.model.arch['vocab']}) reached the text tower "
+                "(a tokenizer that does not match the checkpoint?); the engine clamped them to a valid row instead of following them")
 
     def check_overflow(self):
         """non-finite gradient elements since the last call (the AdamW kernels skipped and counted them, include/mmhip.h).
@@ -872,8 +737,7 @@ class MMLate_Model(object):
         """reference :416-532.  `loss_fn` is accepted for signature parity; the class weights it would carry are passed
         as `class_weight` (nn.CrossEntropyLoss(weight=w), run_mm_late.py:85)."""
         import pandas as pd
-        if class_weight is None and loss_fn is not None and getattr(loss_fn, "weight", None) is not None:
-            class_weight = loss_fn.weight
+        class_weight = self._class_weight(loss_fn, class_weight)
         res_val, res_te, step = [], [], 0
         # MMHIP_EPOCH_PREFETCH=1 (datasets.loaders_from_data_key hangs a twin loader on the training loader): epochs alternate between the two
         # loaders and the next epoch's loader is primed -- iterator created, its workers decoding -- once this epoch's workers have been handed
@@ -922,8 +786,7 @@ class MMLate_Model(object):
     def eval(self, dataloader, loss_fn=None, tim_loss_fn=None, iadds_loss_fn=None, class_weight=None):
         """reference :534-638: forward without dropout, same loss mix (ITM inputs re-sampled, :565-568), argmax."""
         m, lib = self.model, _lib.lib()
-        if class_weight is None and loss_fn is not None and getattr(loss_fn, "weight", None) is not None:
-            class_weight = loss_fn.weight
+        class_weight = self._class_weight(loss_fn, class_weight)
         m.eval()
         ids_all, preds, labels, losses = [], [], [], []
         w_cls, w_itc, w_itm = self.loss_weights()

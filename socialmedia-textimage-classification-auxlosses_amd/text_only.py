@@ -9,19 +9,17 @@ The reference classifies last_hidden[:, 0, :]; the encoder's pooler is computed 
 keys), never computed here, receive no gradient and no optimizer step -- what torch does with `grad is None`.
 There is no CPU / eager fallback: without the built library (or without a GPU) construction raises.
 """
-import ctypes as C
 import logging
 import math
 import os
 
 import numpy as np
 import torch
-import torch.nn as nn
 
 from . import _lib
 from . import dist as mmdist
 from .config import MODEL_DIR_DICT, TEXT_ARCH, metric_names
-from .mm_late import _Node, _read_hf_dir
+from .engine_module import FlatTrainer, WordTableEngineModule, _read_hf_dir, merge_ranges
 from .utils import agg_metrics_val
 
 logger = logging.getLogger(__name__)
@@ -50,12 +48,16 @@ class _TxtFunction(torch.autograd.Function):
         return (None,) * 4 + tuple(model._engine_backward_autograd(d_logits))
 
 
-class _TextOnly(nn.Module):
+class _TextOnly(WordTableEngineModule):
     """shared body of BERT and BERNICE.  Keyword-only extras are additive, as in MM_Model: `arch` overrides (layer count, vocab ... for tests),
     `arch_name` (the TEXT_ARCH preset when model_dir holds no checkpoint), `dtype` ('bf16' | 'f16' | 'bf16x3'), `max_posts` / `max_text_len`
     (capacity), `device`, `seed`, `backward_products` (bf16x3 only)."""
 
     _default_arch_name = "bernice"
+    # a text-only handle is an mmhip_handle: the stage ranges of the late-fusion family are read through its entry points (include/mmhip.h)
+    _ABI = dict(create="mmhip_txt_create", destroy="mmhip_txt_destroy", param_count="mmhip_txt_param_count", param_info_at="mmhip_txt_param_info_at",
+                workspace_bytes="mmhip_txt_workspace_bytes", num_stages="mmhip_num_backward_stages", stage_grad_range="mmhip_stage_grad_range")
+    _embeddings = ("bert_model", "embeddings")
 
     def __init__(self, model_dir, num_labels, dropout=0.1, *, arch=None, arch_name=None, dtype="bf16", max_posts=64, max_text_len=128,
                  device=None, seed=0, backward_products=None):
@@ -80,78 +82,25 @@ class _TextOnly(nn.Module):
                             type_vocab=a["type_vocab"], txt_kind=_lib.TXT_XLMR if a["txt_kind"] == "xlmr" else _lib.TXT_BERT, pad_id=a["pad_id"],
                             ln_eps=a["ln_eps_txt"], num_labels=self.num_labels, p_hidden=a["p_hidden"], p_attn=a["p_attn"], p_head=float(dropout),
                             dtype={"bf16": _lib.BF16, "f16": _lib.F16, "bf16x3": _lib.BF16X3}[dtype])
-        self._handle, self._capacity, self._fwd_token = None, (0, 0), 0
-        self._seed_base = int(seed) if seed is not None else int(torch.initial_seed())
-        self._calls, self._ws, self._last, self._grad_dirty = 0, None, {}, False
-        self._create_engine(max_posts, max_text_len, first=True)
+        self._init_engine(int(seed) if seed is not None else int(torch.initial_seed()))
+        self._create_engine(max_posts, max_text_len)
         self._init_weights()
         if sd is not None:
             self._load_tower(sd)
         self._refresh_weights()
 
     # ------------------------------------------------------------------ engine / buffers
-    def _create_engine(self, max_posts, max_text_len, first=False):
-        lib = _lib.lib()
-        cfg = _lib.TxtConfig(max_posts=int(max_posts), max_text_len=int(max_text_len), loss_scale=float(getattr(self, "_loss_scale", 0.0)), **self._cfg_kw)
-        h = C.c_void_p()
-        _lib.check(lib.mmhip_txt_create(C.byref(cfg), C.byref(h)), "txt_create")
-        if self._handle is not None:
-            lib.mmhip_txt_destroy(self._handle)
-        self._handle = h
-        self._capacity = (int(max_posts), int(max_text_len))
-        dev = self.device_
-        if first:
-            n = lib.mmhip_txt_numel(h)
-            self._flat_train = torch.zeros(n, dtype=torch.float32, device=dev)
-            self._flat_grad = torch.zeros(n, dtype=torch.float32, device=dev)
-            self._infos = []
-            pi = _lib.ParamInfo()
-            for i in range(lib.mmhip_txt_param_count(h)):
-                _lib.check(lib.mmhip_txt_param_info_at(h, i, C.byref(pi)), "txt_param_info")
-                self._infos.append(dict(name=pi.name.decode(), shape=tuple(pi.dims[: pi.ndim]), group=pi.group, offset=int(pi.offset), numel=int(pi.numel)))
-            self._register_parameters()
-            self._word_info = next(i for i in self._infos if i["name"].endswith("word_embeddings.weight"))
-            self._word_row_state = torch.zeros((self._word_info["shape"][0] + 3) // 4 * 4, dtype=torch.uint8, device=dev)
-            # device words of this handle: [0:2] {non-finite counter, void-step flag}, [2] clamped token ids (include/mmhip.h)
-            self._guard4 = torch.zeros(4, dtype=torch.int32, device=dev)
-            self._nonfinite, self._bad_index = self._guard4[:2], self._guard4[2:3]
-            self._loss_scale = 0.0
-        # a text-only handle is an mmhip_handle: the per-handle setters of the late-fusion family take it (include/mmhip.h)
-        _lib.check(lib.mmhip_set_row_state(h, _lib.ptr(self._word_row_state)), "set_row_state")
-        _lib.check(lib.mmhip_set_guard(h, _lib.ptr(self._nonfinite)), "set_guard")
-        _lib.check(lib.mmhip_set_index_counter(h, _lib.ptr(self._bad_index)), "set_index_counter")
-        if self.backward_products is not None:
-            _lib.check(lib.mmhip_set_backward_products(h, self.backward_products), "set_backward_products")
-        self._ws = None
-        torch.cuda.empty_cache()
-        self._ws = torch.empty(lib.mmhip_txt_workspace_bytes(h), dtype=torch.uint8, device=dev)
-        if os.environ.get("MMHIP_POISON_WS"):       # debugging aid: no kernel may read workspace it has not written
-            self._ws.fill_(int(os.environ["MMHIP_POISON_WS"], 0))
-        _lib.check(lib.mmhip_txt_bind(h, _lib.ptr(self._flat_train), _lib.ptr(self._flat_grad), _lib.ptr(self._ws), self._ws.numel()), "txt_bind")
-        self._weights_version = None
+    def _config(self, max_posts, max_text_len):
+        return _lib.TxtConfig(max_posts=int(max_posts), max_text_len=int(max_text_len), loss_scale=float(getattr(self, "_loss_scale", 0.0)), **self._cfg_kw)
 
-    def _register_parameters(self):
-        """nn.Parameters are views into the flat fp32 buffer, registered under the reference checkpoint's keys"""
-        for inf in self._infos:
-            view = self._flat_train[inf["offset"]: inf["offset"] + inf["numel"]].view(inf["shape"])
-            p = nn.Parameter(view, requires_grad=True)
-            node, parts = self, inf["name"].split(".")
-            for part in parts[:-1]:
-                if part not in node._modules:
-                    node.add_module(part, _Node())
-                node = node._modules[part]
-            node.register_parameter(parts[-1], p)
-            inf["param"] = p
-        # transformers 4.25.1 checkpoints carry this buffer (the naming the late path uses)
-        emb = self._modules["bert_model"]._modules["embeddings"]
-        emb.register_buffer("position_ids", torch.arange(self.arch["max_pos"], device=self.device_).unsqueeze(0))
+    def _allocate_flats(self, h):
+        n = _lib.lib().mmhip_txt_numel(h)
+        self._flat_train = torch.zeros(n, dtype=torch.float32, device=self.device_)
+        self._flat_grad = torch.zeros(n, dtype=torch.float32, device=self.device_)
+        return {1: self._flat_train}
 
-    def __del__(self):
-        try:
-            if self._handle is not None:
-                _lib.lib().mmhip_txt_destroy(self._handle)
-        except Exception:
-            pass
+    def _bind(self, h):
+        _lib.check(_lib.lib().mmhip_txt_bind(h, _lib.ptr(self._flat_train), _lib.ptr(self._flat_grad), _lib.ptr(self._ws), self._ws.numel()), "txt_bind")
 
     def _init_weights(self):
         """HF initializer_range 0.02 for the encoder, nn.Linear defaults for the classifier (reference: from_pretrained + nn.Linear)"""
@@ -193,10 +142,6 @@ class _TextOnly(nn.Module):
         elif self._weights_version != self._flat_train._version:
             self._refresh_weights()        # parameters were modified in place (optimizer.step / load_state_dict)
 
-    def _next_seed(self):
-        self._calls += 1
-        return (self._seed_base * 0x9E3779B97F4A7C15 + self._calls) & 0xFFFFFFFFFFFFFFFF
-
     def _inputs(self, ids, mask, type_ids):
         dev = self.device_
         ids = ids.to(dev, torch.int64).contiguous()
@@ -227,24 +172,11 @@ class _TextOnly(nn.Module):
 
     def active_ranges(self):
         """merged [begin, end) element ranges of the flat buffer that AdamW steps"""
-        out = []
-        for b, e in sorted((i["offset"], i["offset"] + ((i["numel"] + 3) & ~3)) for i in self.trainable_infos()):
-            if out and out[-1][1] == b:
-                out[-1][1] = e
-            else:
-                out.append([b, e])
-        return [tuple(x) for x in out]
-
-    def _clean_grad(self):
-        if self._grad_dirty:
-            self._flat_grad.zero_()
-            self._word_row_state.bitwise_and_(0xFE)
-            self._grad_dirty = False
+        return merge_ranges((i["offset"], i["numel"]) for i in self.trainable_infos())
 
     def _engine_backward(self, d_logits=None):
         """gradient of the last forward into the flat gradient buffer (cleared first); d_logits None: the one mmhip_txt_loss left in the handle"""
-        self._flat_grad.zero_()
-        self._word_row_state.bitwise_and_(0xFE)
+        self._zero_grad_state()
         if d_logits is not None:
             d_logits = d_logits.to(self.device_, torch.float32).contiguous()
         _lib.check(_lib.lib().mmhip_txt_backward(self._handle, _lib.ptr(d_logits), _lib.stream_ptr()), "txt_backward")
@@ -279,7 +211,7 @@ class BERT(_TextOnly):
 
 
 # =====================================================================================================================
-class TextModel(object):
+class TextModel(FlatTrainer):
     """reference models/text_only.py:68-268.  `train()` / `eval()` keep the reference's semantics and return dictionaries; the step is fused."""
 
     def __init__(self, config, model_name, freeze=False, **model_kw):
@@ -334,20 +266,6 @@ class TextModel(object):
         to = lambda t: t.to(self.device, non_blocking=True)
         return to(b["input_ids"]), to(b["attention_mask"]), (to(b["token_type_ids"]) if "token_type_ids" in b else None)
 
-    # ---- checkpoints: plain state_dict with the reference's keys
-    def load_saved_model(self, model_path):
-        self.model.load_state_dict(torch.load(model_path, map_location=self.device))
-
-    def save_model(self, model_path):
-        torch.save(self.model.state_dict(), model_path)
-
-    def _moments(self):
-        m = self.model
-        if self._opt is None:
-            self._opt = (torch.zeros_like(m._flat_train), torch.zeros_like(m._flat_train))
-            m._word_row_state.bitwise_and_(1)                      # fresh moments: no row has any yet
-        return self._opt
-
     # ---- one fused training step on device tensors -> (loss[1] device tensor, n_correct[1] device tensor)
     def train_step(self, ids, mask, token_type_ids, onehot, class_weight, lr, weight_decay, step, seed=None):
         m = self.model
@@ -377,7 +295,6 @@ class TextModel(object):
         if not m.training:
             m.train()
         m._clean_grad()
-        em, ev = self._moments()
         m._engine_forward(ids, mask, token_type_ids if self.with_types else None, seed=seed)
         onehot = onehot.to(self.device, torch.int64).contiguous()
         cw = None if class_weight is None else class_weight.to(self.device, torch.float32).contiguous()
@@ -385,29 +302,13 @@ class TextModel(object):
         ncorr = torch.empty(1, dtype=torch.int32, device=self.device)
         _lib.check(lib.mmhip_txt_loss(m._handle, _lib.ptr(onehot), _lib.ptr(cw), _lib.ptr(loss), _lib.ptr(ncorr), _lib.stream_ptr()), "txt_loss")
         m._engine_backward(None)
-        at = lambda t, el: C.c_void_p(t.data_ptr() + el * 4)
-        V, H = m._word_info["shape"]
-        w0 = m._word_info["offset"]                                 # the word table closes the buffer
-        for b, e in m.active_ranges():
-            dense_end = min(e, w0)
-            if dense_end > b:
-                _lib.check(lib.mmhip_adamw_guarded(at(m._flat_train, b), at(m._flat_grad, b), at(em, b), at(ev, b), dense_end - b, lr, 0.9, 0.999, 1e-8,
-                                                   weight_decay, step, 1.0, 1, _lib.stream_ptr(), _lib.ptr(m._nonfinite)), "adamw")
-            if e > w0:
-                _lib.check(lib.mmhip_adamw_rows_guarded(at(m._flat_train, w0), at(m._flat_grad, w0), at(em, w0), at(ev, w0), V, H,
-                                                        _lib.ptr(m._word_row_state), lr, 0.9, 0.999, 1e-8, weight_decay, step, 1.0, 1,
-                                                        _lib.stream_ptr(), _lib.ptr(m._nonfinite)), "adamw_rows")
+        self._adamw_ranges(m.active_ranges(), lr, weight_decay, step, 1.0)
         m._grad_dirty = False
         m._refresh_weights()
         return loss, ncorr
 
-    def check_indices(self):
-        """token ids outside [0, vocab) were clamped by the engine: the reference's nn.Embedding raises IndexError for them"""
-        n = int(self.model._bad_index.item())
-        seen = getattr(self, "_bad_seen", 0)
-        if n > seen:
-            self._bad_seen = n
-            raise IndexError(f"index out of range in self: {n - seen} token id(s) outside the embedding tables reached the text tower")
+    def _clamped_message(self, n):
+        return f"index out of range in self: {n} token id(s) outside the embedding tables reached the text tower"
 
     def check_overflow(self):
         n = int(self.model._nonfinite[0].item()) - getattr(self, "_nf_seen", 0)
@@ -417,12 +318,6 @@ class TextModel(object):
                 raise FloatingPointError(f"non-finite gradients met {n} times ({self.model.dtype_name}): the run has diverged")
             logger.warning("f16 gradient overflow: %d step(s) were skipped on the device", n)
         return max(n, 0)
-
-    @staticmethod
-    def _class_weight(loss_fn, class_weight):
-        if class_weight is None and loss_fn is not None and getattr(loss_fn, "weight", None) is not None:
-            return loss_fn.weight
-        return class_weight
 
     def train(self, dataloader, val_dataloader, epochs, loss_fn=None, lr=1e-5, weight_decay=0.00025, te_dataloader=None, model_path=None,
               val_filename=None, te_filename=None, class_weight=None, log_every=50):

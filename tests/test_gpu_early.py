@@ -329,6 +329,54 @@ def test_native_step_equals_the_autograd_path():
             assert not da[o:o + n_].any() and not db[o:o + n_].any(), name
 
 
+def test_capacity_growth_between_training_steps_leaves_no_trace():
+    """the engine is re-created WHILE TRAINING: trainer A is made for 2 posts x 16 tokens x 8 boxes and meets a 4 x 24 x 12 batch in its second
+    step, trainer B is made for it.  Same seed, weights, ITM draws and steps (dropout off, bf16x3, AdamW eps = 1e-2 as in
+    test_native_step_equals_the_autograd_path, whose bound for two paths over the same weights this takes): the parameter deltas agree to
+    1e-4 of the largest delta.  On the grown handle every .grad still is a slice of the flat gradient buffer, and a token id == vocab
+    reaches check_indices(): the index counter was attached to the new handle too."""
+    kw = dict(l_layers=1, r_layers=1, x_layers=1, vocab=300, max_pos=64)
+    arch = dict(kw, p_hidden=0.0, p_attn=0.0)
+    shapes = ((2, 16, 8), (4, 24, 12))
+    batches = [L.synthetic_batch(L.LxmertConfig(num_labels=3, n_boxes=nb, **kw), B, T, 40 + B) for B, T, nb in shapes]
+    P = L.make_params(L.LxmertConfig(num_labels=3, **kw), 2)
+    res, trainers = [], []
+    for cap_b, cap_t, cap_n in shapes:
+        cfg = types.SimpleNamespace(batch_size=cap_b, num_labels=3, use_clip_loss=True, beta_itc=0.1, use_tim_loss=True, beta_itm=0.1, max_length=cap_t,
+                                    dropout=0.0)
+        tr = MMEarly_Model(cfg, "lxmert", arch=arch, seed=3, dtype="bf16x3", max_posts=cap_b, max_boxes=cap_n)
+        tr.adam_eps = 1e-2
+        m = tr.model
+        missing, unexpected = m.load_state_dict(P, strict=False)
+        assert not missing and not unexpected and m._capacity == (cap_b, cap_t, cap_n)
+        p0 = m._flat.clone()
+        losses = []
+        for step, (ids, mask, tt, feats, boxes, onehot) in enumerate(batches, 1):
+            np.random.seed(50 + step)
+            losses.append(tr.train_step(ids, mask, tt, feats, boxes, onehot, None, 1e-3, 0.0, step).clone())
+        torch.cuda.synchronize()
+        assert m._capacity == shapes[1]
+        res.append((m._flat - p0, torch.stack(losses).cpu()))
+        trainers.append(tr)
+    (da, la), (db, lb) = res
+    scale, d = db.abs().max().item(), (da - db).abs().max().item()
+    print("early growth: delta diff", d, "scale", scale, "losses", la.tolist(), lb.tolist())
+    assert scale > 1e-6 and d < 1e-4 * scale + 2.5e-7, (d, scale)
+    assert torch.isfinite(la).all() and torch.isfinite(lb).all()
+    tr = trainers[0]
+    m = tr.model
+    g0, g1 = m._flat_grad.data_ptr(), m._flat_grad.data_ptr() + 4 * m._flat_grad.numel()
+    for k, p in m.named_parameters():
+        assert p.grad is not None and g0 <= p.grad.data_ptr() and p.grad.data_ptr() + 4 * p.grad.numel() <= g1, k
+    tr.check_indices()
+    ids, mask, tt, feats, boxes, onehot = batches[1]
+    bad = ids.clone()
+    bad[1, 1] = 300
+    tr.train_step(bad, mask, tt, feats, boxes, onehot, None, 1e-3, 0.0, 3)
+    with pytest.raises(IndexError):
+        tr.check_indices()
+
+
 def test_full_size_step_properties():
     """BASELINE config 5 at full size (9 + 5 + 5 layers, bs 32, T = 128, 36 x 2048 ROI features, ITC + ITM, dropout on): finite decreasing loss over
     a few steps, the pooler untouched, replicas of the same seed bit-identical in the deterministic kernels' outputs (forward), every gradient range

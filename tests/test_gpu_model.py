@@ -895,6 +895,47 @@ def test_capacity_growth_param_updates_and_errors():
     assert not torch.equal(a, b)
 
 
+def test_capacity_growth_between_training_steps_leaves_no_trace(monkeypatch):
+    """the engine is re-created WHILE TRAINING: trainer A is made at capacity (2, 16) and meets a (4, 32) batch in its second step, trainer B is
+    made at (4, 32).  Same seed, same loaded weights, same two steps, MMHIP_DETERMINISTIC=1: parameters, both moments, the word-table row
+    flags and the losses are bit-identical -- the new handle got the row flags, guard words, moments and 16-bit operand copies of the old one.
+    Then a token id == vocab on the grown handle must reach check_indices(): the index counter was attached to the new handle too."""
+    import types
+    monkeypatch.setenv("MMHIP_DETERMINISTIC", "1")
+    ocfg = O.OracleConfig(layers_txt=2, layers_img=1, vocab=3000, max_pos=130, num_labels=3)
+    arch = dict(layers_txt=2, layers_img=1, vocab=3000, max_pos=130)
+    P = O.make_params(ocfg, 5)
+    batches = [O.synthetic_batch(ocfg, B, T, 200 + B, True) for B, T in ((2, 16), (4, 32))]
+    res, trainers = [], []
+    for cap_b, cap_t in ((2, 16), (4, 32)):
+        cfgd = types.SimpleNamespace(batch_size=cap_b, num_labels=3, use_clip_loss=True, beta_itc=0.1, use_tim_loss=True, beta_itm=0.1,
+                                     max_length=cap_t, dropout=0.05)
+        tr = MMLate_Model(cfgd, "bernice", "vit", "attention", arch=arch, seed=3)
+        load_oracle_params(tr.model, P)
+        assert tr.model._capacity == (cap_b, cap_t)
+        losses = []
+        for step, (ids, mask, pixels, onehot) in enumerate(batches, 1):
+            np.random.seed(30 + step)                # the ITM sampling draws from numpy's global stream
+            loss, _ = tr.train_step(ids.cuda(), mask.cuda(), pixels, onehot, None, 1e-3, 0.01, step)
+            losses.append(loss.clone())
+        torch.cuda.synchronize()
+        assert tr.model._capacity == (4, 32)
+        res.append((tr.model._flat_train.clone(), tr._opt[0].clone(), tr._opt[1].clone(), tr.model._word_row_state.clone(), torch.stack(losses).cpu()))
+        trainers.append(tr)
+    for name, x, y in zip(("flat_train", "adam_m", "adam_v", "row_state", "losses"), res[0], res[1]):
+        assert torch.equal(x, y), (name, (x.float() - y.float()).abs().max().item())
+    assert res[0][0].isfinite().all() and float(res[0][4][-1][0]) > 0 and int(res[0][3].sum()) > 0
+    tr = trainers[0]
+    tr.check_indices()
+    ids, mask, pixels, onehot = batches[1]
+    bad = ids.clone()
+    bad[1, 2] = 3000
+    np.random.seed(33)
+    tr.train_step(bad.cuda(), mask.cuda(), pixels, onehot, None, 1e-3, 0.01, 3)
+    with pytest.raises(IndexError):
+        tr.check_indices()
+
+
 def test_full_size_backward_is_the_mean_of_half_batches():
     """BASELINE size (12+12 layers, V=250002, T=128): without ITC/ITM posts are independent, so the gradient of the mean loss
     over 64 posts equals the mean of the gradients over its two halves (dropout off).  Exercises every backward kernel at

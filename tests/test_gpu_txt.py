@@ -296,6 +296,42 @@ def test_fused_step_is_the_staged_step(kind, dtype, monkeypatch):
                            torch.zeros(4096, device=DEV))
 
 
+def test_capacity_growth_between_training_steps_leaves_no_trace(monkeypatch):
+    """the handle is re-created WHILE TRAINING: trainer A is made at capacity (2, 16) and meets a (4, 32) batch in its second step, trainer B is made
+    at (4, 32).  Same seed, weights and steps, MMHIP_DETERMINISTIC=1: parameters, both moments, the row flags and the losses are bit-identical.
+    Then a token id == vocab on the grown handle reaches check_indices(): the index counter was attached to the new handle too."""
+    from smtc_amd.text_only import TextModel
+    monkeypatch.setenv("MMHIP_DETERMINISTIC", "1")
+    batches = [_case("xlmr", 2, 16, 8), _case("xlmr")]
+    cfg = batches[1]["cfg"]
+    name, a = KINDS["xlmr"]
+    res, trainers = [], []
+    for cap_b, cap_t in ((2, 16), (4, 32)):
+        class Cfg:
+            batch_size, num_labels, max_length, dropout, use_loss_correction = cap_b, 3, cap_t, 0.1, False
+        tm = TextModel(Cfg, name, arch=dict(a, layers=2, vocab=500), dtype="bf16", device=DEV, seed=3)
+        tm.model.load_state_dict(batches[1]["P"], strict=False)
+        assert cfg.layers_txt == 2 and cfg.vocab == 500 and tm.model._capacity == (cap_b, cap_t)
+        losses = []
+        for st, c in enumerate(batches, 1):
+            loss, _ = tm.train_step(c["ids"], c["mask"], c["tt"], c["onehot"], c["w"], 1e-3, 0.01, st)
+            losses.append(loss.clone())
+        torch.cuda.synchronize()
+        assert tm.model._capacity == (4, 32)
+        res.append((tm.model._flat_train.clone(), tm._opt[0].clone(), tm._opt[1].clone(), tm.model._word_row_state.clone(), torch.cat(losses).cpu()))
+        trainers.append(tm)
+    for what, x, y in zip(("flat_train", "adam_m", "adam_v", "row_state", "losses"), res[0], res[1]):
+        assert torch.equal(x, y), (what, (x.float() - y.float()).abs().max().item())
+    assert res[0][0].isfinite().all() and float(res[0][4][-1]) > 0 and int(res[0][3].sum()) > 0
+    tm, c = trainers[0], batches[1]
+    tm.check_indices()
+    bad = c["ids"].clone()
+    bad[1, 2] = 500
+    tm.train_step(bad, c["mask"], c["tt"], c["onehot"], c["w"], 1e-3, 0.01, 3)
+    with pytest.raises(IndexError):
+        tm.check_indices()
+
+
 @pytest.mark.parametrize("kind", ["xlmr", "bert"])
 def test_training_steps(kind):
     """eight fused steps on one batch: finite, decreasing loss; the pooler bit-unchanged; the gradient buffer cleared"""
