@@ -378,7 +378,7 @@ void build_workspace(mmhip_early& e) {
 }
 
 int side_init(mmhip_early& e) {
-    if (e.overlap < 0) { const char* v = getenv("MMHIP_EARLY_STREAMS"); e.overlap = v ? atoi(v) : 1; }
+    if (e.overlap < 0) e.overlap = env_int("MMHIP_EARLY_STREAMS", 1);
     if (e.side) return 0;
     CHECK_HIP(pool_stream(POOL_VIT, &e.side));          // process-wide streams (mmhip_common.h: pool_stream): vision chain ...
     CHECK_HIP(pool_stream(POOL_SIDE, &e.wside));        // ... and weight gradients + AdamW, as in the late-fusion engine
@@ -1026,8 +1026,7 @@ int mmhip_early_train_step(mmhip_early_handle h, const int64_t* ids, const int64
     a.bc1 = (float)(1.0 - pow((double)beta1, step));
     a.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, step));
     a.zero_grad = 1; a.grad_scale = grad_scale;
-    const char* early_env = getenv("MMHIP_EARLY_ADAMW");
-    const bool layer_opt = !on_stage && e.overlap != 0 && (early_env ? atoi(early_env) != 0 : true);
+    const bool layer_opt = !on_stage && e.overlap != 0 && env_int("MMHIP_EARLY_ADAMW", 1) != 0;          // read per step
     StageOpt so{a, adam_m, adam_v};
     CHECK_RC(side_init(e));
     CHECK_RC(backward_impl(e, nullptr, nullptr, nullptr, s, on_stage, user, layer_opt && e.overlap > 0 ? &so : nullptr));

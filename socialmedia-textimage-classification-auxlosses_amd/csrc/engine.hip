@@ -94,6 +94,8 @@ struct mmhip_engine {
     std::string tm_prefix = "dual_encoder.text_model.";      // state-dict prefix of the text tower
     size_t lin_w = 0, lin_b = 0;                             // text-only classifier
     size_t tt_all = 0; bool has_tt = false;                  // the engine's clamped copy of the token type ids; the last forward was given some
+                                                             // (has_tt is raised by txt_forward_impl alone: no late-fusion handle ever has it, so text_embed
+                                                             // reads tt_all, which only a text-only workspace carves, on that handle kind only)
     int cls_only = -1;         // -1 = read MMHIP_CLS_ONLY on first use; 1: the last text layer runs its post-attention part on CLS rows only
     bool cls_compact = false;  // state of the last forward
     int overlap = -1;          // -1 = read MMHIP_OVERLAP on first use
@@ -480,7 +482,7 @@ int run_gemm_pair(mmhip_engine& e, G& g0, G& g1, hipStream_t s) {
 
 // ------------------------------------------------------------------------------------------------ side stream
 int side_init(mmhip_engine& e) {
-    if (e.overlap < 0) { const char* v = getenv("MMHIP_OVERLAP"); e.overlap = v ? atoi(v) : 1; }
+    if (e.overlap < 0) e.overlap = env_int("MMHIP_OVERLAP", 1);
     if (!e.overlap || e.side) return 0;
     // The side streams are borrowed from the process-wide pool (mmhip_common.h: pool_stream -- why they are not created per engine).
     // The forward's two towers race for the CUs: whichever chain is longer should not be the one that waits.  The image
@@ -507,53 +509,151 @@ int refresh_layer(mmhip_engine& e, const float* base, const LayerOff& o, const L
 }
 
 // ------------------------------------------------------------------------------------------------ forward pieces
-int vit_forward(mmhip_engine& e, const float* pixels, hipStream_t s) {
+// Every launch of a tower's forward is written once, here.  text_forward, vit_forward and towers_forward_lockstep below are orderings of these pieces
+// on the streams they name: a piece takes its stream from the caller and never chooses one (run_gemm picks its scratch by it), and every tower
+// GEMM passes part_gemm (a no-op whenever the forward is not partitioned: cur_part = {0, 0}, as under lockstep).
+inline int run_gemm(mmhip_engine& e, G&& g, hipStream_t s) { return run_gemm(e, g, s); }
+
+// text embeddings; opens a forward: MMHIP_CLS_ONLY is read on the engine's first one, and no layer has closed yet
+int text_embed(mmhip_engine& e, hipStream_t s) {
     const mmhip_config& c = e.cfg;
-    const int H = e.Hv(), I = e.Iv(), B = e.B, P = e.P(), Kpp = e.Kpp(), dt = e.dt();
-    const int Mv = B * P;
-    const bool clip = e.clip();
-    const float* F = e.frozen;
-    const bool px = e.px;
-    CHECK_HIP(launch_patchify(pixels, e.ws + e.v_patches, B, c.image, c.patch, Kpp, px ? DT_PAIR : dt, s));
-    {
-        G g(e.ws + e.v_patches, Kpp, e.ws + e.patch_w16, Kpp, e.ws + e.v_pe, H, B * (P - 1), H, Kpp);
-        if (!clip) g.bias(F + e.v_patch_b);           // CLIP's patch conv has no bias
-        g.px_in(px);
-        part_gemm(e, g, 1);
-        CHECK_RC(run_gemm(e, g, s));
-    }
-    CHECK_HIP(launch_vit_assemble(e.ws + e.v_pe, F + e.v_cls, F + e.v_pos, e.ws + e.v_x, B, P, H, dt, s));
-    char* x = e.ws + e.v_x;
-    if (clip) {      // pre_layrnorm, in place (HF:models/clip/modeling_clip.py CLIPVisionTransformer.forward)
-        LNArgs ln{x, x, F + e.v_pre_ln_w, F + e.v_pre_ln_b, nullptr, nullptr, Mv, H, H, H, c.ln_eps_img};
-        CHECK_HIP(launch_layernorm_fwd(ln, dt, s));
-    }
-    for (int l = 0; l < c.layers_img; ++l) {
-        const LayerOff& o = e.vit[l];
-        const LayerW16& w = e.vit_w16[l];
-        LNArgs ln{x, e.ws + e.v_ln, F + o.ln1_w, F + o.ln1_b, nullptr, nullptr, Mv, H, H, H, c.ln_eps_img};
-        ln_pair(ln, px, e.ws + e.v_ln, true);          // only GEMMs read it: the pair alone
-        CHECK_HIP(launch_layernorm_fwd(ln, dt, s));
-        { G g(e.ws + e.v_ln, H, e.ws + w.qkv, H, e.ws + e.v_qkv, 3 * H, Mv, 3 * H, H); g.bias(F + o.qkv_b).px_in(px).px_out(px); part_gemm(e, g, 1); CHECK_RC(run_gemm(e, g, s)); }
-        AttnArgs at = attn_args(e.ws + e.v_qkv, nullptr, e.ws + e.v_ctx, nullptr, B, P, e.heads_v(), H);
+    const float* W = e.train;
+    EmbedArgs ea{};
+    ea.ids = e.wsp<int64_t>(e.ids_all); ea.mask = e.wsp<int64_t>(e.mask_all);
+    ea.word = W + e.t_word; ea.pos = W + e.t_pos; ea.type = W + e.t_type; ea.gamma = W + e.t_eln_w; ea.beta = W + e.t_eln_b;
+    ea.x = e.ws + e.x0; ea.xhat = e.ws + e.xhat_emb; ea.rstd = e.wsp<float>(e.rstd_emb); ea.pos_ids = e.wsp<int>(e.pos_ids);
+    ea.maskbias = e.wsp<float>(e.maskbias);
+    ea.posts = e.Bt; ea.T = e.T; ea.H = c.hidden; ea.xlmr = c.txt_kind == MMHIP_TXT_XLMR; ea.pad_id = c.pad_id; ea.eps = c.ln_eps_txt;
+    ea.drop = make_drop(c.p_hidden, e.seed, STREAM_EMBED, e.train_mode);
+    if (e.has_tt) ea.type_ids = e.wsp<int64_t>(e.tt_all);
+    embed_pair(ea, e.px, e.ws + e.x0p);
+    CHECK_HIP(launch_embed_fwd(ea, e.dt(), s));
+    if (e.cls_only < 0) e.cls_only = env_int("MMHIP_CLS_ONLY", 1);
+    e.cls_compact = false;
+    return 0;
+}
+
+// The forward launches of text layer l.  Its input is the layer below's output (the embeddings' for l = 0): x as the residual reads it, xg as the
+// GEMMs read it (parity mode: its plane pair).
+// Only the CLS row of the last layer's output is ever consumed (fusion query and pooler, mm_late.py:111,155-158): its attention needs query
+// tile 0 only and everything after it runs on Bt rows (row stride T*H in the full tensors, compact [Bt, .] outputs).  Dropout indices keep
+// the full-tensor numbering (row_mul = T).
+struct TextLayer {
+    mmhip_engine& e;
+    const int l;
+    const LayerOff& o; const LayerW16& w; const TextAct& a;
+    const float* W;
+    const int H, I, T, Bt, Mt;
+    const bool px, tr, compact;
+    const int Mr, rs, rmul;
+    const char *x, *xg;
+    TextLayer(mmhip_engine& e, int l)
+        : e(e), l(l), o(e.txt[l]), w(e.txt_w16[l]), a(e.tact[l]), W(e.train), H(e.cfg.hidden), I(e.cfg.inter), T(e.T), Bt(e.Bt), Mt(e.Bt * e.T), px(e.px),
+          tr(e.train_mode), compact(e.cls_only > 0 && l == e.cfg.layers_txt - 1), Mr(compact ? Bt : Mt), rs(compact ? T * H : H), rmul(compact ? T : 1),
+          x(e.ws + (l ? e.tact[l - 1].out : e.x0)), xg(px ? e.ws + (l ? e.tact[l - 1].outp : e.x0p) : x) {}
+    G part(G& g) const { part_gemm(e, g, 0); return g; }
+    G qkv() const { return part(G(xg, H, e.ws + w.qkv, H, e.ws + a.qkv, 3 * H, Mt, 3 * H, H).bias(W + o.qkv_b).px_in(px).px_out(px)); }
+    int attention(hipStream_t s) const {
+        AttnArgs at = attn_args(e.ws + a.qkv, e.wsp<float>(e.maskbias), e.ws + a.ctx, e.wsp<float>(a.lse), Bt, T, e.cfg.heads, H,
+                                make_drop(e.cfg.p_attn, e.seed, stream_attn(l), tr));
         attn_pair(at, px);
-        CHECK_HIP(launch_attn_fwd(at, dt, s));
-        { G g(e.ws + e.v_ctx, H, e.ws + w.ao, H, x, H, Mv, H, H); g.bias(F + o.ao_b).residual(x, H).px_in(px); part_gemm(e, g, 1); CHECK_RC(run_gemm(e, g, s)); }
-        LNArgs ln2{x, e.ws + e.v_ln, F + o.ln2_w, F + o.ln2_b, nullptr, nullptr, Mv, H, H, H, c.ln_eps_img};
-        ln_pair(ln2, px, e.ws + e.v_ln, true);          // only GEMMs read it: the pair alone
-        CHECK_HIP(launch_layernorm_fwd(ln2, dt, s));
-        { G g(e.ws + e.v_ln, H, e.ws + w.fc1, H, e.ws + e.v_h, I, Mv, I, H); g.bias(F + o.fc1_b); if (clip) g.qgelu(); else g.gelu(); g.px_in(px).px_out(px); part_gemm(e, g, 1); CHECK_RC(run_gemm(e, g, s)); }
-        { G g(e.ws + e.v_h, I, e.ws + w.fc2, I, x, H, Mv, H, I); g.bias(F + o.fc2_b).residual(x, H).px_in(px); part_gemm(e, g, 1); CHECK_RC(run_gemm(e, g, s)); }
+        at.q_tiles = compact ? 1 : 0;
+        CHECK_HIP(launch_attn_fwd(at, e.dt(), s));
+        return 0;
     }
-    if (clip) {
+    G attn_out() const {
+        return part(G(e.ws + a.ctx, rs, e.ws + w.ao, H, e.ws + a.pre1, H, Mr, H, H)
+                        .bias(W + o.ao_b).dropout(make_drop(e.cfg.p_hidden, e.seed, stream_attn_out(l), tr), rmul).residual(x, rs).px_in(px));
+    }
+    G fc1() const { return part(G(e.ws + (px ? a.a1p : a.a1), H, e.ws + w.fc1, H, e.ws + a.h, I, Mr, I, H).bias(W + o.fc1_b).aux(e.ws + a.u, I).gelu().px_in(px).px_out(px)); }
+    G fc2() const {
+        return part(G(e.ws + a.h, I, e.ws + w.fc2, I, e.ws + a.pre2, H, Mr, H, I)
+                        .bias(W + o.fc2_b).dropout(make_drop(e.cfg.p_hidden, e.seed, stream_ffn_out(l), tr), rmul).residual(e.ws + a.a1, H).px_in(px));
+    }
+    int ln(size_t in, size_t out, size_t pair, size_t gamma, size_t beta, size_t mean, size_t rstd, hipStream_t s) const {
+        LNArgs n{e.ws + in, e.ws + out, W + gamma, W + beta, e.wsp<float>(mean), e.wsp<float>(rstd), Mr, H, H, H, e.cfg.ln_eps_txt};
+        ln_pair(n, px, e.ws + pair);
+        CHECK_HIP(launch_layernorm_fwd(n, e.dt(), s));
+        return 0;
+    }
+    int ln1(hipStream_t s) const { return ln(a.pre1, a.a1, a.a1p, o.ln1_w, o.ln1_b, a.mean1, a.rstd1, s); }
+    // closes the layer: from here on the engine's last hidden state is this layer's output, compact if it ran on the CLS rows
+    int ln2(hipStream_t s) const {
+        CHECK_RC(ln(a.pre2, a.out, a.outp, o.ln2_w, o.ln2_b, a.mean2, a.rstd2, s));
+        e.cls_compact = compact;
+        return 0;
+    }
+};
+
+// patchify, patch GEMM, [CLS | patches] + positions, and CLIP's pre_layrnorm (in place; HF:models/clip/modeling_clip.py CLIPVisionTransformer.forward)
+int vit_embed(mmhip_engine& e, const float* pixels, hipStream_t s) {
+    const mmhip_config& c = e.cfg;
+    const int H = e.Hv(), B = e.B, P = e.P(), Kpp = e.Kpp(), dt = e.dt();
+    const float* F = e.frozen;
+    CHECK_HIP(launch_patchify(pixels, e.ws + e.v_patches, B, c.image, c.patch, Kpp, e.px ? DT_PAIR : dt, s));
+    G g(e.ws + e.v_patches, Kpp, e.ws + e.patch_w16, Kpp, e.ws + e.v_pe, H, B * (P - 1), H, Kpp);
+    if (!e.clip()) g.bias(F + e.v_patch_b);           // CLIP's patch conv has no bias
+    g.px_in(e.px);
+    part_gemm(e, g, 1);
+    CHECK_RC(run_gemm(e, g, s));
+    CHECK_HIP(launch_vit_assemble(e.ws + e.v_pe, F + e.v_cls, F + e.v_pos, e.ws + e.v_x, B, P, H, dt, s));
+    if (e.clip()) {
+        LNArgs ln{e.ws + e.v_x, e.ws + e.v_x, F + e.v_pre_ln_w, F + e.v_pre_ln_b, nullptr, nullptr, B * P, H, H, H, c.ln_eps_img};
+        CHECK_HIP(launch_layernorm_fwd(ln, dt, s));
+    }
+    return 0;
+}
+
+// The forward launches of image layer l (pre-LN: HF ViTLayer / CLIPEncoderLayer) on the residual stream v_x, in place.
+struct ImageLayer {
+    const mmhip_engine& e;
+    const LayerOff& o; const LayerW16& w;
+    const float* F;
+    const int H, I, Mv;
+    const bool px;
+    char* x;
+    ImageLayer(const mmhip_engine& e, int l)
+        : e(e), o(e.vit[l]), w(e.vit_w16[l]), F(e.frozen), H(e.Hv()), I(e.Iv()), Mv(e.B * e.P()), px(e.px), x(e.ws + e.v_x) {}
+    G part(G& g) const { part_gemm(e, g, 1); return g; }
+    int ln(size_t gamma, size_t beta, hipStream_t s) const {
+        LNArgs n{x, e.ws + e.v_ln, F + gamma, F + beta, nullptr, nullptr, Mv, H, H, H, e.cfg.ln_eps_img};
+        ln_pair(n, px, e.ws + e.v_ln, true);          // only GEMMs read it: the pair alone
+        CHECK_HIP(launch_layernorm_fwd(n, e.dt(), s));
+        return 0;
+    }
+    int ln1(hipStream_t s) const { return ln(o.ln1_w, o.ln1_b, s); }
+    int ln2(hipStream_t s) const { return ln(o.ln2_w, o.ln2_b, s); }
+    G qkv() const { return part(G(e.ws + e.v_ln, H, e.ws + w.qkv, H, e.ws + e.v_qkv, 3 * H, Mv, 3 * H, H).bias(F + o.qkv_b).px_in(px).px_out(px)); }
+    int attention(hipStream_t s) const {
+        AttnArgs at = attn_args(e.ws + e.v_qkv, nullptr, e.ws + e.v_ctx, nullptr, e.B, e.P(), e.heads_v(), H);
+        attn_pair(at, px);
+        CHECK_HIP(launch_attn_fwd(at, e.dt(), s));
+        return 0;
+    }
+    G attn_out() const { return part(G(e.ws + e.v_ctx, H, e.ws + w.ao, H, x, H, Mv, H, H).bias(F + o.ao_b).residual(x, H).px_in(px)); }
+    G fc1() const {
+        G g(e.ws + e.v_ln, H, e.ws + w.fc1, H, e.ws + e.v_h, I, Mv, I, H);
+        g.bias(F + o.fc1_b);
+        if (e.clip()) g.qgelu(); else g.gelu();
+        return part(g.px_in(px).px_out(px));
+    }
+    G fc2() const { return part(G(e.ws + e.v_h, I, e.ws + w.fc2, I, x, H, Mv, H, I).bias(F + o.fc2_b).residual(x, H).px_in(px)); }
+};
+
+// closes the image tower: last hidden state in v_out, pooled feature in h_vpool
+int vit_close(mmhip_engine& e, hipStream_t s) {
+    const int H = e.Hv(), B = e.B, P = e.P(), Mv = B * P, dt = e.dt();
+    const float* F = e.frozen;
+    char* x = e.ws + e.v_x;
+    if (e.clip()) {
         // last_hidden_state = the encoder output as it is; pooler_output = post_layernorm(CLS row)   (CLIPVisionTransformer.forward)
         CHECK_HIP(hipMemcpyAsync(e.ws + e.v_out, x, (size_t)Mv * H * e.esz(), hipMemcpyDeviceToDevice, s));
         CHECK_HIP(launch_gather_rows_f32(x, (size_t)P * H, e.wsp<float>(e.h_vpool), H, B, H, dt, s));
-        LNArgs lnp{e.wsp<float>(e.h_vpool), e.wsp<float>(e.h_vpool), F + e.v_ln_w, F + e.v_ln_b, nullptr, nullptr, B, H, H, H, c.ln_eps_img};
+        LNArgs lnp{e.wsp<float>(e.h_vpool), e.wsp<float>(e.h_vpool), F + e.v_ln_w, F + e.v_ln_b, nullptr, nullptr, B, H, H, H, e.cfg.ln_eps_img};
         CHECK_HIP(launch_layernorm_fwd(lnp, DT_F32, s));
         return 0;
     }
-    LNArgs lnf{x, e.ws + e.v_out, F + e.v_ln_w, F + e.v_ln_b, nullptr, nullptr, Mv, H, H, H, c.ln_eps_img};
+    LNArgs lnf{x, e.ws + e.v_out, F + e.v_ln_w, F + e.v_ln_b, nullptr, nullptr, Mv, H, H, H, e.cfg.ln_eps_img};
     CHECK_HIP(launch_layernorm_fwd(lnf, dt, s));
     // pooler on the CLS rows (row stride P*H): tanh(dense(x[:,0]))
     SmallGemmArgs sp = small(e.ws + e.v_out, P * H, F + e.v_pool_w, H, F + e.v_pool_b, e.wsp<float>(e.h_vpool), H, B, H, H, ACT_TANH);
@@ -561,58 +661,33 @@ int vit_forward(mmhip_engine& e, const float* pixels, hipStream_t s) {
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------ the towers' forward: orderings of the pieces
+int vit_forward(mmhip_engine& e, const float* pixels, hipStream_t s) {
+    CHECK_RC(vit_embed(e, pixels, s));
+    for (int l = 0; l < e.cfg.layers_img; ++l) {
+        const ImageLayer v(e, l);
+        CHECK_RC(v.ln1(s));
+        CHECK_RC(run_gemm(e, v.qkv(), s));
+        CHECK_RC(v.attention(s));
+        CHECK_RC(run_gemm(e, v.attn_out(), s));
+        CHECK_RC(v.ln2(s));
+        CHECK_RC(run_gemm(e, v.fc1(), s));
+        CHECK_RC(run_gemm(e, v.fc2(), s));
+    }
+    return vit_close(e, s);
+}
+
 int text_forward(mmhip_engine& e, hipStream_t s) {
-    const mmhip_config& c = e.cfg;
-    const int H = c.hidden, I = c.inter, T = e.T, Bt = e.Bt, Mt = Bt * T, dt = e.dt();
-    const float* W = e.train;
-    const bool tr = e.train_mode;
-    EmbedArgs ea{};
-    ea.ids = e.wsp<int64_t>(e.ids_all); ea.mask = e.wsp<int64_t>(e.mask_all);
-    ea.word = W + e.t_word; ea.pos = W + e.t_pos; ea.type = W + e.t_type; ea.gamma = W + e.t_eln_w; ea.beta = W + e.t_eln_b;
-    ea.x = e.ws + e.x0; ea.xhat = e.ws + e.xhat_emb; ea.rstd = e.wsp<float>(e.rstd_emb); ea.pos_ids = e.wsp<int>(e.pos_ids);
-    ea.maskbias = e.wsp<float>(e.maskbias);
-    ea.posts = Bt; ea.T = T; ea.H = H; ea.xlmr = c.txt_kind == MMHIP_TXT_XLMR; ea.pad_id = c.pad_id; ea.eps = c.ln_eps_txt;
-    ea.drop = make_drop(c.p_hidden, e.seed, STREAM_EMBED, tr);
-    if (e.has_tt) ea.type_ids = e.wsp<int64_t>(e.tt_all);
-    const bool px = e.px;
-    embed_pair(ea, px, e.ws + e.x0p);
-    CHECK_HIP(launch_embed_fwd(ea, dt, s));
-    const char* x = e.ws + e.x0;
-    const char* xg = px ? e.ws + e.x0p : x;          // the layer input as the GEMMs read it (parity mode: its plane pair)
-    if (e.cls_only < 0) { const char* v = getenv("MMHIP_CLS_ONLY"); e.cls_only = v ? atoi(v) : 1; }
-    e.cls_compact = false;
-    for (int l = 0; l < c.layers_txt; ++l) {
-        const LayerOff& o = e.txt[l];
-        const LayerW16& w = e.txt_w16[l];
-        const TextAct& a = e.tact[l];
-        { G g(xg, H, e.ws + w.qkv, H, e.ws + a.qkv, 3 * H, Mt, 3 * H, H); g.bias(W + o.qkv_b).px_in(px).px_out(px); part_gemm(e, g, 0); CHECK_RC(run_gemm(e, g, s)); }
-        // Only the CLS row of the last layer's output is ever consumed (fusion query and pooler, mm_late.py:111,155-158):
-        // its attention needs query tile 0 only and everything after it runs on Bt rows (row stride T*H in the full
-        // tensors, compact [Bt, .] outputs).  Dropout indices keep the full-tensor numbering (row_mul = T).
-        const bool compact = e.cls_only > 0 && l == c.layers_txt - 1;
-        const int Mr = compact ? Bt : Mt, rs = compact ? T * H : H, rmul = compact ? T : 1;
-        AttnArgs at = attn_args(e.ws + a.qkv, e.wsp<float>(e.maskbias), e.ws + a.ctx, e.wsp<float>(a.lse), Bt, T, c.heads, H, make_drop(c.p_attn, e.seed, stream_attn(l), tr));
-        attn_pair(at, px);
-        at.q_tiles = compact ? 1 : 0;
-        CHECK_HIP(launch_attn_fwd(at, dt, s));
-        { G g(e.ws + a.ctx, rs, e.ws + w.ao, H, e.ws + a.pre1, H, Mr, H, H);
-          g.bias(W + o.ao_b).dropout(make_drop(c.p_hidden, e.seed, stream_attn_out(l), tr), rmul).residual(x, rs).px_in(px);
-          part_gemm(e, g, 0);
-          CHECK_RC(run_gemm(e, g, s)); }
-        LNArgs ln1{e.ws + a.pre1, e.ws + a.a1, W + o.ln1_w, W + o.ln1_b, e.wsp<float>(a.mean1), e.wsp<float>(a.rstd1), Mr, H, H, H, c.ln_eps_txt};
-        ln_pair(ln1, px, e.ws + a.a1p);
-        CHECK_HIP(launch_layernorm_fwd(ln1, dt, s));
-        { G g(e.ws + (px ? a.a1p : a.a1), H, e.ws + w.fc1, H, e.ws + a.h, I, Mr, I, H); g.bias(W + o.fc1_b).aux(e.ws + a.u, I).gelu().px_in(px).px_out(px); part_gemm(e, g, 0); CHECK_RC(run_gemm(e, g, s)); }
-        { G g(e.ws + a.h, I, e.ws + w.fc2, I, e.ws + a.pre2, H, Mr, H, I);
-          g.bias(W + o.fc2_b).dropout(make_drop(c.p_hidden, e.seed, stream_ffn_out(l), tr), rmul).residual(e.ws + a.a1, H).px_in(px);
-          part_gemm(e, g, 0);
-          CHECK_RC(run_gemm(e, g, s)); }
-        LNArgs ln2{e.ws + a.pre2, e.ws + a.out, W + o.ln2_w, W + o.ln2_b, e.wsp<float>(a.mean2), e.wsp<float>(a.rstd2), Mr, H, H, H, c.ln_eps_txt};
-        ln_pair(ln2, px, e.ws + a.outp);
-        CHECK_HIP(launch_layernorm_fwd(ln2, dt, s));
-        e.cls_compact = compact;
-        x = e.ws + a.out;
-        xg = px ? e.ws + a.outp : x;
+    CHECK_RC(text_embed(e, s));
+    for (int l = 0; l < e.cfg.layers_txt; ++l) {
+        const TextLayer t(e, l);
+        CHECK_RC(run_gemm(e, t.qkv(), s));
+        CHECK_RC(t.attention(s));
+        CHECK_RC(run_gemm(e, t.attn_out(), s));
+        CHECK_RC(t.ln1(s));
+        CHECK_RC(run_gemm(e, t.fc1(), s));
+        CHECK_RC(run_gemm(e, t.fc2(), s));
+        CHECK_RC(t.ln2(s));
     }
     return 0;
 }
@@ -631,137 +706,52 @@ bool lockstep_ok(const mmhip_engine& e) {
     // kernels forked onto two streams between the pairs: on two streams one tower's attention / LayerNorm kernels hide under the other's
     // GEMMs for free, in lockstep they are serial work between launches that wait for each other.  Off by default in every mode.
     static int on = -2;
-    if (on == -2) { const char* v = getenv("MMHIP_LOCKSTEP"); on = v ? atoi(v) : 0; }
+    if (on == -2) on = env_int("MMHIP_LOCKSTEP", 0);
     return on > 0 && (e.dt() == DT_BF16 || e.dt() == DT_F16 || (e.dt() == DT_F32 && e.px)) && !e.clip() && e.Hv() == e.cfg.hidden && e.Iv() == e.cfg.inter &&
            e.cfg.layers_txt > 0 && e.cfg.layers_img > 0;
 }
 int towers_forward_lockstep(mmhip_engine& e, const float* pixels, hipStream_t s) {
     const mmhip_config& c = e.cfg;
-    const int H = c.hidden, I = c.inter, T = e.T, B = e.B, Bt = e.Bt, Mt = Bt * T, P = e.P(), Kpp = e.Kpp(), dt = e.dt();
-    const int Mv = B * P;
-    const float* W = e.train;
-    const float* F = e.frozen;
-    const bool tr = e.train_mode, px = e.px;
     CHECK_RC(e.span(0, s));
-    // ---- embeddings of both towers
-    CHECK_HIP(launch_patchify(pixels, e.ws + e.v_patches, B, c.image, c.patch, Kpp, px ? DT_PAIR : dt, s));
-    { G g(e.ws + e.v_patches, Kpp, e.ws + e.patch_w16, Kpp, e.ws + e.v_pe, H, B * (P - 1), H, Kpp); g.bias(F + e.v_patch_b).px_in(px); CHECK_RC(run_gemm(e, g, s)); }
-    CHECK_HIP(launch_vit_assemble(e.ws + e.v_pe, F + e.v_cls, F + e.v_pos, e.ws + e.v_x, B, P, H, dt, s));
-    char* xv = e.ws + e.v_x;
-    EmbedArgs ea{};
-    ea.ids = e.wsp<int64_t>(e.ids_all); ea.mask = e.wsp<int64_t>(e.mask_all);
-    ea.word = W + e.t_word; ea.pos = W + e.t_pos; ea.type = W + e.t_type; ea.gamma = W + e.t_eln_w; ea.beta = W + e.t_eln_b;
-    ea.x = e.ws + e.x0; ea.xhat = e.ws + e.xhat_emb; ea.rstd = e.wsp<float>(e.rstd_emb); ea.pos_ids = e.wsp<int>(e.pos_ids);
-    ea.maskbias = e.wsp<float>(e.maskbias);
-    ea.posts = Bt; ea.T = T; ea.H = H; ea.xlmr = c.txt_kind == MMHIP_TXT_XLMR; ea.pad_id = c.pad_id; ea.eps = c.ln_eps_txt;
-    ea.drop = make_drop(c.p_hidden, e.seed, STREAM_EMBED, tr);
-    embed_pair(ea, px, e.ws + e.x0p);
-    CHECK_HIP(launch_embed_fwd(ea, dt, s));
-    const char* xt = e.ws + e.x0;
-    const char* xtg = px ? e.ws + e.x0p : xt;          // the text layer input as the GEMMs read it
-    if (e.cls_only < 0) { const char* v = getenv("MMHIP_CLS_ONLY"); e.cls_only = v ? atoi(v) : 1; }
-    e.cls_compact = false;
-    const int L = c.layers_txt > c.layers_img ? c.layers_txt : c.layers_img;
+    CHECK_RC(vit_embed(e, pixels, s));
+    CHECK_RC(text_embed(e, s));
     // Between the paired GEMMs the towers' row kernels are independent: the image tower's attention / LayerNorm go to the side stream, beside the
     // text tower's on `s` (fork / join by events; 71 + 42 us of attention and 18 + 13 us of LayerNorm per layer, each alone on the chip, round 5)
     hipStream_t sv = use_side(e) ? e.side_vit[0] : s;
     auto fork = [&]() -> int { if (sv != s) { CHECK_HIP(hipEventRecord(e.ev_fork, s)); CHECK_HIP(hipStreamWaitEvent(sv, e.ev_fork, 0)); } return 0; };
     auto join = [&]() -> int { if (sv != s) { CHECK_HIP(hipEventRecord(e.ev_vit, sv)); CHECK_HIP(hipStreamWaitEvent(s, e.ev_vit, 0)); } return 0; };
-    auto attn = [&](hipStream_t st, const char* qkv, const float* mb, char* ctx, float* lse, int posts, int S, int heads, const DropCfg* d, int q_tiles) -> int {
-        AttnArgs at = attn_args(qkv, mb, ctx, lse, posts, S, heads, H, d ? *d : DropCfg{});
-        attn_pair(at, px);
-        at.q_tiles = q_tiles;
-        CHECK_HIP(launch_attn_fwd(at, dt, st));
-        return 0;
-    };
+    const int L = c.layers_txt > c.layers_img ? c.layers_txt : c.layers_img;
     for (int l = 0; l < L; ++l) {
+        // a tower that has no layer l contributes nothing (its piece is built from its layer 0 and never enqueued); the other's GEMM runs alone
         const bool ht = l < c.layers_txt, hv = l < c.layers_img;
-        const LayerOff& ot = e.txt[ht ? l : 0];
-        const LayerW16& wt = e.txt_w16[ht ? l : 0];
-        const TextAct& a = e.tact[ht ? l : 0];
-        const LayerOff& ov = e.vit[hv ? l : 0];
-        const LayerW16& wv = e.vit_w16[hv ? l : 0];
-        const bool compact = ht && e.cls_only > 0 && l == c.layers_txt - 1;
-        const int Mr = compact ? Bt : Mt, rs = compact ? T * H : H, rmul = compact ? T : 1;
-        auto both = [&](G& gt, G& gv) -> int {
+        const TextLayer t(e, ht ? l : 0);
+        const ImageLayer v(e, hv ? l : 0);
+        auto both = [&](G gt, G gv) -> int {
             if (ht && hv) return run_gemm_pair(e, gt, gv, s);
             return run_gemm(e, ht ? gt : gv, s);
         };
         // ---- QKV (image tower: pre-LN; layer 0's runs here, the later layers' beside the text tower's closing LayerNorm of the layer above)
-        if (hv && l == 0) {
-            LNArgs ln{xv, e.ws + e.v_ln, F + ov.ln1_w, F + ov.ln1_b, nullptr, nullptr, Mv, H, H, H, c.ln_eps_img};
-            ln_pair(ln, px, e.ws + e.v_ln, true);          // only GEMMs read it: the pair alone
-            CHECK_HIP(launch_layernorm_fwd(ln, dt, s));
-        }
-        {
-            G gt(xtg, H, e.ws + wt.qkv, H, e.ws + a.qkv, 3 * H, Mt, 3 * H, H); gt.bias(W + ot.qkv_b).px_in(px).px_out(px);
-            G gv(e.ws + e.v_ln, H, e.ws + wv.qkv, H, e.ws + e.v_qkv, 3 * H, Mv, 3 * H, H); gv.bias(F + ov.qkv_b).px_in(px).px_out(px);
-            CHECK_RC(both(gt, gv));
-        }
+        if (hv && l == 0) CHECK_RC(v.ln1(s));
+        CHECK_RC(both(t.qkv(), v.qkv()));
         // ---- attention
-        if (hv) {
-            CHECK_RC(fork());
-            CHECK_RC(attn(sv, e.ws + e.v_qkv, nullptr, e.ws + e.v_ctx, nullptr, B, P, e.heads_v(), nullptr, 0));
-        }
-        if (ht) {
-            const DropCfg d = make_drop(c.p_attn, e.seed, stream_attn(l), tr);
-            CHECK_RC(attn(s, e.ws + a.qkv, e.wsp<float>(e.maskbias), e.ws + a.ctx, e.wsp<float>(a.lse), Bt, T, c.heads, &d, compact ? 1 : 0));
-        }
+        if (hv) { CHECK_RC(fork()); CHECK_RC(v.attention(sv)); }
+        if (ht) CHECK_RC(t.attention(s));
         if (hv) CHECK_RC(join());
-        // ---- attention output (+ residual)
-        {
-            G gt(e.ws + a.ctx, rs, e.ws + wt.ao, H, e.ws + a.pre1, H, Mr, H, H);
-            gt.bias(W + ot.ao_b).dropout(make_drop(c.p_hidden, e.seed, stream_attn_out(l), tr), rmul).residual(xt, rs).px_in(px);
-            G gv(e.ws + e.v_ctx, H, e.ws + wv.ao, H, xv, H, Mv, H, H); gv.bias(F + ov.ao_b).residual(xv, H).px_in(px);
-            CHECK_RC(both(gt, gv));
-        }
-        if (hv) {
-            CHECK_RC(fork());
-            LNArgs ln2{xv, e.ws + e.v_ln, F + ov.ln2_w, F + ov.ln2_b, nullptr, nullptr, Mv, H, H, H, c.ln_eps_img};
-            ln_pair(ln2, px, e.ws + e.v_ln, true);          // only GEMMs read it: the pair alone
-            CHECK_HIP(launch_layernorm_fwd(ln2, dt, sv));
-        }
-        if (ht) {
-            LNArgs ln1{e.ws + a.pre1, e.ws + a.a1, W + ot.ln1_w, W + ot.ln1_b, e.wsp<float>(a.mean1), e.wsp<float>(a.rstd1), Mr, H, H, H, c.ln_eps_txt};
-            ln_pair(ln1, px, e.ws + a.a1p);
-            CHECK_HIP(launch_layernorm_fwd(ln1, dt, s));
-        }
+        // ---- attention output (+ residual), then the image tower's second LayerNorm beside the text tower's first
+        CHECK_RC(both(t.attn_out(), v.attn_out()));
+        if (hv) { CHECK_RC(fork()); CHECK_RC(v.ln2(sv)); }
+        if (ht) CHECK_RC(t.ln1(s));
         if (hv) CHECK_RC(join());
         // ---- feed-forward
-        {
-            G gt(e.ws + (px ? a.a1p : a.a1), H, e.ws + wt.fc1, H, e.ws + a.h, I, Mr, I, H); gt.bias(W + ot.fc1_b).aux(e.ws + a.u, I).gelu().px_in(px).px_out(px);
-            G gv(e.ws + e.v_ln, H, e.ws + wv.fc1, H, e.ws + e.v_h, I, Mv, I, H); gv.bias(F + ov.fc1_b).gelu().px_in(px).px_out(px);
-            CHECK_RC(both(gt, gv));
-        }
-        {
-            G gt(e.ws + a.h, I, e.ws + wt.fc2, I, e.ws + a.pre2, H, Mr, H, I);
-            gt.bias(W + ot.fc2_b).dropout(make_drop(c.p_hidden, e.seed, stream_ffn_out(l), tr), rmul).residual(e.ws + a.a1, H).px_in(px);
-            G gv(e.ws + e.v_h, I, e.ws + wv.fc2, I, xv, H, Mv, H, I); gv.bias(F + ov.fc2_b).residual(xv, H).px_in(px);
-            CHECK_RC(both(gt, gv));
-        }
+        CHECK_RC(both(t.fc1(), v.fc1()));
+        CHECK_RC(both(t.fc2(), v.fc2()));
         // ---- the text layer's closing LayerNorm beside the image tower's opening one of the next layer
         const bool vnext = l + 1 < c.layers_img;
-        if (vnext) {
-            CHECK_RC(fork());
-            const LayerOff& on = e.vit[l + 1];
-            LNArgs ln{xv, e.ws + e.v_ln, F + on.ln1_w, F + on.ln1_b, nullptr, nullptr, Mv, H, H, H, c.ln_eps_img};
-            ln_pair(ln, px, e.ws + e.v_ln, true);          // only GEMMs read it: the pair alone
-            CHECK_HIP(launch_layernorm_fwd(ln, dt, sv));
-        }
-        if (ht) {
-            LNArgs ln2{e.ws + a.pre2, e.ws + a.out, W + ot.ln2_w, W + ot.ln2_b, e.wsp<float>(a.mean2), e.wsp<float>(a.rstd2), Mr, H, H, H, c.ln_eps_txt};
-            ln_pair(ln2, px, e.ws + a.outp);
-            CHECK_HIP(launch_layernorm_fwd(ln2, dt, s));
-            e.cls_compact = compact;
-            xt = e.ws + a.out;
-            xtg = px ? e.ws + a.outp : xt;
-        }
+        if (vnext) { CHECK_RC(fork()); CHECK_RC(ImageLayer(e, l + 1).ln1(sv)); }
+        if (ht) CHECK_RC(t.ln2(s));
         if (vnext) CHECK_RC(join());
     }
-    LNArgs lnf{xv, e.ws + e.v_out, F + e.v_ln_w, F + e.v_ln_b, nullptr, nullptr, Mv, H, H, H, c.ln_eps_img};
-    CHECK_HIP(launch_layernorm_fwd(lnf, dt, s));
-    SmallGemmArgs sp = small(e.ws + e.v_out, P * H, F + e.v_pool_w, H, F + e.v_pool_b, e.wsp<float>(e.h_vpool), H, B, H, H, ACT_TANH);
-    CHECK_HIP(launch_small_nt(sp, dt, s));
+    CHECK_RC(vit_close(e, s));
     CHECK_RC(e.span(1, s));
     return e.span(2, s);
 }
@@ -1006,9 +996,9 @@ int text_layer_backward(mmhip_engine& e, int l, hipStream_t s) {
     CHECK_HIP(launch_layernorm_bwd(b2, dt, s));
     const char* df = (px || d_ffn.thresh16) ? ddrop2 : dpre2;
     // du = (df . W2) * gelu'(u);  d_a1 = du . W1 + dpre2
-    if (e.part_bwd < 0) { const char* v = getenv("MMHIP_PART_BWD"); e.part_bwd = v ? atoi(v) : 0; }
+    if (e.part_bwd < 0) e.part_bwd = env_int("MMHIP_PART_BWD", 0);
     static int bwd_mask = -1;
-    if (bwd_mask < 0) { const char* v = getenv("MMHIP_PART_BWD_MASK"); bwd_mask = v ? atoi(v) : 15; }
+    if (bwd_mask < 0) bwd_mask = env_int("MMHIP_PART_BWD_MASK", 15);
     auto part_bwd = [&](G& g, int bit) {
         if (e.part_bwd > 0 && (bwd_mask & bit) && side && g.a.M >= 2048 && g.a.N % 256 == 0 && g.a.K % 64 == 0 && (dt == DT_BF16 || dt == DT_F16)) g.tile(15).grid(e.part_bwd);
     };
@@ -1017,7 +1007,7 @@ int text_layer_backward(mmhip_engine& e, int l, hipStream_t s) {
     // exactly <= 256 of them -- in isolation 7 % faster than the 192 tiles of 256x128, in the step -0.05 ms (same-box A/B; the
     // same tile in the FORWARD costs +0.3 ms: it leaves no CU to the image tower).  MMHIP_BWD_TILE12=0 turns it off.
     static int bt12 = -1;
-    if (bt12 < 0) { const char* v = getenv("MMHIP_BWD_TILE12"); bt12 = v ? atoi(v) : 1; }
+    if (bt12 < 0) bt12 = env_int("MMHIP_BWD_TILE12", 1);
     const int nt = (bt12 && Mr >= 4096 && Mr <= 8192 && H % 96 == 0) ? 12 : 0;
     { G g(du, I, e.ws + w.fc1T, I, dx2, H, Mr, H, I); g.residual(dpre2, H).px_in(px, np); g.tile(nt); part_bwd(g, 2); CHECK_RC(run_gemm(e, g, s)); }
     // ---- a1 = LN1(pre1), pre1 = drop(ao(ctx)) + x_in        (dx2 = d_a1)
@@ -1127,6 +1117,14 @@ int embed_backward(mmhip_engine& e, hipStream_t s) {
     return 0;
 }
 
+// parity mode: operands as plane pairs or split per call (MMHIP_X3_PAIRS), MFMA products per k slice of the backward (MMHIP_X3_BWD); read at create
+void read_x3_env(mmhip_engine& e) {
+    if (e.cfg.dtype != MMHIP_BF16X3) return;
+    e.px = env_int("MMHIP_X3_PAIRS", 1) != 0;
+    const int n = env_int("MMHIP_X3_BWD", 3);
+    e.bwd_np = n >= 1 && n <= 3 ? n : 3;
+}
+
 }  // namespace
 
 // ================================================================================================ C ABI
@@ -1156,8 +1154,7 @@ int mmhip_create(const mmhip_config* cfg, mmhip_handle* out) {
     mmhip_engine* e = new (std::nothrow) mmhip_engine();
     if (!e) return MMHIP_E_INVALID;
     e->cfg = c;
-    if (c.dtype == MMHIP_BF16X3) { const char* v = getenv("MMHIP_X3_PAIRS"); e->px = v ? atoi(v) != 0 : true; }
-    if (c.dtype == MMHIP_BF16X3) { const char* v = getenv("MMHIP_X3_BWD"); const int n = v ? atoi(v) : 3; e->bwd_np = n >= 1 && n <= 3 ? n : 3; }
+    read_x3_env(*e);
     build_layout(*e);
     build_workspace(*e);
     *out = e;
@@ -1285,7 +1282,7 @@ int mmhip_forward(mmhip_handle h, const int64_t* ids, const int64_t* mask, const
         CHECK_HIP(hipEventRecord(e.ev_fork, s));
         CHECK_RC(e.span(0, s));
         static int force = -2;
-        if (force == -2) { const char* v = getenv("MMHIP_VIT_PRIO"); force = v ? atoi(v) : -1; }
+        if (force == -2) force = env_int("MMHIP_VIT_PRIO", -1);
         const bool vit_longer = (double)e.B * e.P() * e.cfg.layers_img > (double)e.Bt * e.T * e.cfg.layers_txt;     // rows x layers of equal width
         e.vit_is_long = vit_longer;
         hipStream_t sv = e.side_vit[force >= 0 ? (force ? 1 : 0) : (vit_longer ? 1 : 0)];
@@ -1583,12 +1580,11 @@ static int step_backward_update(mmhip_handle h, int use_itc, int use_itm, float*
     // of after the whole backward; the layer's fp32 LayerNorm weights and transposed 16-bit copies are read by its own backward
     // kernels on the caller's stream, so the side stream first waits for the event recorded behind them.
     hipStream_t s = (hipStream_t)stream;
-    const char* early_env = getenv("MMHIP_EARLY_ADAMW");          // read per step: tests compare both orders in one process
     // f16 with the step guard armed: a void step is only known when the backward has reached the embeddings, so every AdamW waits for it
     unsigned* gc = guard_counter(e);
     unsigned* gf = guard_flag(e);
-    const int early = (e.dt() == DT_F16 && gf) ? 0 : (early_env ? atoi(early_env) : 1);
-    if (e.dt() == DT_F16 && gf && !early_env) {
+    const int early = (e.dt() == DT_F16 && gf) ? 0 : env_int("MMHIP_EARLY_ADAMW", 1);          // read per step: tests compare both orders in one process
+    if (e.dt() == DT_F16 && gf && !getenv("MMHIP_EARLY_ADAMW")) {
         static bool told = false;
         if (!told && getenv("MMHIP_VERBOSE")) { fprintf(stderr, "[mmhip] f16 with the step guard armed: every AdamW launch follows the backward (no per-layer optimizer beside it)\n"); told = true; }
     }
@@ -1607,6 +1603,16 @@ static int step_backward_update(mmhip_handle h, int use_itc, int use_itm, float*
     bool opt_pending = false, dense_by_caller = false;
     std::vector<char> layer_done((size_t)(L > 0 ? L : 1), 0);
     std::vector<int> open_layers;          // text layers whose gradient stage lies in the bucket that is still open
+    // text layer l on the side stream: its AdamW (adamw = false: the caller stepped it, MMHIP_CB_HANDLED), then its 16-bit operand refresh
+    auto layer_update = [&](int l, bool adamw) -> int {
+        const LayerOff& o = e.txt[l];
+        if (adamw)
+            CHECK_RC(adamw_impl(e.train + o.begin, e.grad + o.begin, adam_m + o.begin, adam_v + o.begin, o.end - o.begin, lr, beta1, beta2, eps, weight_decay,
+                                step, grad_scale, 1, e.side, gc, gf));
+        CHECK_RC(refresh_layer(e, e.train, o, e.txt_w16[l], true, e.side, e.cfg.hidden, e.cfg.inter));
+        layer_done[l] = adamw ? 1 : 2;          // 2: stepped by the caller, refreshed here
+        return 0;
+    };
     for (int st = 0; st < L + 2; ++st) {
         CHECK_RC(mmhip_backward_stage(h, st, stream));
         if (cb && st >= 1) {
@@ -1622,14 +1628,7 @@ static int step_backward_update(mmhip_handle h, int use_itc, int use_itm, float*
                     CHECK_HIP(hipStreamWaitEvent(e.side, e.ev_layer[0], 0));
                     const int w = cb(user, MMHIP_CB_WAIT_BUCKET);
                     if (w != 0 && w != MMHIP_CB_HANDLED) return w;
-                    for (int l : open_layers) {
-                        const LayerOff& o = e.txt[l];
-                        if (w == 0)
-                            CHECK_RC(adamw_impl(e.train + o.begin, e.grad + o.begin, adam_m + o.begin, adam_v + o.begin, o.end - o.begin, lr, beta1, beta2, eps,
-                                                    weight_decay, step, grad_scale, 1, e.side, gc, gf));
-                        CHECK_RC(refresh_layer(e, e.train, o, e.txt_w16[l], true, e.side, e.cfg.hidden, e.cfg.inter));
-                        layer_done[l] = w == 0 ? 1 : 2;          // 2: stepped by the caller (MMHIP_CB_HANDLED), refreshed here
-                    }
+                    for (int l : open_layers) CHECK_RC(layer_update(l, w == 0));
                     CHECK_HIP(hipEventRecord(e.ev_opt, e.side));
                     opt_pending = true;
                 }
@@ -1638,13 +1637,9 @@ static int step_backward_update(mmhip_handle h, int use_itc, int use_itm, float*
         }
         if (layer_opt && st >= 1 && st <= L) {
             const int l = L - st, set = l & 1;
-            const LayerOff& o = e.txt[l];
             CHECK_HIP(hipEventRecord(e.ev_layer[set], s));
             CHECK_HIP(hipStreamWaitEvent(e.side, e.ev_layer[set], 0));
-            CHECK_RC(adamw_impl(e.train + o.begin, e.grad + o.begin, adam_m + o.begin, adam_v + o.begin, o.end - o.begin, lr, beta1, beta2, eps,
-                                   weight_decay, step, grad_scale, 1, e.side, gc, gf));
-            CHECK_RC(refresh_layer(e, e.train, o, e.txt_w16[l], true, e.side, e.cfg.hidden, e.cfg.inter));
-            layer_done[l] = 1;
+            CHECK_RC(layer_update(l, true));
             CHECK_HIP(hipEventRecord(e.ev_opt, e.side));
             opt_pending = true;
         }
@@ -1817,8 +1812,7 @@ int mmhip_txt_create(const mmhip_txt_config* cfg, mmhip_txt_handle* out) {
     c.loss_scale = t.loss_scale; c.img_kind = MMHIP_IMG_VIT;
     e->txt_only = true;
     e->tm_prefix = "bert_model.";
-    if (c.dtype == MMHIP_BF16X3) { const char* v = getenv("MMHIP_X3_PAIRS"); e->px = v ? atoi(v) != 0 : true; }
-    if (c.dtype == MMHIP_BF16X3) { const char* v = getenv("MMHIP_X3_BWD"); const int n = v ? atoi(v) : 3; e->bwd_np = n >= 1 && n <= 3 ? n : 3; }
+    read_x3_env(*e);
     build_layout_txt(*e);
     build_workspace(*e);
     *out = e;

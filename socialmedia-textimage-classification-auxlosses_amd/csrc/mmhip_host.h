@@ -3,6 +3,7 @@
 // parity mode, the attention scale -- is written here once.  Host code only: no kernels, nothing that knows an engine struct; everything inline.
 #pragma once
 #include <cmath>
+#include <cstdlib>
 #include <initializer_list>
 #include <string>
 #include <vector>
@@ -22,6 +23,10 @@
     } while (0)
 
 namespace mmhip {
+
+// integer environment switch: atoi of the variable, `dflt` when it is unset.  Reads the environment on every call: whether a value is kept (a
+// function-level static, an engine field) or read again per call is the caller's choice
+inline int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
 
 // ------------------------------------------------------------------------------------------------ dropout
 // Drop when an element's 16 random bits < thresh16 = round(p * 65536), at most 65535; `on` = false (eval mode) or p = 0 turn it off (thresh16 = 0,
