@@ -383,6 +383,17 @@ int mmhip_op_attn_fwd(int dtype, const void* qkv, const float* maskbias, void* c
                       float p_drop, uint64_t seed, uint32_t stream_id, void* stream);
 int mmhip_op_attn_bwd(int dtype, const void* qkv, const float* maskbias, const void* ctx, const void* dctx, const float* lse,
                       void* dqkv, int posts, int S, int heads, float p_drop, uint64_t seed, uint32_t stream_id, void* stream);
+/* Self-attention backward at image length: 129 <= S <= 288 keys (ViT-B/16: 197, CLIP-ViT-L/14 @224: 257), head dimension 64, every matrix product on
+ * the matrix cores in all four forms -- MMHIP_BF16, MMHIP_F16, MMHIP_F32 (parity mode on fp32 tensors, three bf16 products per matrix product) and
+ * MMHIP_PAIR (the same on plane pairs).  Arguments, shapes and layouts are mmhip_op_attn_bwd's: qkv and dqkv [posts*S, 3*heads*64] packed q|k|v (pairs:
+ * rows [hi | lo] of twice that many bf16), ctx and dctx [posts*S, heads*64], maskbias fp32 [posts, S] additive (0 / -inf) or NULL, lse fp32
+ * [posts, heads, S] (natural log, as mmhip_op_attn_fwd writes it); p_drop / seed / stream_id replay that forward's dropout mask.  Every element of dqkv
+ * is written, each by one writer, from fp32 sums rounded once: a call repeated gives the same bits; dK and dV of a masked key are exact zeros.
+ * MMHIP_E_INVALID before any GPU work, nothing written: a NULL tensor or lse, posts < 1 (or > 65535), heads < 1, a dtype other than the four, S < 129
+ * or S > 288, qkv / ctx / dctx / dqkv off 16-byte alignment (every form; there is no vector-ALU kernel behind this entry).
+ * mmhip_op_attn_bwd is unchanged: S <= 128 on the matrix cores, fp32 tensors above that on the vector ALUs, 16-bit tensors and pairs above 128 rejected. */
+int mmhip_op_attn_bwd_long(int dtype, const void* qkv, const float* maskbias, const void* ctx, const void* dctx, const float* lse,
+                           void* dqkv, int posts, int S, int heads, float p_drop, uint64_t seed, uint32_t stream_id, void* stream);
 /* global-batch ITC on caller-owned buffers (no engine).  txt_n / img_n fp32 [G, E]: the gathered normalised rows; logit_scale a device scalar.
  * G <= 8192, E <= 1024, else MMHIP_E_INVALID with nothing written.  ws: scratch of mmhip_op_itc_global_ws_bytes(G, B_local) bytes (forward and
  * backward may share it).  Every call with the same inputs gives the same bits (ordered partial reductions, one writer per word).

@@ -127,6 +127,7 @@ _SIGS = {
     "mmhip_op_layernorm_bwd": (I, [I, P, P, P, P, P, P, P, P, P, I, I, P]),
     "mmhip_op_attn_fwd": (I, [I, P, P, P, P, I, I, I, F, U64, U32, P]),
     "mmhip_op_attn_bwd": (I, [I, P, P, P, P, P, P, I, I, I, F, U64, U32, P]),
+    "mmhip_op_attn_bwd_long": (I, [I, P, P, P, P, P, P, I, I, I, F, U64, U32, P]),
     "mmhip_op_itc_global_ws_bytes": (U64, [I, I]),
     "mmhip_op_itc_fwd": (I, [P, P, P, I, I, P, P, P, P, P, P]),
     "mmhip_op_itc_bwd": (I, [P, P, P, P, P, P, P, I, I, P, P, P, P]),

@@ -8,6 +8,7 @@
 //
 // Backward (text tower only, S <= 128): wave w owns key tile w; S = Q.K^T and dP = dO.V^T are computed with the key on
 // the lane, so P and dS are the B operands of dV^T = dO^T.P and dK^T = Q^T.dS; only dS crosses LDS, once, for dQ.
+// Backward at image length (129 <= S <= 288, its own launcher launch_attn_bwd_long): a key role and a query role, at the end of this file.
 #include "mmhip_common.h"
 #include "mmhip_kernels.h"
 
@@ -979,6 +980,318 @@ hipError_t launch_attn_bwd(const AttnBwdArgs& a, int dtype, hipStream_t s) {
         return hipGetLastError();
     }
     return dtype == DT_BF16 ? launch_bwd_d<bf16_t>(a, s) : launch_bwd_d<f16_t>(a, s);
+}
+
+// ------------------------------------------------------------------------------------------------ long backward (129 .. 288 keys)
+// Self-attention backward at image length, two roles (two kernels on one stream), every matrix product on MFMA, no reduction across workgroups:
+//   * key role    -- a workgroup owns a chunk of at most four 32-key tiles (wave w: tile chunk * tpc + w), keeps the Q and dO images of ALL queries in
+//                    LDS and walks the query tiles exactly as attn_bwd_kernel does: S = Q.K^T and dP = dO.V^T with the key on the lane, P and dS as the
+//                    B operands of dV^T = dO^T.P and dK^T = Q^T.dS.  dK / dV stay in fp32 registers over all queries and are stored once.
+//   * query role  -- a workgroup owns a chunk of at most four 32-query tiles (one per wave), keeps the K and V images of ALL keys in LDS and walks the key
+//                    tiles as the forward does: S^T = K.Q^T and dP^T = V.dO^T with the query on the lane, so the dS^T accumulator tile is, once
+//                    rounded, the B operand of dQ^T = K^T.dS^T.  dQ stays in fp32 registers over all keys and is stored once.
+// The scores are computed twice (once per role); nothing but the staged images crosses LDS, no barrier follows the staging, every output word has one
+// writer.  The key tiles (resp. query tiles) are spread evenly over ceil(tiles / 4) chunks: 5 -> 3 + 2, 7 -> 4 + 3, 9 -> 3 + 3 + 3.
+// LDS: two images of SP = 32 ceil(S / 32) rows (parity forms: four) + 8 (4) bytes per row: 76 032 B for the 16-bit forms, 149 760 B for the parity forms at 288.
+template <typename T> struct LongOp16 {          // bf16 / f16 tensors: one image per tensor, one product, P / dS rounded to T
+    typedef T elem;
+    typedef typename Vec<T>::v8 frag;
+    static constexpr int NIMG = 1;
+    static __device__ __forceinline__ void stage(char* img, int, const elem* src, int ld, int, int rv, int rp, bool tr, int tid) { stage_image<T>(img, src, ld, rv, rp, tr, tid, 256); }
+    static __device__ __forceinline__ frag gfrag(const elem* p, int) { return *reinterpret_cast<const frag*>(p); }
+    static __device__ __forceinline__ frag rfrag(const char* img, int, int off) { return lds_read8<T>(img, off); }
+    static __device__ __forceinline__ frag tfrag(const char* img, int, int r0, int c0, int lane) { return tr_frag_acc_order<T>(img, r0, c0, lane); }
+    static __device__ __forceinline__ frag pack(const float* v) {
+        frag f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[e] = from_f<T>(v[e]);
+        return f;
+    }
+    static __device__ __forceinline__ f32x16 mma(const frag& x, const frag& y, f32x16 c) { return mfma32(x, y, c); }
+    static __device__ __forceinline__ float dot64(const elem* o, const elem* g, int) {
+        float d = 0.f;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const frag ov = *reinterpret_cast<const frag*>(o + c * 8), gv = *reinterpret_cast<const frag*>(g + c * 8);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) d += to_f<T>(ov[e]) * to_f<T>(gv[e]);
+        }
+        return d;
+    }
+    static __device__ __forceinline__ void store4(elem* p, int, f32x4 v) {
+        typename Vec<T>::v4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = from_f<T>(v[e]);
+        *reinterpret_cast<typename Vec<T>::v4*>(p) = o;
+    }
+};
+template <bool PAIR> struct LongOp3 {            // parity mode: hi and lo images (the lo image `ib` bytes behind), three products, P / dS split in registers
+    typedef X3IO<PAIR> IO;
+    typedef typename IO::elem elem;
+    typedef Frag3 frag;
+    static constexpr int NIMG = 2;
+    static __device__ __forceinline__ void stage(char* img, int ib, const elem* src, int ld, int lo, int rv, int rp, bool tr, int tid) { IO::stage(img, img + ib, src, ld, lo, rv, rp, tr, tid, 256); }
+    static __device__ __forceinline__ frag gfrag(const elem* p, int lo) { return IO::frag(p, lo); }
+    static __device__ __forceinline__ frag rfrag(const char* img, int ib, int off) { return lds_pair(img, img + ib, off); }
+    static __device__ __forceinline__ frag tfrag(const char* img, int ib, int r0, int c0, int lane) {
+        Frag3 f;
+        f.hi = tr_frag_acc_order<bf16_t>(img, r0, c0, lane);
+        f.lo = tr_frag_acc_order<bf16_t>(img + ib, r0, c0, lane);
+        return f;
+    }
+    static __device__ __forceinline__ frag pack(const float* v) { return split8(v); }
+    static __device__ __forceinline__ f32x16 mma(const frag& x, const frag& y, f32x16 c) { return mma3_32(x, y, c); }
+    static __device__ __forceinline__ float dot64(const elem* o, const elem* g, int lo) {
+        float d = 0.f;
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            const f32x4 ov = IO::load4(o + c * 4, lo), gv = IO::load4(g + c * 4, lo);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) d += ov[e] * gv[e];
+        }
+        return d;
+    }
+    static __device__ __forceinline__ void store4(elem* p, int lo, f32x4 v) { IO::store4(p, lo, v); }
+};
+// tiles [t0, t1) of chunk blockIdx.z when `nt` tiles are spread over gridDim.z chunks
+__device__ __forceinline__ int long_tiles_per_chunk(int nt) { return (nt + (int)gridDim.z - 1) / (int)gridDim.z; }
+
+template <typename OP, bool DROP>
+__global__ __launch_bounds__(256) void attn_bwd_long_kv_kernel(AttnBwdArgs a) {
+    typedef typename OP::elem E;
+    typedef typename OP::frag F;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int head = blockIdx.x, post = blockIdx.y;
+    const int S = a.S, nt = (S + 31) / 32, SP = nt * 32, IB = SP * 128;
+    char* Qimg = smem;                                   // [NIMG][SP][64] tr images: row reads for S / dP, transposing reads for dK / dV
+    char* dOimg = smem + OP::NIMG * IB;
+    float* lse2 = reinterpret_cast<float*>(smem + 2 * OP::NIMG * IB);      // lse * log2e
+    float* Dv = lse2 + SP;
+    const size_t row0 = (size_t)post * S;
+    const E* qb = (const E*)a.qkv + row0 * a.ld_qkv + head * HD;
+    const E* kb = qb + a.hidden;
+    const E* vb = kb + a.hidden;
+    const E* dob = (const E*)a.dctx + row0 * a.ld_ctx + head * HD;
+    const E* ob = (const E*)a.ctx + row0 * a.ld_ctx + head * HD;
+    OP::stage(Qimg, IB, qb, a.ld_qkv, a.lo_qkv, S, SP, true, tid);
+    OP::stage(dOimg, IB, dob, a.ld_ctx, a.lo_ctx, S, SP, true, tid);
+    for (int q = tid; q < SP; q += 256) {
+        float d = 0.f, l = 0.f;
+        if (q < S) {
+            d = OP::dot64(ob + (size_t)q * a.ld_ctx, dob + (size_t)q * a.ld_ctx, a.lo_ctx);
+            l = a.lse[((size_t)post * a.heads + head) * S + q] * LOG2E;
+        }
+        Dv[q] = d;
+        lse2[q] = l;
+    }
+    const int r = lane & 31, h2 = lane >> 5;
+    const int tpc = long_tiles_per_chunk(nt);
+    const int kt = (int)blockIdx.z * tpc + w;
+    const bool has_keys = w < tpc && kt < nt;
+    const int key = kt * 32 + r;
+    const int krow = min(key, S - 1);
+    F kf[4], vf[4];
+    float mbk = 0.f;
+    if (has_keys) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            kf[s] = OP::gfrag(kb + (size_t)krow * a.ld_qkv + 16 * s + 8 * h2, a.lo_qkv);
+            vf[s] = OP::gfrag(vb + (size_t)krow * a.ld_qkv + 16 * s + 8 * h2, a.lo_qkv);
+        }
+        mbk = (key < S) ? (a.maskbias ? a.maskbias[(size_t)post * S + key] : 0.f) : -INFINITY;
+        mbk *= LOG2E;
+    }
+    __syncthreads();
+    if (!has_keys) return;                               // no barrier below
+    const float sc = a.scale * LOG2E;
+    // dropout element of (query q, this lane's key) = e_lane + q * S in 32-bit wrap-around arithmetic, as in attn_bwd_kernel
+    const uint32_t e_lane = (uint32_t)(((size_t)post * a.heads + head) * S) * (uint32_t)S + (uint32_t)key + (uint32_t)(4 * h2) * (uint32_t)S;
+    f32x16 dk[2] = {f32x16{}, f32x16{}}, dv[2] = {f32x16{}, f32x16{}};
+#pragma unroll 1
+    for (int qt = 0; qt < nt; ++qt) {
+        const int q0 = qt * 32;
+        const uint32_t e_tile = e_lane + (uint32_t)q0 * (uint32_t)S;
+        f32x16 sacc = f32x16{}, pacc = f32x16{};
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int off = trimg_off(q0 + r, 2 * s + h2);
+            sacc = OP::mma(OP::rfrag(Qimg, IB, off), kf[s], sacc);        // S[q][key]
+            pacc = OP::mma(OP::rfrag(dOimg, IB, off), vf[s], pacc);       // dP[q][key]
+        }
+        // element reg <-> query q0 + (reg&3) + 8*(reg>>2) + 4*h2, key = this lane's key
+        float pdv[16], dsv[16];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const f32x4 l4 = *reinterpret_cast<const f32x4*>(lse2 + q0 + 8 * g + 4 * h2);
+            const f32x4 d4 = *reinterpret_cast<const f32x4*>(Dv + q0 + 8 * g + 4 * h2);
+            uint32_t e_el = e_tile + (uint32_t)g * (8u * (uint32_t)S);
+#pragma unroll
+            for (int e = 0; e < 4; ++e, e_el += (uint32_t)S) {
+                const int reg = 4 * g + e;
+                const int q = q0 + 8 * g + 4 * h2 + e;
+                float p = fast_exp2(sacc[reg] * sc + mbk - l4[e]);
+                if (q >= S) p = 0.f;
+                float pd = p, dpd = pacc[reg];
+                if (DROP) {
+                    const bool kp = mm_keep(e_el, a.drop);
+                    pd = kp ? p * a.drop.keep_scale : 0.f;
+                    dpd = kp ? dpd * a.drop.keep_scale : 0.f;
+                }
+                pdv[reg] = pd;
+                dsv[reg] = p * (dpd - d4[e]) * a.scale;
+            }
+        }
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+            const F pf = OP::pack(pdv + 8 * s2), dsf = OP::pack(dsv + 8 * s2);
+#pragma unroll
+            for (int dt = 0; dt < 2; ++dt) {
+                dv[dt] = OP::mma(OP::tfrag(dOimg, IB, q0 + 16 * s2, dt * 32, lane), pf, dv[dt]);      // dV^T += dO^T[d][q] . P[q][key]
+                dk[dt] = OP::mma(OP::tfrag(Qimg, IB, q0 + 16 * s2, dt * 32, lane), dsf, dk[dt]);      // dK^T += Q^T[d][q] . dS[q][key]
+            }
+        }
+    }
+    if (key < S) {
+        // dk[dt][reg] = dK(key, d = dt*32 + (reg&3) + 8*(reg>>2) + 4*h2)
+        E* dkp = (E*)a.dqkv + (row0 + key) * a.ld_qkv + a.hidden + head * HD;
+        E* dvp = dkp + a.hidden;
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                f32x4 o1, o2;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { o1[e] = dk[dt][4 * g + e]; o2[e] = dv[dt][4 * g + e]; }
+                OP::store4(dkp + dt * 32 + 8 * g + 4 * h2, a.lo_qkv, o1);
+                OP::store4(dvp + dt * 32 + 8 * g + 4 * h2, a.lo_qkv, o2);
+            }
+    }
+}
+
+template <typename OP, bool DROP>
+__global__ __launch_bounds__(256) void attn_bwd_long_q_kernel(AttnBwdArgs a) {
+    typedef typename OP::elem E;
+    typedef typename OP::frag F;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int head = blockIdx.x, post = blockIdx.y;
+    const int S = a.S, nt = (S + 31) / 32, SP = nt * 32, IB = SP * 128;
+    char* Kimg = smem;                                   // [NIMG][SP][64] tr images of K: row reads for S^T, transposing reads for dQ
+    char* Vimg = smem + OP::NIMG * IB;                   // row images of V
+    float* mb = reinterpret_cast<float*>(smem + 2 * OP::NIMG * IB);        // additive key bias * log2e
+    const size_t row0 = (size_t)post * S;
+    const E* qb = (const E*)a.qkv + row0 * a.ld_qkv + head * HD;
+    const E* kb = qb + a.hidden;
+    const E* dob = (const E*)a.dctx + row0 * a.ld_ctx + head * HD;
+    const E* ob = (const E*)a.ctx + row0 * a.ld_ctx + head * HD;
+    OP::stage(Kimg, IB, kb, a.ld_qkv, a.lo_qkv, S, SP, true, tid);
+    OP::stage(Vimg, IB, kb + a.hidden, a.ld_qkv, a.lo_qkv, S, SP, false, tid);
+    for (int k = tid; k < SP; k += 256) {
+        const float b = (k < S) ? (a.maskbias ? a.maskbias[(size_t)post * S + k] : 0.f) : -INFINITY;
+        mb[k] = b * LOG2E;
+    }
+    const int r = lane & 31, h2 = lane >> 5;
+    const int tpc = long_tiles_per_chunk(nt);
+    const int qt = (int)blockIdx.z * tpc + w;
+    const bool has_q = w < tpc && qt < nt;
+    const int q = qt * 32 + r;
+    const int qrow = min(q, S - 1);
+    F qf[4], gf[4];
+    float D = 0.f, l2 = 0.f;
+    if (has_q) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            qf[s] = OP::gfrag(qb + (size_t)qrow * a.ld_qkv + 16 * s + 8 * h2, a.lo_qkv);
+            gf[s] = OP::gfrag(dob + (size_t)qrow * a.ld_ctx + 16 * s + 8 * h2, a.lo_ctx);
+        }
+        D = OP::dot64(ob + (size_t)qrow * a.ld_ctx, dob + (size_t)qrow * a.ld_ctx, a.lo_ctx);      // the key role's sum, term for term
+        l2 = a.lse[((size_t)post * a.heads + head) * S + qrow] * LOG2E;
+    }
+    __syncthreads();
+    if (!has_q) return;                                  // no barrier below
+    const float sc = a.scale * LOG2E;
+    const uint32_t ebase = (uint32_t)(((size_t)post * a.heads + head) * S + (uint32_t)qrow) * (uint32_t)S;      // the forward's index of (this lane's query, key 0)
+    f32x16 dq[2] = {f32x16{}, f32x16{}};
+#pragma unroll 1
+    for (int kt = 0; kt < nt; ++kt) {
+        f32x16 sacc = f32x16{}, pacc = f32x16{};
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            sacc = OP::mma(OP::rfrag(Kimg, IB, trimg_off(kt * 32 + r, 2 * s + h2)), qf[s], sacc);       // S^T[key][q]
+            pacc = OP::mma(OP::rfrag(Vimg, IB, rowimg_off(kt * 32 + r, 2 * s + h2)), gf[s], pacc);      // dP^T[key][q]
+        }
+        // element reg <-> key kt*32 + (reg&3) + 8*(reg>>2) + 4*h2, query = this lane's query
+        float dsv[16];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const f32x4 b4 = *reinterpret_cast<const f32x4*>(mb + kt * 32 + 8 * g + 4 * h2);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int reg = 4 * g + e;
+                const float p = fast_exp2(sacc[reg] * sc + b4[e] - l2);
+                float dpd = pacc[reg];
+                if (DROP) dpd = mm_keep(ebase + (uint32_t)(kt * 32 + 8 * g + 4 * h2 + e), a.drop) ? dpd * a.drop.keep_scale : 0.f;
+                dsv[reg] = p * (dpd - D) * a.scale;
+            }
+        }
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+            const F dsf = OP::pack(dsv + 8 * s2);
+#pragma unroll
+            for (int dt = 0; dt < 2; ++dt) dq[dt] = OP::mma(OP::tfrag(Kimg, IB, kt * 32 + 16 * s2, dt * 32, lane), dsf, dq[dt]);      // dQ^T += K^T[d][key] . dS^T[key][q]
+        }
+    }
+    if (q < S) {
+        // dq[dt][reg] = dQ(query q, d = dt*32 + (reg&3) + 8*(reg>>2) + 4*h2)
+        E* dqp = (E*)a.dqkv + (row0 + q) * a.ld_qkv + head * HD;
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                f32x4 o;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] = dq[dt][4 * g + e];
+                OP::store4(dqp + dt * 32 + 8 * g + 4 * h2, a.lo_qkv, o);
+            }
+    }
+}
+
+static constexpr int LONG_BWD_MIN_S = 129, LONG_BWD_MAX_S = 288;
+template <typename OP, bool DROP>
+static hipError_t launch_bwd_long_od(const AttnBwdArgs& a, hipStream_t s) {
+    constexpr int lds_max = 2 * OP::NIMG * LONG_BWD_MAX_S * 128 + 2 * LONG_BWD_MAX_S * 4;
+    static bool done = false;
+    if (!done) {
+        (void)hipFuncSetAttribute((const void*)attn_bwd_long_kv_kernel<OP, DROP>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+        (void)hipFuncSetAttribute((const void*)attn_bwd_long_q_kernel<OP, DROP>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+        done = true;
+    }
+    const int nt = (a.S + 31) / 32, SP = nt * 32, chunks = (nt + 3) / 4;
+    const int img = 2 * OP::NIMG * SP * 128;
+    hipLaunchKernelGGL((attn_bwd_long_kv_kernel<OP, DROP>), dim3(a.heads, a.posts, chunks), dim3(256), img + 2 * SP * 4, s, a);
+    hipLaunchKernelGGL((attn_bwd_long_q_kernel<OP, DROP>), dim3(a.heads, a.posts, chunks), dim3(256), img + SP * 4, s, a);
+    return hipGetLastError();
+}
+template <typename OP>
+static hipError_t launch_bwd_long_o(const AttnBwdArgs& a, hipStream_t s) {
+    return a.drop.thresh16 ? launch_bwd_long_od<OP, true>(a, s) : launch_bwd_long_od<OP, false>(a, s);
+}
+hipError_t launch_attn_bwd_long(const AttnBwdArgs& a, int dtype, hipStream_t s) {
+    if (a.S < LONG_BWD_MIN_S || a.S > LONG_BWD_MAX_S || a.posts < 1 || a.posts > 65535 || a.heads < 1) return hipErrorInvalidValue;
+    if (a.hidden != a.heads * HD || a.ld_qkv % 8 || a.ld_ctx % 8) return hipErrorInvalidValue;
+    if (a.q_tiles || a.Sq_live || a.Sk_live || a.q_rps || a.kv_rps || a.ctx_rps || a.nprod == 1) return hipErrorInvalidValue;      // self-attention, three products
+    if (!a.qkv || !a.ctx || !a.dctx || !a.lse || !a.dqkv) return hipErrorInvalidValue;
+    // every form reads and writes 16-byte vectors and there is no vector-ALU kernel behind this launcher
+    if (((uintptr_t)a.qkv | (uintptr_t)a.ctx | (uintptr_t)a.dctx | (uintptr_t)a.dqkv) & 15) return hipErrorInvalidValue;
+    if (dtype == DT_F32) {
+        if (a.pair && (a.lo_qkv % 8 || a.lo_ctx % 8)) return hipErrorInvalidValue;
+        return a.pair ? launch_bwd_long_o<LongOp3<true>>(a, s) : launch_bwd_long_o<LongOp3<false>>(a, s);
+    }
+    if (a.pair) return hipErrorInvalidValue;
+    if (dtype == DT_BF16) return launch_bwd_long_o<LongOp16<bf16_t>>(a, s);
+    if (dtype == DT_F16) return launch_bwd_long_o<LongOp16<f16_t>>(a, s);
+    return hipErrorInvalidValue;
 }
 
 }  // namespace mmhip

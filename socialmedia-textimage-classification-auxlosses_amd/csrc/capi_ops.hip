@@ -324,6 +324,16 @@ int mmhip_op_attn_bwd(int dtype, const void* qkv, const float* maskbias, const v
     CHECK_HIP(launch_attn_bwd(a, dtype, (hipStream_t)stream));
     return 0;
 }
+int mmhip_op_attn_bwd_long(int dtype, const void* qkv, const float* maskbias, const void* ctx, const void* dctx, const float* lse,
+                           void* dqkv, int posts, int S, int heads, float p_drop, uint64_t seed, uint32_t stream_id, void* stream) {
+    if (!qkv || !ctx || !dctx || !lse || !dqkv || posts < 1 || posts > 65535 || heads < 1 || S < 129 || S > 288) return MMHIP_E_INVALID;
+    if (dtype != MMHIP_BF16 && dtype != MMHIP_F16 && dtype != MMHIP_F32 && dtype != MMHIP_PAIR) return MMHIP_E_INVALID;
+    if (((uintptr_t)qkv | (uintptr_t)ctx | (uintptr_t)dctx | (uintptr_t)dqkv) & 15) return MMHIP_E_INVALID;      // 16-byte vector accesses, no ALU kernel behind this entry
+    AttnBwdArgs a = attn_bwd_args(qkv, maskbias, ctx, dctx, lse, dqkv, posts, S, heads, heads * 64, make_drop(p_drop, seed, stream_id));
+    if (dtype == MMHIP_PAIR) { attn_pair(a, true); dtype = MMHIP_F32; }
+    CHECK_HIP(launch_attn_bwd_long(a, dtype, (hipStream_t)stream));
+    return 0;
+}
 int mmhip_op_colsum(int dtype, const void* x, int rows, int cols, int ld, float* out, void* stream) {
     if (!x || !out || (dtype != MMHIP_BF16 && dtype != MMHIP_F16 && dtype != MMHIP_F32)) return MMHIP_E_INVALID;      // (any other code would be read as fp32)
     CHECK_HIP(launch_colsum(x, rows, cols, ld, out, dtype, (hipStream_t)stream));

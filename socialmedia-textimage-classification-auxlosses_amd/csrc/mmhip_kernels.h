@@ -152,6 +152,11 @@ hipError_t launch_attn_fwd(const AttnArgs& a, int dtype, hipStream_t s);
 hipError_t launch_attn_fwd_f32(const AttnArgs& a, hipStream_t s);
 hipError_t launch_attn_bwd_f32(const AttnBwdArgs& a, hipStream_t s);
 hipError_t launch_attn_bwd(const AttnBwdArgs& a, int dtype, hipStream_t s);
+// self-attention backward at image length, 129 <= S <= 288, every product on MFMA (csrc/attention.hip "long backward").  dtype DT_BF16 | DT_F16 |
+// DT_F32 (parity mode: fp32 tensors, or plane pairs with a.pair).  hipErrorInvalidValue before any launch for: S outside the range; q_tiles, Sq_live,
+// Sk_live, q_rps, kv_rps or ctx_rps non-zero; nprod == 1; hidden != heads * 64; a leading dimension that is no multiple of 8; qkv / ctx / dctx / dqkv
+// off 16-byte alignment (no vector-ALU kernel stands behind this launcher).  launch_attn_bwd's own dispatch does not reach it.
+hipError_t launch_attn_bwd_long(const AttnBwdArgs& a, int dtype, hipStream_t s);
 
 // ---------------------------------------------------------------- row ops (LayerNorm, embeddings, elementwise)
 struct LNArgs {

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """GPU micro-benchmark of the non-GEMM kernels of the step -- LayerNorm forward / backward and self-attention forward / backward -- each alone on
 the chip, in the three element forms the engines use: bf16 (0), fp32 (2) and plane pairs (3: the parity mode's tensors).  Median per-launch time
-from HIP events over interleaved rounds, the algorithmic bytes of each launch and the HBM fraction they imply (8 TB/s spec).
+from HIP events over interleaved rounds, the algorithmic bytes of each launch and the HBM fraction they imply (8 TB/s spec).  Last section: the
+attention backward for 129..288 keys (mmhip_op_attn_bwd_long) in its four forms beside the vector-ALU path and the scaled 128-key kernels.
     python tools/rowop_bench.py [--rounds 15] > profiles/rNN_rowop_bench.txt"""
 import argparse
 import ctypes as C
@@ -107,6 +108,47 @@ def main():
                 tags.append("bwd " + NAME[dt])
         for tag, us in zip(tags, timed(fns, a.rounds)):
             print(f"attn posts {posts} S {S} p_drop {pdrop} {tag:9s} {us:8.1f} us")
+    long_backward(a.rounds)
+
+
+def attn_tensors(dt, posts, S, heads, pdrop):
+    """qkv, ctx, lse (written by the forward op), d ctx, dqkv of one attention problem in form dt"""
+    H, rows, w = heads * 64, posts * S, 2 if dt == 3 else 1
+    et = torch.float32 if dt == 2 else torch.float16 if dt == 1 else torch.bfloat16
+    qkv = (torch.randn(rows, 3 * H * w, device=dev) * 0.5).to(et)
+    ctx = torch.empty(rows, H * w, device=dev, dtype=et)
+    lse = torch.empty(posts * heads * S, device=dev)
+    dctx = (torch.randn(rows, H * w, device=dev) * 0.1).to(et)
+    assert lib.mmhip_op_attn_fwd(dt, p(qkv), None, p(ctx), p(lse), posts, S, heads, pdrop, 7, 3, st()) == 0
+    return qkv, ctx, lse, dctx, torch.empty_like(qkv)
+
+
+def long_backward(rounds):
+    """mmhip_op_attn_bwd_long (129..288 keys, matrix cores) in its four forms, beside the only path mmhip_op_attn_bwd has at those lengths (fp32 tensors
+    on the vector ALUs) and beside the 128-key kernels of each form scaled by the work, posts * heads * S^2"""
+    forms = {0: "bf16", 1: "f16", 2: "fp32", 3: "pair"}
+    print("## attention backward at image length: mmhip_op_attn_bwd_long; `alu` = mmhip_op_attn_bwd on fp32 tensors (vector ALUs), the only path before it")
+    print("# x128 = time / (the form's mmhip_op_attn_bwd at posts 64, S 128, 12 heads, p_drop 0.1, scaled by posts * heads * S^2); /alu = time / alu")
+
+    def bwd(name, dt, t, posts, S, heads, pdrop):
+        qkv, ctx, lse, dctx, dqkv = t
+        return lambda: getattr(lib, name)(dt, p(qkv), None, p(ctx), p(dctx), p(lse), p(dqkv), posts, S, heads, pdrop, 7, 3, st())
+
+    base = [attn_tensors(dt, 64, 128, 12, 0.1) for dt in forms]
+    t128 = dict(zip(forms, timed([bwd("mmhip_op_attn_bwd", dt, t, 64, 128, 12, 0.1) for dt, t in zip(forms, base)], rounds)))
+    for dt in forms:
+        print(f"attn posts 64 S 128 heads 12 p_drop 0.1 bwd {forms[dt]:5s} {t128[dt]:8.1f} us")
+    del base
+    for posts, S, heads in ((64, 197, 12), (32, 257, 16)):
+        for pdrop in (0.0, 0.1):
+            ts = [attn_tensors(dt, posts, S, heads, pdrop) for dt in forms]
+            fns = [bwd("mmhip_op_attn_bwd_long", dt, t, posts, S, heads, pdrop) for dt, t in zip(forms, ts)]
+            fns.append(bwd("mmhip_op_attn_bwd", 2, ts[2], posts, S, heads, pdrop))
+            us = timed(fns, rounds)
+            work = posts * heads * S * S / (64 * 12 * 128 * 128)
+            print(f"attn posts {posts} S {S} heads {heads} p_drop {pdrop} bwd alu   {us[-1]:8.1f} us")
+            for dt, t in zip(forms, us):
+                print(f"attn posts {posts} S {S} heads {heads} p_drop {pdrop} bwd_long {forms[dt]:5s} {t:8.1f} us   x128 {t / (t128[dt] * work):5.2f}   /alu {t / us[-1]:6.3f}")
 
 
 if __name__ == "__main__":
