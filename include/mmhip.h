@@ -554,6 +554,61 @@ int mmhip_op_cls_head_fwd(int x_dtype, const void* x, uint64_t x_stride, const f
 int mmhip_op_cls_head_bwd(int x_dtype, const void* x, uint64_t x_stride, const float* W, const float* d_logits, int B, int C, int H, float p, uint64_t seed,
                           float* dW, float* db, int dx_dtype, void* dx, uint64_t dx_stride, float dx_scale, int accumulate, void* stream);
 
+/* ==== image-only handle: the reference's image-only trainer (models/image_only.py, models/run_img.py --model_name vit) =====================
+ * HF ViTForImageClassification -- ViT without a pooler, classifier(layernorm(x)[:, 0, :]) -- as a TRAINABLE pre-LN tower on this engine's kernels:
+ * the image layers' forward launches of the late-fusion engine with their activations kept, a backward per layer (the attention backward is
+ * launch_attn_bwd_long: 129..288 tokens), the ViT embedding backward, the fused CLS classifier head of the text-only handle with p = 0.
+ * One flat fp32 parameter buffer (no frozen one), ordered [classifier, vit.layernorm | layers last -> first | patch weight, patch bias,
+ * position_embeddings, cls_token]; backward stage 0 = head + final LayerNorm, 1 .. L = the layers last -> first, L + 1 = the embeddings
+ * (mmhip_num_backward_stages / mmhip_stage_grad_range answer for it).  Every parameter is MMHIP_G_ALWAYS.  Names are the state-dict keys of
+ * transformers 4.25.1: vit.embeddings.*, vit.encoder.layer.N.*, vit.layernorm.*, classifier.*.
+ * Nothing random happens in a step: the checkpoint's tower dropouts are 0 and the reference never applies --dropout on this branch, so `train` changes
+ * nothing that is computed or kept: every forward runs on the per-layer saved buffer sets, and the flag is only recorded as the handle's mode.  With MMHIP_DETERMINISTIC=1 a step is bitwise reproducible.
+ * An image-only handle is an mmhip_handle: mmhip_backward_begin / _stage / _join_stage / _finish, the stage ranges and the per-handle setters that
+ * make sense -- guard, loss scale, backward products, side stream, step spans, GEMM timing -- take it; every other late-fusion or text-only call
+ * answers MMHIP_E_STATE / _INVALID, as mmhip_img_* do on the other handle kinds.
+ * mmhip_img_create answers MMHIP_E_INVALID for: a token count (image / patch)^2 + 1 outside 129 .. 288, a non-zero tower dropout, 3 * patch^2 no
+ * multiple of 64, num_labels > 16, and the hidden / heads / inter rules of mmhip_txt_create. */
+typedef struct mmhip_img_config {
+    int hidden, heads, inter, layers;    /* 768, 12, 3072, 12 */
+    int image, patch;                    /* 224, 16 */
+    float ln_eps;                        /* 1e-12 */
+    int num_labels;                      /* <= 16 */
+    int dtype;                           /* MMHIP_BF16 | MMHIP_F16 | MMHIP_BF16X3 */
+    int max_posts;                       /* capacity */
+    float loss_scale;                    /* as mmhip_config.loss_scale */
+    float p_hidden, p_attn;              /* the checkpoint's hidden_dropout_prob / attention_probs_dropout_prob: must be 0 (nothing here drops) */
+} mmhip_img_config;
+typedef mmhip_handle mmhip_img_handle;
+
+int mmhip_img_create(const mmhip_img_config* cfg, mmhip_img_handle* out);
+void mmhip_img_destroy(mmhip_img_handle h);
+int mmhip_img_param_count(mmhip_img_handle h);
+int mmhip_img_param_info_at(mmhip_img_handle h, int index, mmhip_param_info* out);     /* buffer is always 1 */
+uint64_t mmhip_img_numel(mmhip_img_handle h);
+uint64_t mmhip_img_workspace_bytes(mmhip_img_handle h);
+int mmhip_img_bind(mmhip_img_handle h, float* params, float* grad, void* workspace, uint64_t workspace_bytes);
+int mmhip_img_refresh_weights(mmhip_img_handle h, void* stream);
+/* pixels fp32 [B, 3, image, image]; logits fp32 [B, num_labels] (may be NULL) */
+int mmhip_img_forward(mmhip_img_handle h, const float* pixels, int B, int train, float* logits, void* stream);
+/* nn.CrossEntropyLoss(weight) on float one-hot targets of the last forward's logits, as mmhip_txt_loss */
+int mmhip_img_loss(mmhip_img_handle h, const int64_t* onehot, const float* class_w, float* loss, int* n_correct, void* stream);
+/* d_logits fp32 [B, num_labels], or NULL after the loss call; gradients are ADDED into `grad` (zero on entry) */
+int mmhip_img_backward(mmhip_img_handle h, const float* d_logits, void* stream);
+/* one fused step of ImageModel.train (models/image_only.py:179-218): forward with the loss in the head's launch -> backward -> per-layer AdamW +
+ * operand refresh on the side stream beside the stages below -> the remaining dense ranges.  Single process. */
+int mmhip_img_train_step(mmhip_img_handle h, const float* pixels, const int64_t* onehot, const float* class_w, int B, float* adam_m, float* adam_v,
+                         float lr, float beta1, float beta2, float eps, float weight_decay, int step, float* loss, int* n_correct, void* stream);
+/* Backward of the ViT token assembly alone (operator tests; csrc/rowops.hip launch_vit_embed_bwd).  dx [B*P, H] in `dtype` (MMHIP_BF16 | _F16 | _F32;
+ * MMHIP_PAIR reads fp32 like _F32).  dpos fp32 [P, H] += alpha * sum_b dx[b, p, :]; dcls fp32 [H] += alpha * sum_b dx[b, 0, :]; dpe [B*(P-1), H]: the
+ * patch rows, compact -- the same words for _BF16 / _F16 / _F32, rows [hi(H) | lo(H)] bf16 for _PAIR (pair_hi_only != 0: the hi plane alone).
+ * fp32 sums over the posts in ascending order, one writer per word, no atomics: a repeated call gives the same bits.  More than 8 posts are cut
+ * into slices of 8 whose partial rows go through `ws` (mmhip_op_vit_embed_bwd_ws_bytes; 0 for B <= 8; too small: MMHIP_E_CAPACITY).
+ * MMHIP_E_INVALID before any launch: H % 8 != 0 or H > 1024, P < 2, a NULL tensor, any pointer off 16-byte alignment. */
+uint64_t mmhip_op_vit_embed_bwd_ws_bytes(int B, int P, int H);
+int mmhip_op_vit_embed_bwd(int dtype, const void* dx, int B, int P, int H, float alpha, float* dpos, float* dcls, void* dpe, int pair_hi_only, void* ws,
+                           uint64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

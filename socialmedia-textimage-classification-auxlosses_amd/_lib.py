@@ -8,6 +8,7 @@ LIB_PATH = os.environ.get("MMHIP_LIB_PATH") or os.path.join(HERE, "libmmhip.so")
 
 BF16, F16, F32 = 0, 1, 2
 BF16X3 = 2          # as an engine dtype: the strict-parity mode (fp32 activations, bf16x3 matrix products; include/mmhip.h)
+PAIR = 3            # op-level entry points that say so only: the parity mode's tensors as bf16 plane pairs (MMHIP_PAIR)
 TXT_BERT, TXT_XLMR = 0, 1
 FUSION_CONCAT, FUSION_ATTENTION = 0, 1
 IMG_VIT, IMG_CLIP = 0, 1
@@ -36,6 +37,12 @@ class TxtConfig(C.Structure):        # include/mmhip.h: mmhip_txt_config
                 ("type_vocab", C.c_int), ("txt_kind", C.c_int), ("pad_id", C.c_int), ("ln_eps", C.c_float), ("num_labels", C.c_int),
                 ("p_hidden", C.c_float), ("p_attn", C.c_float), ("p_head", C.c_float), ("dtype", C.c_int), ("max_posts", C.c_int),
                 ("max_text_len", C.c_int), ("loss_scale", C.c_float)]
+
+
+class ImgConfig(C.Structure):        # include/mmhip.h: mmhip_img_config
+    _fields_ = [("hidden", C.c_int), ("heads", C.c_int), ("inter", C.c_int), ("layers", C.c_int), ("image", C.c_int), ("patch", C.c_int),
+                ("ln_eps", C.c_float), ("num_labels", C.c_int), ("dtype", C.c_int), ("max_posts", C.c_int), ("loss_scale", C.c_float),
+                ("p_hidden", C.c_float), ("p_attn", C.c_float)]
 
 
 class ParamInfo(C.Structure):
@@ -164,6 +171,20 @@ _SIGS = {
     "mmhip_txt_train_step": (I, [P, P, P, P, P, P, I, I, U64, P, P, F, F, F, F, F, I, P, P, P]),
     "mmhip_op_cls_head_fwd": (I, [I, P, U64, P, P, I, I, I, F, U64, P, P, P, P, P, P, P]),
     "mmhip_op_cls_head_bwd": (I, [I, P, U64, P, P, I, I, I, F, U64, P, P, I, P, U64, F, I, P]),
+    "mmhip_img_create": (I, [C.POINTER(ImgConfig), C.POINTER(P)]),
+    "mmhip_img_destroy": (None, [P]),
+    "mmhip_img_param_count": (I, [P]),
+    "mmhip_img_param_info_at": (I, [P, I, C.POINTER(ParamInfo)]),
+    "mmhip_img_numel": (U64, [P]),
+    "mmhip_img_workspace_bytes": (U64, [P]),
+    "mmhip_img_bind": (I, [P, P, P, P, U64]),
+    "mmhip_img_refresh_weights": (I, [P, P]),
+    "mmhip_img_forward": (I, [P, P, I, I, P, P]),
+    "mmhip_img_loss": (I, [P, P, P, P, P, P]),
+    "mmhip_img_backward": (I, [P, P, P]),
+    "mmhip_img_train_step": (I, [P, P, P, P, I, P, P, F, F, F, F, F, I, P, P, P]),
+    "mmhip_op_vit_embed_bwd_ws_bytes": (U64, [I, I, I]),
+    "mmhip_op_vit_embed_bwd": (I, [I, P, I, I, I, F, P, P, P, I, P, U64, P]),
     "mmhip_version": (C.c_char_p, []),
 }
 EXPORTS = tuple(_SIGS)

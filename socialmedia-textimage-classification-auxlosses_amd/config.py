@@ -25,6 +25,7 @@ metric_names = ["f1_weighted", "f1_macro", "precision_weighted", "precision_macr
 RES_PATH = "../results/"
 results_dir_mm_late = RES_PATH + "mm_late/"
 results_dir_txt = RES_PATH + "txt_only/"
+results_dir_img = RES_PATH + "img_only/"
 MODEL_DIR_DICT = {"bert": "../../../BERT-base/", "bertweet": "../../../BERTWEET-base/", "roberta": "../../../RoBERTa-base/",
                   "bernice": "../../../BERNICE/", "vit": "../../../ViT/", "beit": "../../../BEiT/", "deit": "../../../DEiT/",
                   "clip": "../../../CLIP-ViT-L-14/", "clip336": "../../../CLIP-ViT-L-14-336/",

@@ -409,4 +409,19 @@ int mmhip_op_cls_head_bwd(int x_dtype, const void* x, uint64_t x_stride, const f
     return r == hipErrorInvalidValue ? MMHIP_E_INVALID : (int)r;
 }
 
+// ------------------------------------------------------------------------------------------------ ViT embedding backward (image-only model)
+uint64_t mmhip_op_vit_embed_bwd_ws_bytes(int B, int P, int H) { return B < 1 || P < 1 || H < 1 ? 0 : (uint64_t)partial_floats_vit_embed(B, P, H) * 4; }
+int mmhip_op_vit_embed_bwd(int dtype, const void* dx, int B, int P, int H, float alpha, float* dpos, float* dcls, void* dpe, int pair_hi_only, void* ws,
+                           uint64_t ws_bytes, void* stream) {
+    if (B < 1 || P < 2 || H < 8 || H % 8 || H > 1024 || !dx || !dpos || !dcls || !dpe) return MMHIP_E_INVALID;
+    if (dtype != MMHIP_BF16 && dtype != MMHIP_F16 && dtype != MMHIP_F32 && dtype != MMHIP_PAIR) return MMHIP_E_INVALID;
+    const uint64_t need = mmhip_op_vit_embed_bwd_ws_bytes(B, P, H);
+    if (need && (!ws || ws_bytes < need)) return MMHIP_E_CAPACITY;
+    VitEmbedBwdArgs a{};
+    a.dx = dx; a.dpos = dpos; a.dcls = dcls; a.dpe = dpe; a.B = B; a.P = P; a.H = H; a.alpha = alpha; a.partial = need ? (float*)ws : nullptr;
+    if (dtype == MMHIP_PAIR) { a.pair = 1; a.pair_hi_only = pair_hi_only != 0; a.ld_pair = 2 * H; a.lo_pair = H; }
+    const hipError_t r = launch_vit_embed_bwd(a, dtype == MMHIP_PAIR ? DT_F32 : dtype, (hipStream_t)stream);
+    return r == hipErrorInvalidValue ? MMHIP_E_INVALID : (int)r;
+}
+
 }  // extern "C"

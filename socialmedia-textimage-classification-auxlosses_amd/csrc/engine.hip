@@ -22,6 +22,10 @@ struct TextAct {    // saved activations of one text layer (byte offsets into th
     size_t qkv, ctx, pre1, a1, u, h, pre2, out, mean1, rstd1, mean2, rstd2, lse;
     size_t a1p, outp;      // parity mode with plane pairs: the LayerNorm outputs once more as pairs (the fp32 forms stay the residual inputs)
 };
+struct ImgAct {     // saved activations of one trainable image layer (pre-LN): the layer's input stream, LN1 output (plane pairs: the pair alone), qkv, ctx,
+                    // the mid stream, LN2 output, the pre-GELU value u and the GELU output h; the layer's output is the next layer's x_in
+    size_t x_in, ln1, qkv, ctx, lse, x_mid, ln2, u, h, mean1, rstd1, mean2, rstd2;
+};
 
 }  // namespace
 
@@ -96,6 +100,22 @@ struct mmhip_engine {
     size_t tt_all = 0; bool has_tt = false;                  // the engine's clamped copy of the token type ids; the last forward was given some
                                                              // (has_tt is raised by txt_forward_impl alone: no late-fusion handle ever has it, so text_embed
                                                              // reads tt_all, which only a text-only workspace carves, on that handle kind only)
+    // image-only handle (mmhip_img_create): the image tower, trainable, under the fused CLS classifier head -- parameters under the keys of HF
+    // ViTForImageClassification (vit.*, classifier.*) in the trainable buffer, the tower's offsets in vit / v_*; no text tower, no frozen buffer
+    bool img_only = false;
+    std::vector<ImgAct> iact;
+    size_t i_xfin = 0, i_cls = 0, i_clsln = 0, i_mean = 0, i_rstd = 0, i_dcls = 0, i_dclsx = 0, i_dclsx_p = 0;      // last stream; CLS rows around the final LayerNorm
+    size_t i_dxs[3] = {0, 0, 0}, i_dxs_p[3] = {0, 0, 0};      // residual-stream gradients (+ their plane pairs): layer l reads [(l + 1) % 3], writes [l % 3]
+    size_t i_set[2][4];        // per layer parity, read by the side stream: du, dqkv, d mid stream, its plane pair
+    size_t i_dln = 0, i_dctx = 0, i_dpe = 0, i_epartial = 0;
+    // The weight-gradient products reduce over the rows of a batch, B * P of them -- 3152 at the reference's batch size of 16, no multiple of the tile
+    // kernels' 64-row slices.  Their operands therefore carry rows up to the next multiple of 64 (pad64), zero in both: the grouped tile kernel takes
+    // every batch size.  Nothing ever writes those rows; they are cleared when the batch size changes (i_pad_B: the B they were cleared for).
+    int i_pad_B = 0;
+    static size_t pad64(size_t rows) { return (rows + 63) & ~(size_t)63; }
+    int nl() const { return img_only ? cfg.layers_img : cfg.layers_txt; }                 // layers with a backward stage
+    const std::vector<LayerOff>& lay() const { return img_only ? vit : txt; }
+    const std::vector<LayerW16>& lay_w16() const { return img_only ? vit_w16 : txt_w16; }
     int cls_only = -1;         // -1 = read MMHIP_CLS_ONLY on first use; 1: the last text layer runs its post-attention part on CLS rows only
     bool cls_compact = false;  // state of the last forward
     int overlap = -1;          // -1 = read MMHIP_OVERLAP on first use
@@ -189,28 +209,27 @@ void add_clip_layer(ParamTable& b, int H, int I, int l, LayerOff& o) {
     o.ln2_b = b.add(p + "layer_norm2.bias", 0, g, {H});
     o.end = b.off[0];
 }
-void add_vit_layer(ParamTable& b, const mmhip_config& c, int l, LayerOff& o) {
-    const int H = c.hidden_img > 0 ? c.hidden_img : c.hidden, I = c.inter_img > 0 ? c.inter_img : c.inter;
-    const std::string p = "dual_encoder.vision_model.encoder.layer." + std::to_string(l) + ".";
-    const int g = MMHIP_G_FROZEN;
-    o.begin = b.off[0];
-    o.qkv_w = b.add(p + "attention.attention.query.weight", 0, g, {H, H});
-    b.add(p + "attention.attention.key.weight", 0, g, {H, H});
-    b.add(p + "attention.attention.value.weight", 0, g, {H, H});
-    o.qkv_b = b.add(p + "attention.attention.query.bias", 0, g, {H});
-    b.add(p + "attention.attention.key.bias", 0, g, {H});
-    b.add(p + "attention.attention.value.bias", 0, g, {H});
-    o.ao_w = b.add(p + "attention.output.dense.weight", 0, g, {H, H});
-    o.ao_b = b.add(p + "attention.output.dense.bias", 0, g, {H});
-    o.fc1_w = b.add(p + "intermediate.dense.weight", 0, g, {I, H});
-    o.fc1_b = b.add(p + "intermediate.dense.bias", 0, g, {I});
-    o.fc2_w = b.add(p + "output.dense.weight", 0, g, {H, I});
-    o.fc2_b = b.add(p + "output.dense.bias", 0, g, {H});
-    o.ln1_w = b.add(p + "layernorm_before.weight", 0, g, {H});
-    o.ln1_b = b.add(p + "layernorm_before.bias", 0, g, {H});
-    o.ln2_w = b.add(p + "layernorm_after.weight", 0, g, {H});
-    o.ln2_b = b.add(p + "layernorm_after.bias", 0, g, {H});
-    o.end = b.off[0];
+// HF ViTLayer under `prefix` (the frozen tower of the dual encoder; the trainable one of the image-only model) in buffer `buf`, group `g`
+void add_vit_layer(ParamTable& b, const std::string& prefix, int buf, int g, int H, int I, int l, LayerOff& o) {
+    const std::string p = prefix + "encoder.layer." + std::to_string(l) + ".";
+    o.begin = b.off[buf];
+    o.qkv_w = b.add(p + "attention.attention.query.weight", buf, g, {H, H});
+    b.add(p + "attention.attention.key.weight", buf, g, {H, H});
+    b.add(p + "attention.attention.value.weight", buf, g, {H, H});
+    o.qkv_b = b.add(p + "attention.attention.query.bias", buf, g, {H});
+    b.add(p + "attention.attention.key.bias", buf, g, {H});
+    b.add(p + "attention.attention.value.bias", buf, g, {H});
+    o.ao_w = b.add(p + "attention.output.dense.weight", buf, g, {H, H});
+    o.ao_b = b.add(p + "attention.output.dense.bias", buf, g, {H});
+    o.fc1_w = b.add(p + "intermediate.dense.weight", buf, g, {I, H});
+    o.fc1_b = b.add(p + "intermediate.dense.bias", buf, g, {I});
+    o.fc2_w = b.add(p + "output.dense.weight", buf, g, {H, I});
+    o.fc2_b = b.add(p + "output.dense.bias", buf, g, {H});
+    o.ln1_w = b.add(p + "layernorm_before.weight", buf, g, {H});
+    o.ln1_b = b.add(p + "layernorm_before.bias", buf, g, {H});
+    o.ln2_w = b.add(p + "layernorm_after.weight", buf, g, {H});
+    o.ln2_b = b.add(p + "layernorm_after.bias", buf, g, {H});
+    o.end = b.off[buf];
 }
 
 // text layers last -> first, then the embeddings: the tail of the trainable buffer in both layouts (the word table closes it)
@@ -255,7 +274,7 @@ void build_layout(mmhip_engine& e) {
         e.v_pos = b.add(vm + "embeddings.position_embeddings", 0, MMHIP_G_FROZEN, {1, P, Hv});
         e.v_patch_w = b.add(vm + "embeddings.patch_embeddings.projection.weight", 0, MMHIP_G_FROZEN, {Hv, 3, c.patch, c.patch});
         e.v_patch_b = b.add(vm + "embeddings.patch_embeddings.projection.bias", 0, MMHIP_G_FROZEN, {Hv});
-        for (int l = 0; l < c.layers_img; ++l) add_vit_layer(b, c, l, e.vit[l]);
+        for (int l = 0; l < c.layers_img; ++l) add_vit_layer(b, vm, 0, MMHIP_G_FROZEN, Hv, e.Iv(), l, e.vit[l]);
         e.v_ln_w = b.add(vm + "layernorm.weight", 0, MMHIP_G_FROZEN, {Hv});
         e.v_ln_b = b.add(vm + "layernorm.bias", 0, MMHIP_G_FROZEN, {Hv});
         e.v_pool_w = b.add(vm + "pooler.dense.weight", 0, MMHIP_G_FROZEN, {Hv, Hv});
@@ -310,6 +329,87 @@ void build_layout_txt(mmhip_engine& e) {
     e.n_train = b.off[1];
 }
 
+// HF ViTForImageClassification (the reference's image_only.py `vit` branch): no pooler; every parameter trains in one AdamW group.
+// Order: [classifier, vit.layernorm | layers last -> first | embeddings: patch weight, patch bias, position_embeddings, cls_token] -- the backward
+// finishes these address ranges in this order
+void build_layout_img(mmhip_engine& e) {
+    const mmhip_config& c = e.cfg;
+    const int H = e.Hv(), C = c.num_labels, P = e.P(), g = MMHIP_G_ALWAYS;
+    ParamTable b{e.params};
+    e.heads_begin = b.off[1];
+    e.lin_w = b.add("classifier.weight", 1, g, {C, H});
+    e.lin_b = b.add("classifier.bias", 1, g, {C});
+    e.v_ln_w = b.add("vit.layernorm.weight", 1, g, {H});
+    e.v_ln_b = b.add("vit.layernorm.bias", 1, g, {H});
+    e.heads_end = b.off[1];
+    e.vit.resize(c.layers_img);
+    for (int l = c.layers_img - 1; l >= 0; --l) add_vit_layer(b, "vit.", 1, g, H, e.Iv(), l, e.vit[l]);
+    e.emb_begin = b.off[1];
+    e.v_patch_w = b.add("vit.embeddings.patch_embeddings.projection.weight", 1, g, {H, 3, c.patch, c.patch});
+    e.v_patch_b = b.add("vit.embeddings.patch_embeddings.projection.bias", 1, g, {H});
+    e.v_pos = b.add("vit.embeddings.position_embeddings", 1, g, {1, P, H});
+    e.v_cls = b.add("vit.embeddings.cls_token", 1, g, {1, 1, H});
+    e.emb_end = b.off[1];
+    e.v_pool_w = e.v_pool_b = 0;
+    e.n_frozen = 0;
+    e.n_train = b.off[1];
+}
+
+// the image tower's share alone: operand copies with transposes, the activations a pre-LN backward needs, its gradient temporaries, the head's words
+void build_workspace_img(mmhip_engine& e) {
+    const mmhip_config& c = e.cfg;
+    const size_t H = e.Hv(), I = e.Iv(), C = c.num_labels, Bm = c.max_posts, P = e.P(), Kpp = e.Kpp(), Z = e.esz();
+    const size_t Mv = mmhip_engine::pad64(Bm * P), Mp = mmhip_engine::pad64(Bm * (P - 1));      // rows of every token / patch tensor: padded (i_pad_B)
+    Carver w;
+    e.vit_w16.resize(c.layers_img);
+    for (auto& L : e.vit_w16) {
+        L.qkv = w.take(3 * H * H * Z); L.ao = w.take(H * H * Z); L.fc1 = w.take(I * H * Z); L.fc2 = w.take(H * I * Z);
+        L.qkvT = w.take(3 * H * H * Z); L.aoT = w.take(H * H * Z); L.fc1T = w.take(I * H * Z); L.fc2T = w.take(H * I * Z);
+    }
+    e.patch_w16 = w.take(H * Kpp * Z);
+    e.v_patches = w.take(Mp * Kpp * Z); e.v_pe = w.take(Mp * H * Z);
+    e.iact.resize(c.layers_img);
+    for (auto& a : e.iact) {
+        a.x_in = w.take(Mv * H * Z); a.ln1 = w.take(Mv * H * Z); a.qkv = w.take(Mv * 3 * H * Z); a.ctx = w.take(Mv * H * Z);
+        a.lse = w.take(Bm * e.heads_v() * P * 4);
+        a.x_mid = w.take(Mv * H * Z); a.ln2 = w.take(Mv * H * Z); a.u = w.take(Mv * I * Z); a.h = w.take(Mv * I * Z);
+        a.mean1 = w.take(Mv * 4); a.rstd1 = w.take(Mv * 4); a.mean2 = w.take(Mv * 4); a.rstd2 = w.take(Mv * 4);
+    }
+    e.i_xfin = w.take(Mv * H * Z);
+    e.i_cls = w.take(Bm * H * Z); e.i_clsln = w.take(Bm * H * Z); e.i_mean = w.take(Bm * 4); e.i_rstd = w.take(Bm * 4);
+    e.i_dcls = w.take(Bm * H * Z); e.i_dclsx = w.take(Bm * H * Z);
+    if (e.px) e.i_dclsx_p = w.take(Bm * H * Z);
+    for (int i = 0; i < 3; ++i) {
+        e.i_dxs[i] = w.take(Mv * H * Z);
+        if (e.px) e.i_dxs_p[i] = w.take(Mv * H * Z);
+    }
+    for (int i = 0; i < 2; ++i) {
+        e.i_set[i][0] = w.take(Mv * I * Z); e.i_set[i][1] = w.take(Mv * 3 * H * Z); e.i_set[i][2] = w.take(Mv * H * Z);
+        e.i_set[i][3] = e.px ? w.take(Mv * H * Z) : 0;
+        for (int j = 0; j < 2; ++j) e.g_lnp[i][j] = w.take(partial_floats_rows((int)Mv, (int)H, 2) * 4);
+    }
+    e.i_dln = w.take(Mv * H * Z); e.i_dctx = w.take(Mv * H * Z); e.i_dpe = w.take(Mp * H * Z);
+    e.g_partial = w.take(partial_floats_rows((int)Bm, (int)H, 2) * 4);
+    e.i_epartial = w.take(partial_floats_vit_embed((int)Bm, (int)P, (int)H) * 4);
+    auto f = [&](size_t n) { return w.take(n * 4); };
+    e.h_out_cls = f(Bm * C); e.h_d_out_cls = f(Bm * C); e.h_loss = f(8);
+    e.splitk_ws = f((size_t)(I / 384 + 1) * 128 * (size_t)(I > 3 * H ? I : 3 * H)); e.has_splitk = true;
+    if (c.dtype == MMHIP_BF16X3 && !e.px) {
+        // parity mode without plane pairs: split planes of one GEMM call at a time per stream -- the widest NT problem (the patch GEMM included),
+        // the four weight-gradient problems of a layer together, or the patch weight's
+        size_t b = x3_nt_scratch_bytes((int)Mp, (int)H, (int)Kpp);
+        const size_t nk[5][2] = {{3 * H, H}, {H, H}, {I, H}, {H, I}, {H, 3 * H}};
+        for (auto& q : nk) { const size_t v = x3_nt_scratch_bytes((int)Mv, (int)q[0], (int)q[1]); if (v > b) b = v; }
+        const size_t tn = x3_tn_scratch_bytes((int)Mv, (int)H, (int)I) + x3_tn_scratch_bytes((int)Mv, (int)I, (int)H) + x3_tn_scratch_bytes((int)Mv, (int)(3 * H), (int)H) +
+                          x3_tn_scratch_bytes((int)Mv, (int)H, (int)H);
+        if (tn > b) b = tn;
+        const size_t tp = x3_tn_scratch_bytes((int)Mp, (int)H, (int)Kpp);
+        if (tp > b) b = tp;
+        e.x3_bytes[0] = e.x3_bytes[1] = b; e.x3_bytes[2] = 0;
+        for (int i = 0; i < 2; ++i) e.x3_ws[i] = w.take(b);
+    }
+    e.ws_need = e.ws_base = w.off;
+}
 
 void build_workspace(mmhip_engine& e) {
     const mmhip_config& c = e.cfg;
@@ -589,55 +689,77 @@ struct TextLayer {
 int vit_embed(mmhip_engine& e, const float* pixels, hipStream_t s) {
     const mmhip_config& c = e.cfg;
     const int H = e.Hv(), B = e.B, P = e.P(), Kpp = e.Kpp(), dt = e.dt();
-    const float* F = e.frozen;
+    const float* F = e.img_only ? e.train : e.frozen;
+    char* x0 = e.ws + (!e.img_only ? e.v_x : (c.layers_img ? e.iact[0].x_in : e.i_xfin));
     CHECK_HIP(launch_patchify(pixels, e.ws + e.v_patches, B, c.image, c.patch, Kpp, e.px ? DT_PAIR : dt, s));
     G g(e.ws + e.v_patches, Kpp, e.ws + e.patch_w16, Kpp, e.ws + e.v_pe, H, B * (P - 1), H, Kpp);
     if (!e.clip()) g.bias(F + e.v_patch_b);           // CLIP's patch conv has no bias
     g.px_in(e.px);
     part_gemm(e, g, 1);
     CHECK_RC(run_gemm(e, g, s));
-    CHECK_HIP(launch_vit_assemble(e.ws + e.v_pe, F + e.v_cls, F + e.v_pos, e.ws + e.v_x, B, P, H, dt, s));
+    CHECK_HIP(launch_vit_assemble(e.ws + e.v_pe, F + e.v_cls, F + e.v_pos, x0, B, P, H, dt, s));
     if (e.clip()) {
-        LNArgs ln{e.ws + e.v_x, e.ws + e.v_x, F + e.v_pre_ln_w, F + e.v_pre_ln_b, nullptr, nullptr, B * P, H, H, H, c.ln_eps_img};
+        LNArgs ln{x0, x0, F + e.v_pre_ln_w, F + e.v_pre_ln_b, nullptr, nullptr, B * P, H, H, H, c.ln_eps_img};
         CHECK_HIP(launch_layernorm_fwd(ln, dt, s));
     }
     return 0;
 }
 
-// The forward launches of image layer l (pre-LN: HF ViTLayer / CLIPEncoderLayer) on the residual stream v_x, in place.
+// The forward launches of image layer l (pre-LN: HF ViTLayer / CLIPEncoderLayer), written once over a buffer set.  The frozen tower of the late-fusion
+// model runs every layer on the SHARED set: the residual stream v_x in place, one LayerNorm / qkv / ctx / h buffer, nothing kept.  The trainable
+// tower of the image-only model gives each layer its OWN set (ImgAct): LayerNorm writes mean / rstd, attention its log-sum-exp, FC1 its pre-activation,
+// and the residual GEMMs write the next saved stream instead of in place.
+struct ImageBufs {
+    const float* W;                     // fp32 parameters (biases, LayerNorm)
+    char *x_in, *x_mid, *x_out;         // residual stream before the layer, after the attention block, after the MLP
+    char *ln1, *ln2, *qkv, *ctx, *h, *u;
+    float *lse, *mean1, *rstd1, *mean2, *rstd2;
+};
+inline ImageBufs image_bufs_shared(const mmhip_engine& e) {
+    char* x = e.ws + e.v_x;
+    return ImageBufs{e.frozen, x, x, x, e.ws + e.v_ln, e.ws + e.v_ln, e.ws + e.v_qkv, e.ws + e.v_ctx, e.ws + e.v_h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+}
+inline ImageBufs image_bufs_saved(const mmhip_engine& e, int l) {
+    const ImgAct& a = e.iact[l];
+    char* out = e.ws + (l + 1 < e.cfg.layers_img ? e.iact[l + 1].x_in : e.i_xfin);
+    return ImageBufs{e.train, e.ws + a.x_in, e.ws + a.x_mid, out, e.ws + a.ln1, e.ws + a.ln2, e.ws + a.qkv, e.ws + a.ctx, e.ws + a.h, e.ws + a.u,
+                     e.wsp<float>(a.lse), e.wsp<float>(a.mean1), e.wsp<float>(a.rstd1), e.wsp<float>(a.mean2), e.wsp<float>(a.rstd2)};
+}
 struct ImageLayer {
     const mmhip_engine& e;
     const LayerOff& o; const LayerW16& w;
+    const ImageBufs b;
     const float* F;
     const int H, I, Mv;
     const bool px;
-    char* x;
-    ImageLayer(const mmhip_engine& e, int l)
-        : e(e), o(e.vit[l]), w(e.vit_w16[l]), F(e.frozen), H(e.Hv()), I(e.Iv()), Mv(e.B * e.P()), px(e.px), x(e.ws + e.v_x) {}
+    ImageLayer(const mmhip_engine& e, int l) : ImageLayer(e, l, image_bufs_shared(e)) {}
+    ImageLayer(const mmhip_engine& e, int l, const ImageBufs& b)
+        : e(e), o(e.vit[l]), w(e.vit_w16[l]), b(b), F(b.W), H(e.Hv()), I(e.Iv()), Mv(e.B * e.P()), px(e.px) {}
     G part(G& g) const { part_gemm(e, g, 1); return g; }
-    int ln(size_t gamma, size_t beta, hipStream_t s) const {
-        LNArgs n{x, e.ws + e.v_ln, F + gamma, F + beta, nullptr, nullptr, Mv, H, H, H, e.cfg.ln_eps_img};
-        ln_pair(n, px, e.ws + e.v_ln, true);          // only GEMMs read it: the pair alone
+    int ln(const char* x, char* y, size_t gamma, size_t beta, float* mean, float* rstd, hipStream_t s) const {
+        LNArgs n{x, y, F + gamma, F + beta, mean, rstd, Mv, H, H, H, e.cfg.ln_eps_img};
+        ln_pair(n, px, y, true);          // only GEMMs read it: the pair alone
         CHECK_HIP(launch_layernorm_fwd(n, e.dt(), s));
         return 0;
     }
-    int ln1(hipStream_t s) const { return ln(o.ln1_w, o.ln1_b, s); }
-    int ln2(hipStream_t s) const { return ln(o.ln2_w, o.ln2_b, s); }
-    G qkv() const { return part(G(e.ws + e.v_ln, H, e.ws + w.qkv, H, e.ws + e.v_qkv, 3 * H, Mv, 3 * H, H).bias(F + o.qkv_b).px_in(px).px_out(px)); }
+    int ln1(hipStream_t s) const { return ln(b.x_in, b.ln1, o.ln1_w, o.ln1_b, b.mean1, b.rstd1, s); }
+    int ln2(hipStream_t s) const { return ln(b.x_mid, b.ln2, o.ln2_w, o.ln2_b, b.mean2, b.rstd2, s); }
+    G qkv() const { return part(G(b.ln1, H, e.ws + w.qkv, H, b.qkv, 3 * H, Mv, 3 * H, H).bias(F + o.qkv_b).px_in(px).px_out(px)); }
     int attention(hipStream_t s) const {
-        AttnArgs at = attn_args(e.ws + e.v_qkv, nullptr, e.ws + e.v_ctx, nullptr, e.B, e.P(), e.heads_v(), H);
+        AttnArgs at = attn_args(b.qkv, nullptr, b.ctx, b.lse, e.B, e.P(), e.heads_v(), H);
         attn_pair(at, px);
         CHECK_HIP(launch_attn_fwd(at, e.dt(), s));
         return 0;
     }
-    G attn_out() const { return part(G(e.ws + e.v_ctx, H, e.ws + w.ao, H, x, H, Mv, H, H).bias(F + o.ao_b).residual(x, H).px_in(px)); }
+    G attn_out() const { return part(G(b.ctx, H, e.ws + w.ao, H, b.x_mid, H, Mv, H, H).bias(F + o.ao_b).residual(b.x_in, H).px_in(px)); }
     G fc1() const {
-        G g(e.ws + e.v_ln, H, e.ws + w.fc1, H, e.ws + e.v_h, I, Mv, I, H);
+        G g(b.ln2, H, e.ws + w.fc1, H, b.h, I, Mv, I, H);
         g.bias(F + o.fc1_b);
+        if (b.u) g.aux(b.u, I);
         if (e.clip()) g.qgelu(); else g.gelu();
         return part(g.px_in(px).px_out(px));
     }
-    G fc2() const { return part(G(e.ws + e.v_h, I, e.ws + w.fc2, I, x, H, Mv, H, I).bias(F + o.fc2_b).residual(x, H).px_in(px)); }
+    G fc2() const { return part(G(b.h, I, e.ws + w.fc2, I, b.x_out, H, Mv, H, I).bias(F + o.fc2_b).residual(b.x_mid, H).px_in(px)); }
 };
 
 // closes the image tower: last hidden state in v_out, pooled feature in h_vpool
@@ -1125,6 +1247,188 @@ void read_x3_env(mmhip_engine& e) {
     e.bwd_np = n >= 1 && n <= 3 ? n : 3;
 }
 
+// ------------------------------------------------------------------------------------------------ image-only handle: forward and backward pieces
+// clears the pad rows (mmhip_engine::i_pad_B) of every operand of a weight-gradient product for B posts
+int img_zero_pads(mmhip_engine& e, int B, hipStream_t s) {
+    const size_t H = e.Hv(), I = e.Iv(), P = e.P(), Z = e.esz();
+    const size_t Mv = B * P, Mvp = mmhip_engine::pad64(Mv), Mp = (size_t)B * (P - 1), Mpp = mmhip_engine::pad64(Mp);
+    auto clear = [&](size_t off, size_t rows, size_t rows_padded, size_t width) -> int {
+        if (rows_padded > rows) CHECK_HIP(hipMemsetAsync(e.ws + off + rows * width * Z, 0, (rows_padded - rows) * width * Z, s));
+        return 0;
+    };
+    for (const ImgAct& a : e.iact) {
+        CHECK_RC(clear(a.ln1, Mv, Mvp, H)); CHECK_RC(clear(a.ln2, Mv, Mvp, H)); CHECK_RC(clear(a.ctx, Mv, Mvp, H)); CHECK_RC(clear(a.h, Mv, Mvp, I));
+    }
+    for (int i = 0; i < 3; ++i) {
+        CHECK_RC(clear(e.i_dxs[i], Mv, Mvp, H));
+        if (e.px) CHECK_RC(clear(e.i_dxs_p[i], Mv, Mvp, H));
+    }
+    for (int i = 0; i < 2; ++i) {
+        CHECK_RC(clear(e.i_set[i][0], Mv, Mvp, I)); CHECK_RC(clear(e.i_set[i][1], Mv, Mvp, 3 * H)); CHECK_RC(clear(e.i_set[i][2], Mv, Mvp, H));
+        if (e.px) CHECK_RC(clear(e.i_set[i][3], Mv, Mvp, H));
+    }
+    CHECK_RC(clear(e.v_patches, Mp, Mpp, e.Kpp()));
+    CHECK_RC(clear(e.i_dpe, Mp, Mpp, H));
+    e.i_pad_B = B;
+    return 0;
+}
+
+// the tower on per-layer buffer sets (ImageLayer), the same launch order as vit_forward
+int img_tower_forward(mmhip_engine& e, const float* pixels, hipStream_t s) {
+    CHECK_RC(vit_embed(e, pixels, s));
+    for (int l = 0; l < e.cfg.layers_img; ++l) {
+        const ImageLayer v(e, l, image_bufs_saved(e, l));
+        CHECK_RC(v.ln1(s));
+        CHECK_RC(run_gemm(e, v.qkv(), s));
+        CHECK_RC(v.attention(s));
+        CHECK_RC(run_gemm(e, v.attn_out(), s));
+        CHECK_RC(v.ln2(s));
+        CHECK_RC(run_gemm(e, v.fc1(), s));
+        CHECK_RC(run_gemm(e, v.fc2(), s));
+    }
+    return 0;
+}
+// classifier(layernorm(x)[:, 0, :]): the B CLS rows gathered, the final LayerNorm on them alone (no other row of it is consumed), the fused head, p = 0
+ClsHeadArgs img_head_args(const mmhip_engine& e) {
+    return cls_head(e.ws + e.i_clsln, (size_t)e.Hv(), e.dt(), e.train + e.lin_w, e.B, e.cfg.num_labels, e.Hv(), make_drop(0.f, 0, STREAM_HEAD, false));
+}
+int img_head_classify(mmhip_engine& e, const int64_t* onehot, const float* class_w, float* logits, float* loss, int* n_correct, hipStream_t s) {
+    ClsHeadArgs a = img_head_args(e);
+    a.bias = e.train + e.lin_b; a.logits = e.wsp<float>(e.h_out_cls);
+    if (onehot) {
+        a.onehot = onehot; a.class_w = class_w; a.loss = e.wsp<float>(e.h_loss); a.n_correct = n_correct; a.d_logits_out = e.wsp<float>(e.h_d_out_cls);
+    }
+    CHECK_HIP(launch_cls_head_fwd(a, s));
+    if (logits) CHECK_HIP(hipMemcpyAsync(logits, a.logits, (size_t)e.B * e.cfg.num_labels * 4, hipMemcpyDeviceToDevice, s));
+    if (onehot && loss) CHECK_HIP(hipMemcpyAsync(loss, a.loss, 4, hipMemcpyDeviceToDevice, s));
+    if (onehot) e.bd_out_cls = a.d_logits_out;
+    return 0;
+}
+int img_head_forward(mmhip_engine& e, const int64_t* onehot, const float* class_w, float* logits, float* loss, int* n_correct, hipStream_t s) {
+    const int H = e.Hv(), B = e.B, P = e.P();
+    const size_t rb = (size_t)H * e.esz();
+    CHECK_HIP(hipMemcpy2DAsync(e.ws + e.i_cls, rb, e.ws + e.i_xfin, (size_t)P * rb, rb, B, hipMemcpyDeviceToDevice, s));
+    LNArgs n{e.ws + e.i_cls, e.ws + e.i_clsln, e.train + e.v_ln_w, e.train + e.v_ln_b, e.wsp<float>(e.i_mean), e.wsp<float>(e.i_rstd), B, H, H, H, e.cfg.ln_eps_img};
+    CHECK_HIP(launch_layernorm_fwd(n, e.dt(), s));
+    return img_head_classify(e, onehot, class_w, logits, loss, n_correct, s);
+}
+// stage 0: head, final LayerNorm on the B rows, and the gradient of the last stream: zero but for the CLS rows
+int img_head_backward(mmhip_engine& e, hipStream_t s) {
+    const int H = e.Hv(), B = e.B, P = e.P(), L = e.cfg.layers_img, dt = e.dt();
+    const bool px = e.px, hi1 = px && e.bwd_np == 1;
+    ClsHeadArgs a = img_head_args(e);
+    a.d_logits = e.bd_out_cls; a.dW = e.grad + e.lin_w; a.db = e.grad + e.lin_b; a.accumulate = 1;
+    a.dx = e.ws + e.i_dcls; a.dx_stride = H; a.dx_dtype = dt; a.dx_scale = e.gscale();
+    CHECK_HIP(launch_cls_head_bwd(a, s));
+    LNBwdArgs b{e.ws + e.i_dcls, e.ws + e.i_cls, e.train + e.v_ln_w, e.wsp<float>(e.i_mean), e.wsp<float>(e.i_rstd), e.ws + e.i_dclsx, nullptr,
+                e.grad + e.v_ln_w, e.grad + e.v_ln_b, B, H, e.wsp<float>(e.g_partial), 1.0f / e.gscale(), nullptr, nullptr, make_drop(0.f, 0, 0, false), 1, 0};
+    ln_bwd_pair(b, px, e.ws + e.i_dclsx_p, hi1);
+    CHECK_HIP(launch_layernorm_bwd(b, dt, s));
+    const size_t bytes = (size_t)B * P * H * e.esz();
+    CHECK_HIP(hipMemsetAsync(e.ws + e.i_dxs[L % 3], 0, bytes, s));
+    CHECK_HIP(launch_scatter_rows16(e.ws + e.i_dclsx, e.ws + e.i_dxs[L % 3], B, (size_t)P * H, H, 0, dt, s));
+    if (px) {          // the pair the layer's GEMMs read: rows of 2 H bf16 moved as the H 4-byte words they occupy; an all-zero pair is zero
+        CHECK_HIP(hipMemsetAsync(e.ws + e.i_dxs_p[L % 3], 0, bytes, s));
+        CHECK_HIP(launch_scatter_rows16(e.ws + e.i_dclsx_p, e.ws + e.i_dxs_p[L % 3], B, (size_t)P * H, H, 0, DT_F32, s));
+    }
+    return 0;
+}
+
+// One pre-LN image layer: x_mid = x_in + Wo ctx(LN1(x_in)),  x_out = x_mid + W2 gelu(W1 LN2(x_mid)).  On entry the gradient of x_out is in the
+// stream-gradient buffer (l + 1) % 3, on exit that of x_in in l % 3 (three of them: the layer's weight-gradient launch on the side stream still reads
+// the first while the layer below writes its own).  LNBwdArgs::dres adds the residual branch's gradient inside the LayerNorm backward.
+int image_layer_backward(mmhip_engine& e, int l, hipStream_t s) {
+    const int H = e.Hv(), I = e.Iv(), B = e.B, P = e.P(), Mv = B * P, dt = e.dt();
+    const float* W = e.train;
+    float* Gd = e.grad;
+    const LayerOff& o = e.vit[l];
+    const LayerW16& w = e.vit_w16[l];
+    const ImgAct& a = e.iact[l];
+    const bool px = e.px;
+    const int np = e.bwd_np;
+    const bool hi1 = px && np == 1;          // every reader takes one product: lo planes not written (d ctx excepted: the attention backward keeps three)
+    const int set = l & 1;
+    const bool side = use_side(e);
+    const int di = (l + 1) % 3, dn = l % 3;
+    char *dx = e.ws + e.i_dxs[di], *dxg = px ? e.ws + e.i_dxs_p[di] : dx;                      // fp32 / 16-bit form, and as the GEMMs read it
+    char *dxo = e.ws + e.i_dxs[dn], *dxo_p = e.ws + e.i_dxs_p[dn];
+    char *du = e.ws + e.i_set[set][0], *dqkv = e.ws + e.i_set[set][1], *dxmid = e.ws + e.i_set[set][2];
+    char *dxmid_g = px ? e.ws + e.i_set[set][3] : dxmid;
+    char *dln = e.ws + e.i_dln, *dctx = e.ws + e.i_dctx;
+    if (side && e.tn_pending[set]) {           // the set was last read by layer l+2's side work
+        CHECK_HIP(hipStreamWaitEvent(s, e.ev_tn[set], 0));
+        e.tn_pending[set] = false;
+    }
+    const DropCfg nodrop = make_drop(0.f, 0, 0, false);
+    // du = (dx . W2) * gelu'(u);  d ln2 = du . W1;  dx_mid = LNbwd(d ln2; x_mid) + dx
+    CHECK_RC(run_gemm(e, G(dxg, H, e.ws + w.fc2T, H, du, I, Mv, I, H).mul_gelu_grad(e.ws + a.u, I).px_in(px, np).px_out(px, hi1), s));
+    CHECK_RC(run_gemm(e, G(du, I, e.ws + w.fc1T, I, dln, H, Mv, H, I).px_in(px, np), s));
+    LNBwdArgs b2{dln, e.ws + a.x_mid, W + o.ln2_w, e.wsp<float>(a.mean2), e.wsp<float>(a.rstd2), dxmid, dx, Gd + o.ln2_w, Gd + o.ln2_b, Mv, H,
+                 e.wsp<float>(e.g_lnp[set][0]), 1.0f / e.gscale(), nullptr, nullptr, nodrop, 1, 1};
+    ln_bwd_pair(b2, px, dxmid_g, hi1);
+    CHECK_HIP(launch_layernorm_bwd(b2, dt, s));
+    // d ctx = dx_mid . Wo;  attention backward (129 .. 288 tokens: three products at every policy);  d ln1 = dqkv . Wqkv;  dx_in = LNbwd(d ln1; x_in) + dx_mid
+    CHECK_RC(run_gemm(e, G(dxmid_g, H, e.ws + w.aoT, H, dctx, H, Mv, H, H).px_in(px, np).px_out(px), s));
+    AttnBwdArgs ab = attn_bwd_args(e.ws + a.qkv, nullptr, e.ws + a.ctx, dctx, e.wsp<float>(a.lse), dqkv, B, P, e.heads_v(), H);
+    attn_pair(ab, px, np == 1 ? 3 : np);
+    CHECK_HIP(launch_attn_bwd_long(ab, dt, s));
+    CHECK_RC(run_gemm(e, G(dqkv, 3 * H, e.ws + w.qkvT, 3 * H, dln, H, Mv, H, 3 * H).px_in(px, np), s));
+    LNBwdArgs b1{dln, e.ws + a.x_in, W + o.ln1_w, e.wsp<float>(a.mean1), e.wsp<float>(a.rstd1), dxo, dxmid, Gd + o.ln1_w, Gd + o.ln1_b, Mv, H,
+                 e.wsp<float>(e.g_lnp[set][1]), 1.0f / e.gscale(), nullptr, nullptr, nodrop, 1, 1};
+    ln_bwd_pair(b1, px, dxo_p, hi1);
+    CHECK_HIP(launch_layernorm_bwd(b1, dt, s));
+    // ---- parameter gradients of the layer, off the dX chain -> side stream: the four weight gradients with their bias gradients in one grouped
+    // launch (no split-K, plain stores) and the second stage of the two LayerNorm reductions
+    hipStream_t ps = s;
+    if (side) {
+        CHECK_HIP(hipEventRecord(e.ev_ready[set], s));
+        CHECK_HIP(hipStreamWaitEvent(e.side, e.ev_ready[set], 0));
+        ps = e.side;
+    }
+    CHECK_HIP(launch_layernorm_bwd_reduce(b2, ps));
+    CHECK_HIP(launch_layernorm_bwd_reduce(b1, ps));
+    GemmTNProblem pr[4];
+    const int Mr = (int)mmhip_engine::pad64((size_t)Mv);          // reduction length with the zero pad rows (i_pad_B)
+    pr[0] = GemmTNProblem{dxg, e.ws + a.h, Gd + o.fc2_w, Mr, H, I, H, I, I, 0, Gd + o.fc2_b};               // dW2[H,I]    = dx^T h
+    pr[1] = GemmTNProblem{du, e.ws + a.ln2, Gd + o.fc1_w, Mr, I, H, I, H, H, 0, Gd + o.fc1_b};              // dW1[I,H]    = du^T ln2
+    pr[2] = GemmTNProblem{dqkv, e.ws + a.ln1, Gd + o.qkv_w, Mr, 3 * H, H, 3 * H, H, H, 0, Gd + o.qkv_b};    // dWqkv[3H,H] = dqkv^T ln1
+    pr[3] = GemmTNProblem{dxmid_g, e.ws + a.ctx, Gd + o.ao_w, Mr, H, H, H, H, H, 0, Gd + o.ao_b};           // dWo[H,H]    = dx_mid^T ctx
+    if (px) for (auto& q : pr) tn_pair(q, np);
+    {
+        const int i = e.side && ps == e.side ? 1 : 0;
+        CHECK_HIP(launch_gemm_tn(pr, 4, 0, dt, 0, ps, 1.0f / e.gscale(), e.x3_bytes[i] ? e.ws + e.x3_ws[i] : nullptr, e.x3_bytes[i]));
+    }
+    if (side) {
+        CHECK_HIP(hipEventRecord(e.ev_tn[set], e.side));
+        e.tn_pending[set] = true;
+    }
+    return 0;
+}
+
+// stage L + 1: d position_embeddings, d cls_token and the compact patch-row gradient in one launch; the patch weight's gradient with its bias
+// gradient as one more weight-gradient problem against the forward's patchified pixels (still intact in v_patches)
+int img_embed_backward(mmhip_engine& e, hipStream_t s) {
+    const int H = e.Hv(), B = e.B, P = e.P(), Kpp = e.Kpp(), dt = e.dt();
+    const bool px = e.px;
+    VitEmbedBwdArgs v{};
+    v.dx = e.ws + e.i_dxs[0]; v.dpos = e.grad + e.v_pos; v.dcls = e.grad + e.v_cls; v.dpe = e.ws + e.i_dpe;
+    v.B = B; v.P = P; v.H = H; v.alpha = 1.0f / e.gscale();
+    v.partial = partial_floats_vit_embed(B, P, H) ? e.wsp<float>(e.i_epartial) : nullptr;
+    if (px) { v.pair = 1; v.pair_hi_only = e.bwd_np == 1; v.ld_pair = 2 * H; v.lo_pair = H; }
+    CHECK_HIP(launch_vit_embed_bwd(v, dt, s));
+    GemmTNProblem pr{e.ws + e.i_dpe, e.ws + e.v_patches, e.grad + e.v_patch_w, (int)mmhip_engine::pad64((size_t)B * (P - 1)), H, Kpp, H, Kpp, Kpp, 0,
+                     e.grad + e.v_patch_b};          // (zero pad rows: i_pad_B)
+    if (px) tn_pair(pr, e.bwd_np);
+    CHECK_HIP(launch_gemm_tn(&pr, 1, 0, dt, 0, s, 1.0f / e.gscale(), e.x3_bytes[0] ? e.ws + e.x3_ws[0] : nullptr, e.x3_bytes[0]));
+    return 0;
+}
+
+int img_refresh(mmhip_engine& e, hipStream_t s) {
+    for (int l = 0; l < e.cfg.layers_img; ++l) CHECK_RC(refresh_layer(e, e.train, e.vit[l], e.vit_w16[l], true, s, e.Hv(), e.Iv()));
+    CHECK_HIP(launch_cast_pad(e.train + e.v_patch_w, e.ws + e.patch_w16, e.Hv(), e.Kp(), e.Kpp(), e.px ? DT_PAIR : e.dt(), s));
+    return 0;
+}
+
 }  // namespace
 
 // ================================================================================================ C ABI
@@ -1182,7 +1486,7 @@ uint64_t mmhip_buffer_numel(mmhip_handle h, int buffer) { return !h ? 0 : (buffe
 uint64_t mmhip_workspace_bytes(mmhip_handle h) { return h ? h->ws_need : 0; }
 int mmhip_reserve_itc_global(mmhip_handle h, int max_world) {
     if (!h || max_world < 0) return MMHIP_E_INVALID;
-    if (h->ws || h->txt_only) return MMHIP_E_STATE;          // the workspace is sized before it is bound
+    if (h->ws || h->txt_only || h->img_only) return MMHIP_E_STATE;          // the workspace is sized before it is bound
     mmhip_engine& e = *h;
     const size_t Bm = e.cfg.max_posts, E = e.cfg.proj_dim, Gm = (size_t)max_world * Bm;
     if (max_world > 1 && Gm > (size_t)ITC_GLOBAL_MAX_G) return MMHIP_E_INVALID;
@@ -1199,13 +1503,13 @@ int mmhip_reserve_itc_global(mmhip_handle h, int max_world) {
 }
 int mmhip_set_itc_global(mmhip_handle h, int world, int rank) {
     if (!h || world < 1 || rank < 0 || rank >= world) return MMHIP_E_INVALID;
-    if (h->txt_only) return MMHIP_E_STATE;
+    if (h->txt_only || h->img_only) return MMHIP_E_STATE;
     if (world > 1 && world > h->itc_max_world) return MMHIP_E_CAPACITY;
     h->itc_world = world; h->itc_rank = rank;
     return 0;
 }
 int mmhip_itc_gather_buffers(mmhip_handle h, void** txt_local, void** img_local, void** txt_all, void** img_all) {
-    if (!h || !h->ws || !h->itc_max_world || h->txt_only) return MMHIP_E_STATE;
+    if (!h || !h->ws || !h->itc_max_world || h->txt_only || h->img_only) return MMHIP_E_STATE;
     const mmhip_engine& e = *h;
     if (txt_local) *txt_local = e.ws + e.h_txt_n;
     if (img_local) *img_local = e.ws + e.h_img_n;
@@ -1214,7 +1518,7 @@ int mmhip_itc_gather_buffers(mmhip_handle h, void** txt_local, void** img_local,
     return 0;
 }
 int mmhip_bind(mmhip_handle h, float* frozen, float* train, float* train_grad, void* workspace, uint64_t workspace_bytes) {
-    if (!h || !frozen || !train || !workspace || h->txt_only) return MMHIP_E_INVALID;
+    if (!h || !frozen || !train || !workspace || h->txt_only || h->img_only) return MMHIP_E_INVALID;
     if (workspace_bytes < h->ws_need) return MMHIP_E_CAPACITY;
     if (((uintptr_t)frozen | (uintptr_t)train | (uintptr_t)train_grad | (uintptr_t)workspace) & 255) return MMHIP_E_INVALID;
     h->frozen = frozen; h->train = train; h->grad = train_grad; h->ws = (char*)workspace; h->ws_bytes = workspace_bytes;
@@ -1226,6 +1530,7 @@ int mmhip_refresh_weights(mmhip_handle h, int which, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     mmhip_engine& e = *h;
     if ((which & 1) && e.txt_only) return MMHIP_E_STATE;          // no image tower, no frozen buffer (mmhip_txt_refresh_weights refreshes the text tower)
+    if (e.img_only) return MMHIP_E_STATE;                         // (mmhip_img_refresh_weights)
     if (which & 1) {
         for (int l = 0; l < e.cfg.layers_img; ++l)
             CHECK_RC(refresh_layer(e, e.frozen, e.vit[l], e.vit_w16[l], false, s, e.Hv(), e.Iv()));
@@ -1241,7 +1546,7 @@ int mmhip_refresh_weights(mmhip_handle h, int which, void* stream) {
 int mmhip_forward(mmhip_handle h, const int64_t* ids, const int64_t* mask, const float* pixels, const int64_t* tim_ids,
                   const int64_t* tim_mask, int B, int T, int train, uint64_t seed, float* out_cls, float* logits_per_text,
                   float* out_tim, float* mm_features, void* stream) {
-    if (!h || !h->ws || h->txt_only) return MMHIP_E_STATE;          // (a text-only handle has mmhip_txt_forward)
+    if (!h || !h->ws || h->txt_only || h->img_only) return MMHIP_E_STATE;          // (a text-only handle has mmhip_txt_forward, an image-only one mmhip_img_forward)
     if (!ids || !mask || B < 1 || T < 1) return MMHIP_E_INVALID;
     if ((tim_ids == nullptr) != (tim_mask == nullptr)) return MMHIP_E_INVALID;
     mmhip_engine& e = *h;
@@ -1341,12 +1646,12 @@ uint64_t mmhip_vision_record_bytes(mmhip_handle h) {
     return (P * h->Hv() * h->esz() + (uint64_t)h->Hv() * 4 + 255) & ~255ull;
 }
 int mmhip_vision_export(mmhip_handle h, const int64_t* slots, void* cache, uint64_t cache_records, void* stream) {
-    if (!h || !h->ws || !h->fwd_done || h->txt_only) return MMHIP_E_STATE;
+    if (!h || !h->ws || !h->fwd_done || h->txt_only || h->img_only) return MMHIP_E_STATE;
     if (!slots || !cache || ((uintptr_t)cache & 15)) return MMHIP_E_INVALID;
     return vision_copy(*h, 1, slots, cache, cache_records, h->B, (hipStream_t)stream);
 }
 int mmhip_vision_import(mmhip_handle h, const int64_t* slots, const void* cache, uint64_t cache_records, int B, void* stream) {
-    if (!h || !h->ws || h->txt_only) return MMHIP_E_STATE;
+    if (!h || !h->ws || h->txt_only || h->img_only) return MMHIP_E_STATE;
     if (!slots || !cache || ((uintptr_t)cache & 15) || B < 1) return MMHIP_E_INVALID;
     if (B > h->cfg.max_posts) return MMHIP_E_CAPACITY;
     CHECK_RC(vision_copy(*h, 0, slots, const_cast<void*>(cache), cache_records, B, (hipStream_t)stream));
@@ -1356,7 +1661,7 @@ int mmhip_vision_import(mmhip_handle h, const int64_t* slots, const void* cache,
 
 int mmhip_loss(mmhip_handle h, const int64_t* onehot, const float* class_w, const int64_t* lbl_tim, float w_cls, float w_itc,
                float w_itm, float* loss, int* n_correct, void* stream) {
-    if (!h || !h->fwd_done || h->txt_only) return MMHIP_E_STATE;
+    if (!h || !h->fwd_done || h->txt_only || h->img_only) return MMHIP_E_STATE;
     if (!onehot) return MMHIP_E_INVALID;
     mmhip_engine& e = *h;
     if (w_itm != 0.f && (!e.itm || !lbl_tim)) return MMHIP_E_INVALID;
@@ -1389,13 +1694,13 @@ int mmhip_loss(mmhip_handle h, const int64_t* onehot, const float* class_w, cons
     return 0;
 }
 
-int mmhip_num_backward_stages(mmhip_handle h) { return h ? h->cfg.layers_txt + 2 : MMHIP_E_INVALID; }
+int mmhip_num_backward_stages(mmhip_handle h) { return h ? h->nl() + 2 : MMHIP_E_INVALID; }
 
 int mmhip_stage_grad_range(mmhip_handle h, int stage, uint64_t* begin, uint64_t* end) {
-    if (!h || !begin || !end || stage < 0 || stage > h->cfg.layers_txt + 1) return MMHIP_E_INVALID;
+    if (!h || !begin || !end || stage < 0 || stage > h->nl() + 1) return MMHIP_E_INVALID;
     const mmhip_engine& e = *h;
     if (stage == 0) { *begin = e.heads_begin; *end = e.heads_end; }
-    else if (stage <= e.cfg.layers_txt) { const LayerOff& o = e.txt[e.cfg.layers_txt - stage]; *begin = o.begin; *end = o.end; }
+    else if (stage <= e.nl()) { const LayerOff& o = e.lay()[e.nl() - stage]; *begin = o.begin; *end = o.end; }
     else { *begin = e.emb_begin; *end = e.emb_end; }
     return 0;
 }
@@ -1419,7 +1724,13 @@ int mmhip_backward_stage(mmhip_handle h, int stage, void* stream) {
     if (!h || !h->bwd_begun) return MMHIP_E_STATE;
     mmhip_engine& e = *h;
     hipStream_t s = (hipStream_t)stream;
-    const int L = e.cfg.layers_txt;
+    const int L = e.nl();
+    if (e.img_only) {
+        if (stage == 0) return img_head_backward(e, s);
+        if (stage >= 1 && stage <= L) return image_layer_backward(e, L - stage, s);
+        if (stage == L + 1) return img_embed_backward(e, s);
+        return MMHIP_E_INVALID;
+    }
     if (stage == 0) return e.txt_only ? txt_head_backward(e, s) : heads_backward(e, s);
     if (stage >= 1 && stage <= L) return text_layer_backward(e, L - stage, s);
     if (stage == L + 1) return embed_backward(e, s);
@@ -1428,7 +1739,7 @@ int mmhip_backward_stage(mmhip_handle h, int stage, void* stream) {
 int mmhip_backward_join_stage(mmhip_handle h, int stage, void* stream) {
     if (!h || !h->bwd_begun) return MMHIP_E_STATE;
     mmhip_engine& e = *h;
-    const int L = e.cfg.layers_txt;
+    const int L = e.nl();
     if (stage < 1 || stage > L) return 0;
     const int set = (L - stage) & 1;
     if (e.tn_pending[set]) {
@@ -1589,7 +1900,10 @@ static int step_backward_update(mmhip_handle h, int use_itc, int use_itm, float*
         if (!told && getenv("MMHIP_VERBOSE")) { fprintf(stderr, "[mmhip] f16 with the step guard armed: every AdamW launch follows the backward (no per-layer optimizer beside it)\n"); told = true; }
     }
     CHECK_RC(mmhip_backward_begin(h, nullptr, nullptr, nullptr, nullptr, stream));
-    const int L = e.cfg.layers_txt;
+    const int L = e.nl();          // text layers; an image-only handle: its image layers
+    const std::vector<LayerOff>& lay = e.lay();
+    const std::vector<LayerW16>& lay16 = e.lay_w16();
+    const int lH = e.img_only ? e.Hv() : e.cfg.hidden, lI = e.img_only ? e.Iv() : e.cfg.inter;
     // data-parallel form (cb): the callback is told about stage st-1 once stage st is enqueued and st-1's weight gradients are ordered in the
     // caller's stream -- its collective travels while the stages below compute.  The layer optimizers wait for the gradient exchange: PER BUCKET
     // (round 5).  When the callback answers MMHIP_CB_BUCKET -- "the collective that carries every stage since the last such answer has been
@@ -1605,11 +1919,11 @@ static int step_backward_update(mmhip_handle h, int use_itc, int use_itm, float*
     std::vector<int> open_layers;          // text layers whose gradient stage lies in the bucket that is still open
     // text layer l on the side stream: its AdamW (adamw = false: the caller stepped it, MMHIP_CB_HANDLED), then its 16-bit operand refresh
     auto layer_update = [&](int l, bool adamw) -> int {
-        const LayerOff& o = e.txt[l];
+        const LayerOff& o = lay[l];
         if (adamw)
             CHECK_RC(adamw_impl(e.train + o.begin, e.grad + o.begin, adam_m + o.begin, adam_v + o.begin, o.end - o.begin, lr, beta1, beta2, eps, weight_decay,
                                 step, grad_scale, 1, e.side, gc, gf));
-        CHECK_RC(refresh_layer(e, e.train, o, e.txt_w16[l], true, e.side, e.cfg.hidden, e.cfg.inter));
+        CHECK_RC(refresh_layer(e, e.train, o, lay16[l], true, e.side, lH, lI));
         layer_done[l] = adamw ? 1 : 2;          // 2: stepped by the caller, refreshed here
         return 0;
     };
@@ -1657,7 +1971,7 @@ static int step_backward_update(mmhip_handle h, int use_itc, int use_itm, float*
     CHECK_RC(e.span(4, s));
     // merged [begin, end) ranges of the active gradient groups, in address order (text layers already stepped: skipped)
     bool act[6] = {false, use_itc != 0, use_itm != 0, e.cfg.fusion == MMHIP_FUSION_ATTENTION, true, false};
-    const uint64_t w0 = e.t_word, V = (uint64_t)e.cfg.vocab, H = (uint64_t)e.cfg.hidden;
+    const uint64_t w0 = e.img_only ? e.n_train : e.t_word, V = (uint64_t)e.cfg.vocab, H = (uint64_t)e.cfg.hidden;      // (no word table in an image-only handle)
     uint64_t rb = 0, re = 0;
     bool open = false;
     bool rows_due = false;
@@ -1671,7 +1985,7 @@ static int step_backward_update(mmhip_handle h, int use_itc, int use_itm, float*
         return 0;
     };
     auto in_layer = [&](uint64_t off) {          // a text layer whose optimizer has already run (beside the backward)
-        for (int l = 0; l < L; ++l) if (layer_done[l] && off >= e.txt[l].begin && off < e.txt[l].end) return true;
+        for (int l = 0; l < L; ++l) if (layer_done[l] && off >= lay[l].begin && off < lay[l].end) return true;
         return false;
     };
     for (const auto& p : e.params) {
@@ -1683,7 +1997,9 @@ static int step_backward_update(mmhip_handle h, int use_itc, int use_itm, float*
     }
     CHECK_RC(flush());
     for (int l = 0; l < L; ++l)          // 16-bit GEMM operand copies of the layers stepped just now: no word-table dependence
-        if (!layer_done[l]) CHECK_RC(refresh_layer(e, e.train, e.txt[l], e.txt_w16[l], true, s, e.cfg.hidden, e.cfg.inter));
+        if (!layer_done[l]) CHECK_RC(refresh_layer(e, e.train, lay[l], lay16[l], true, s, lH, lI));
+    if (e.img_only)          // the patch weight was stepped with the embeddings' range just now
+        CHECK_HIP(launch_cast_pad(e.train + e.v_patch_w, e.ws + e.patch_w16, e.Hv(), e.Kp(), e.Kpp(), e.px ? DT_PAIR : e.dt(), s));
     if (rows_due) {
         if (cb) CHECK_RC(cb(user, MMHIP_CB_FINISH_ROWS));                 // the exchanged word rows are summed into the gradient
         if (!e.word_row_state) return MMHIP_E_STATE;
@@ -1879,6 +2195,94 @@ int mmhip_txt_train_step(mmhip_txt_handle h, const int64_t* ids, const int64_t* 
     if (!h || !h->txt_only || !h->ws || !h->grad) return MMHIP_E_STATE;
     if (!adam_m || !adam_v || !onehot || step < 1) return MMHIP_E_INVALID;
     CHECK_RC(txt_forward_impl(h, ids, mask, type_ids, B, T, 1, seed, onehot, class_w, nullptr, loss, n_correct, stream));
+    return step_backward_update(h, 0, 0, adam_m, adam_v, lr, beta1, beta2, eps, weight_decay, step, 1.0f, stream, nullptr, nullptr);
+}
+
+// ================================================================================================ image-only handle (mmhip_img_*)
+// The reference's image-only trainer (models/image_only.py `vit` branch + ImageModel.train): HF ViTForImageClassification as a trainable pre-LN tower.
+int mmhip_img_create(const mmhip_img_config* cfg, mmhip_img_handle* out) {
+    if (!cfg || !out) return MMHIP_E_INVALID;
+    const mmhip_img_config& t = *cfg;
+    if (t.hidden <= 0 || t.hidden % 128 || t.hidden > 1024 || t.heads * 64 != t.hidden || t.inter <= 0 || t.inter % 128 || t.layers < 0) return MMHIP_E_INVALID;
+    if (t.patch < 2 || t.image < t.patch || t.image % t.patch || (3 * t.patch * t.patch) % 64) return MMHIP_E_INVALID;
+    const int P = (t.image / t.patch) * (t.image / t.patch) + 1;
+    if (P < 129 || P > 288) return MMHIP_E_INVALID;          // what launch_attn_bwd_long takes (160 px and 384 px are out of scope)
+    if (t.max_posts < 1 || t.max_posts > 1024) return MMHIP_E_INVALID;
+    if (t.dtype != MMHIP_BF16 && t.dtype != MMHIP_F16 && t.dtype != MMHIP_BF16X3) return MMHIP_E_INVALID;
+    if (t.num_labels < 1 || t.num_labels > CLS_HEAD_MAX_C || !(t.loss_scale >= 0.f) || !(t.ln_eps > 0.f)) return MMHIP_E_INVALID;
+    if (t.p_hidden != 0.f || t.p_attn != 0.f) return MMHIP_E_INVALID;          // the checkpoints' tower dropouts are 0: no dropout is built into this path
+    mmhip_engine* e = new (std::nothrow) mmhip_engine();
+    if (!e) return MMHIP_E_INVALID;
+    mmhip_config& c = e->cfg;
+    c = mmhip_config{};
+    c.hidden = t.hidden; c.heads = t.heads; c.inter = t.inter; c.layers_txt = 0; c.layers_img = t.layers;
+    // text-tower and dual-encoder fields: placeholders -- an image-only handle never lays out, carves or launches anything from them
+    c.vocab = 1; c.max_pos = 1; c.type_vocab = 1; c.txt_kind = MMHIP_TXT_BERT; c.pad_id = 0; c.max_text_len = 1; c.proj_dim = 1; c.fusion = MMHIP_FUSION_CONCAT;
+    c.ln_eps_txt = c.ln_eps_img = t.ln_eps; c.image = t.image; c.patch = t.patch; c.num_labels = t.num_labels; c.dtype = t.dtype; c.max_posts = t.max_posts;
+    c.loss_scale = t.loss_scale; c.img_kind = MMHIP_IMG_VIT;
+    e->img_only = true;
+    read_x3_env(*e);
+    build_layout_img(*e);
+    build_workspace_img(*e);
+    *out = e;
+    return 0;
+}
+void mmhip_img_destroy(mmhip_img_handle h) { if (h && h->img_only) mmhip_destroy(h); }
+int mmhip_img_param_count(mmhip_img_handle h) { return h && h->img_only ? (int)h->params.size() : MMHIP_E_INVALID; }
+int mmhip_img_param_info_at(mmhip_img_handle h, int i, mmhip_param_info* out) { return h && h->img_only ? mmhip_param_info_at(h, i, out) : MMHIP_E_INVALID; }
+uint64_t mmhip_img_numel(mmhip_img_handle h) { return h && h->img_only ? h->n_train : 0; }
+uint64_t mmhip_img_workspace_bytes(mmhip_img_handle h) { return h && h->img_only ? h->ws_need : 0; }
+int mmhip_img_bind(mmhip_img_handle h, float* params, float* grad, void* workspace, uint64_t workspace_bytes) {
+    if (!h || !h->img_only || !params || !workspace) return MMHIP_E_INVALID;
+    if (workspace_bytes < h->ws_need) return MMHIP_E_CAPACITY;
+    if (((uintptr_t)params | (uintptr_t)grad | (uintptr_t)workspace) & 255) return MMHIP_E_INVALID;
+    h->frozen = nullptr; h->train = params; h->grad = grad; h->ws = (char*)workspace; h->ws_bytes = workspace_bytes;
+    h->fwd_done = false;
+    h->i_pad_B = 0;
+    return 0;
+}
+int mmhip_img_refresh_weights(mmhip_img_handle h, void* stream) {
+    if (!h || !h->img_only) return MMHIP_E_INVALID;
+    if (!h->ws) return MMHIP_E_STATE;
+    return img_refresh(*h, (hipStream_t)stream);
+}
+static int img_forward_impl(mmhip_img_handle h, const float* pixels, int B, int train, const int64_t* onehot, const float* class_w, float* logits, float* loss,
+                            int* n_correct, void* stream) {
+    if (!h || !h->img_only || !h->ws) return MMHIP_E_STATE;
+    if (!pixels || B < 1) return MMHIP_E_INVALID;
+    mmhip_engine& e = *h;
+    if (B > e.cfg.max_posts) return MMHIP_E_CAPACITY;
+    hipStream_t s = (hipStream_t)stream;
+    e.B = e.Bt = B; e.T = 1; e.itm = false; e.train_mode = train != 0; e.seed = 0;
+    e.fwd_done = false; e.bwd_begun = false; e.bd_out_cls = nullptr; e.bd_logits = e.bd_out_tim = e.bd_feats = nullptr; e.bd_itc_global = false;
+    CHECK_RC(side_init(e));
+    e.cur_part[0] = e.cur_part[1] = 0;
+    CHECK_RC(e.span(0, s));
+    if (e.i_pad_B != B) CHECK_RC(img_zero_pads(e, B, s));
+    CHECK_RC(img_tower_forward(e, pixels, s));
+    CHECK_RC(e.span(1, s));
+    CHECK_RC(img_head_forward(e, onehot, class_w, logits, loss, n_correct, s));
+    CHECK_RC(e.span(3, s));
+    e.fwd_done = true;
+    return 0;
+}
+int mmhip_img_forward(mmhip_img_handle h, const float* pixels, int B, int train, float* logits, void* stream) {
+    return img_forward_impl(h, pixels, B, train, nullptr, nullptr, logits, nullptr, nullptr, stream);
+}
+int mmhip_img_loss(mmhip_img_handle h, const int64_t* onehot, const float* class_w, float* loss, int* n_correct, void* stream) {
+    if (!h || !h->img_only || !h->fwd_done) return MMHIP_E_STATE;
+    if (!onehot) return MMHIP_E_INVALID;
+    return img_head_classify(*h, onehot, class_w, nullptr, loss, n_correct, (hipStream_t)stream);
+}
+int mmhip_img_backward(mmhip_img_handle h, const float* d_logits, void* stream) {
+    if (!h || !h->img_only) return MMHIP_E_STATE;
+    return mmhip_backward(h, d_logits, nullptr, nullptr, nullptr, stream);
+}
+int mmhip_img_train_step(mmhip_img_handle h, const float* pixels, const int64_t* onehot, const float* class_w, int B, float* adam_m, float* adam_v,
+                         float lr, float beta1, float beta2, float eps, float weight_decay, int step, float* loss, int* n_correct, void* stream) {
+    if (!h || !h->img_only || !h->ws || !h->grad) return MMHIP_E_STATE;
+    if (!adam_m || !adam_v || !onehot || step < 1) return MMHIP_E_INVALID;
+    CHECK_RC(img_forward_impl(h, pixels, B, 1, onehot, class_w, nullptr, loss, n_correct, stream));
     return step_backward_update(h, 0, 0, adam_m, adam_v, lr, beta1, beta2, eps, weight_decay, step, 1.0f, stream, nullptr, nullptr);
 }
 

@@ -224,6 +224,24 @@ hipError_t launch_embed_bwd(const EmbedBwdArgs& a, int dtype, hipStream_t s);
 hipError_t launch_patchify(const float* pixels, void* out, int B, int img, int patch, int ld, int dtype, hipStream_t s);   // rows of ld >= 3*patch^2 columns, zero-padded
 hipError_t launch_cast_pad(const float* src, void* dst, int rows, int cols, int ld, int dtype, hipStream_t s);   // dst[r][0..ld) = cast(src[r][0..cols)), 0 beyond
 hipError_t launch_vit_assemble(const void* patches, const float* cls, const float* pos, void* x, int B, int P, int H, int dtype, hipStream_t s);
+// Backward of launch_vit_assemble.  dx [B*P, H] is the gradient of the tower's first residual stream in the activation type (16-bit; parity mode fp32).
+//   dpos [P, H] += alpha * sum_b dx[b, p, :]      dcls [H] += alpha * sum_b dx[b, 0, :]   (the same sum as row 0 of dpos, computed once)
+//   dpe  [B*(P-1), H]: the patch rows, compact, as the weight-gradient GEMM reads them -- the same 16-bit words; parity mode: fp32 words, or with
+//   `pair` rows [hi(H) | lo(H)] bf16 as split8 writes them (ld_pair / lo_pair in 16-bit elements; pair_hi_only: the hi plane alone)
+// Every output word has one writer that adds the posts in ascending order in fp32: no atomics, the same bits on every call.  More than
+// VIT_EMBED_BWD_POSTS posts are cut into slices of that many: per-slice partial rows in `partial` (partial_floats_vit_embed floats), summed in slice
+// order by a second launch.  16-byte accesses throughout: H % 8 == 0, H <= 1024; hipErrorInvalidValue before any launch for a pointer, ld_pair or
+// lo_pair off 16-byte alignment, or a missing `partial` where the split needs it.
+static constexpr int VIT_EMBED_BWD_POSTS = 8;
+struct VitEmbedBwdArgs {
+    const void* dx; float* dpos; float* dcls; void* dpe;
+    int B, P, H;
+    float alpha;          // 0 is read as 1
+    float* partial;
+    int pair, pair_hi_only, ld_pair, lo_pair;
+};
+size_t partial_floats_vit_embed(int B, int P, int H);      // 0: B fits one slice
+hipError_t launch_vit_embed_bwd(const VitEmbedBwdArgs& a, int dtype, hipStream_t s);
 hipError_t launch_colsum(const void* x, int rows, int cols, int ld, float* out, int dtype, hipStream_t s, float* partial = nullptr, float alpha = 1.0f);   // out[c] += sum_r x[r][c]
 size_t partial_floats_rows(int rows, int width, int nvec);
 size_t partial_floats_colsum(int rows, int cols);

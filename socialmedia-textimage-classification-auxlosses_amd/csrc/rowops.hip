@@ -647,6 +647,89 @@ __global__ __launch_bounds__(256) void vit_assemble_kernel(const T* __restrict__
     }
 }
 
+// ------------------------------------------------------------------------------------------------ ViT embedding backward
+// One workgroup per (token position p, slice of VIT_EMBED_BWD_POSTS posts); a lane owns 8 columns and walks the slice's posts in ascending order:
+// one 16-byte load (fp32: two) per post, the patch rows (p >= 1) stored straight back into the compact copy, eight fp32 sums in registers.
+// A single slice adds its sums into dpos (and, at p = 0, dcls) itself; several leave them in `partial` for vit_embed_bwd_sum_kernel.
+template <typename T> __device__ __forceinline__ void veb_load8(const T* p, typename Vec<T>::v8& raw, float* v) {
+    raw = *reinterpret_cast<const typename Vec<T>::v8*>(p);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = to_f<T>(raw[e]);
+}
+template <> __device__ __forceinline__ void veb_load8<float>(const float* p, f32x8& raw, float* v) {
+    load8(p, v);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) raw[e] = v[e];
+}
+__device__ __forceinline__ void veb_add8(float* d, const float* v, float alpha) {
+    f32x4 x0 = *reinterpret_cast<const f32x4*>(d), x1 = *reinterpret_cast<const f32x4*>(d + 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { x0[e] += alpha * v[e]; x1[e] += alpha * v[4 + e]; }
+    *reinterpret_cast<f32x4*>(d) = x0;
+    *reinterpret_cast<f32x4*>(d + 4) = x1;
+}
+// MODE 0: dpe in T; 1: plane pair; 2: the pair's hi plane only (T = float for 1 and 2)
+template <typename T, int MODE>
+__global__ __launch_bounds__(128) void vit_embed_bwd_kernel(VitEmbedBwdArgs a) {
+    const int p = blockIdx.x, sl = blockIdx.y, c = threadIdx.x * 8;
+    if (c >= a.H) return;
+    const int b0 = sl * VIT_EMBED_BWD_POSTS, b1 = min(a.B, b0 + VIT_EMBED_BWD_POSTS);
+    float acc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+#pragma unroll 4
+    for (int b = b0; b < b1; ++b) {
+        typename Vec<T>::v8 raw;
+        float v[8];
+        veb_load8<T>((const T*)a.dx + ((size_t)b * a.P + p) * a.H + c, raw, v);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] += v[e];
+        if (p > 0) {
+            const size_t row = (size_t)b * (a.P - 1) + (p - 1);
+            if (MODE == 0) {
+                T* d = (T*)a.dpe + row * a.H + c;
+                if (std::is_same<T, float>::value) {
+                    *reinterpret_cast<f32x4*>(d) = f32x4{v[0], v[1], v[2], v[3]};
+                    *reinterpret_cast<f32x4*>(d + 4) = f32x4{v[4], v[5], v[6], v[7]};
+                } else {
+                    *reinterpret_cast<typename Vec<T>::v8*>(d) = raw;
+                }
+            } else {
+                const Frag3 f = split8(v);
+                bf16_t* d = (bf16_t*)a.dpe + row * a.ld_pair + c;
+                *reinterpret_cast<bf16x8*>(d) = f.hi;
+                if (MODE == 1) *reinterpret_cast<bf16x8*>(d + a.lo_pair) = f.lo;
+            }
+        }
+    }
+    if (gridDim.y == 1) {
+        const float alpha = a.alpha == 0.f ? 1.f : a.alpha;
+        veb_add8(a.dpos + (size_t)p * a.H + c, acc, alpha);
+        if (p == 0) veb_add8(a.dcls + c, acc, alpha);
+    } else {
+        float* d = a.partial + ((size_t)sl * a.P + p) * a.H + c;
+        *reinterpret_cast<f32x4*>(d) = f32x4{acc[0], acc[1], acc[2], acc[3]};
+        *reinterpret_cast<f32x4*>(d + 4) = f32x4{acc[4], acc[5], acc[6], acc[7]};
+    }
+}
+// dpos[p][c] += alpha * sum over the slices, in slice order; row 0 goes to dcls as well
+__global__ __launch_bounds__(256) void vit_embed_bwd_sum_kernel(const float* __restrict__ partial, int slices, float* __restrict__ dpos, float* __restrict__ dcls,
+                                                                int P, int H, float alpha) {
+    const size_t n4 = (size_t)P * H / 4;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+        f32x4 sum = *reinterpret_cast<const f32x4*>(partial + i * 4);
+        for (int sl = 1; sl < slices; ++sl) sum += *reinterpret_cast<const f32x4*>(partial + ((size_t)sl * P * H) + i * 4);
+        f32x4 d = *reinterpret_cast<const f32x4*>(dpos + i * 4);
+        d += alpha * sum;
+        *reinterpret_cast<f32x4*>(dpos + i * 4) = d;
+        if (i * 4 < (size_t)H) {
+            f32x4 q = *reinterpret_cast<const f32x4*>(dcls + i * 4);
+            q += alpha * sum;
+            *reinterpret_cast<f32x4*>(dcls + i * 4) = q;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ column sums
 // out[c] += sum_r x[r][c]   (bias gradients).  grid (ceil(cols/256), row chunks); lanes own 4 columns each.
 static constexpr int COLSUM_ROWS = 64;
@@ -943,6 +1026,29 @@ hipError_t launch_vit_assemble(const void* patches, const float* cls, const floa
     if (dtype == DT_BF16) hipLaunchKernelGGL(vit_assemble_kernel<bf16_t>, dim3(cap_grid(total)), dim3(256), 0, s, (const bf16_t*)patches, cls, pos, (bf16_t*)x, B, P, H);
     else if (dtype == DT_F16) hipLaunchKernelGGL(vit_assemble_kernel<f16_t>, dim3(cap_grid(total)), dim3(256), 0, s, (const f16_t*)patches, cls, pos, (f16_t*)x, B, P, H);
     else hipLaunchKernelGGL(vit_assemble_kernel<float>, dim3(cap_grid(total)), dim3(256), 0, s, (const float*)patches, cls, pos, (float*)x, B, P, H);
+    return hipGetLastError();
+}
+size_t partial_floats_vit_embed(int B, int P, int H) {
+    const int slices = (B + VIT_EMBED_BWD_POSTS - 1) / VIT_EMBED_BWD_POSTS;
+    return slices > 1 ? (size_t)slices * P * H : 0;
+}
+hipError_t launch_vit_embed_bwd(const VitEmbedBwdArgs& a, int dtype, hipStream_t s) {
+    if (a.B <= 0) return hipSuccess;
+    if (a.P < 1 || a.H < 8 || a.H % 8 || a.H > 1024 || !a.dx || !a.dpos || !a.dcls || (a.P > 1 && !a.dpe)) return hipErrorInvalidValue;
+    if (((uintptr_t)a.dx | (uintptr_t)a.dpos | (uintptr_t)a.dcls | (uintptr_t)a.dpe | (uintptr_t)a.partial) & 15) return hipErrorInvalidValue;
+    if (a.pair && (dtype != DT_F32 || a.ld_pair % 8 || a.lo_pair % 8 || a.lo_pair < a.H || a.ld_pair < a.lo_pair + a.H)) return hipErrorInvalidValue;
+    const int slices = (a.B + VIT_EMBED_BWD_POSTS - 1) / VIT_EMBED_BWD_POSTS;
+    if (slices > 1 && !a.partial) return hipErrorInvalidValue;
+    const dim3 grid(a.P, slices);
+    if (dtype == DT_BF16) hipLaunchKernelGGL((vit_embed_bwd_kernel<bf16_t, 0>), grid, dim3(128), 0, s, a);
+    else if (dtype == DT_F16) hipLaunchKernelGGL((vit_embed_bwd_kernel<f16_t, 0>), grid, dim3(128), 0, s, a);
+    else if (dtype != DT_F32) return hipErrorInvalidValue;
+    else if (!a.pair) hipLaunchKernelGGL((vit_embed_bwd_kernel<float, 0>), grid, dim3(128), 0, s, a);
+    else if (a.pair_hi_only) hipLaunchKernelGGL((vit_embed_bwd_kernel<float, 2>), grid, dim3(128), 0, s, a);
+    else hipLaunchKernelGGL((vit_embed_bwd_kernel<float, 1>), grid, dim3(128), 0, s, a);
+    if (slices > 1)
+        hipLaunchKernelGGL(vit_embed_bwd_sum_kernel, dim3(cap_grid((size_t)a.P * a.H / 4)), dim3(256), 0, s, a.partial, slices, a.dpos, a.dcls, a.P, a.H,
+                           a.alpha == 0.f ? 1.f : a.alpha);
     return hipGetLastError();
 }
 hipError_t launch_colsum(const void* x, int rows, int cols, int ld, float* out, int dtype, hipStream_t s, float* partial, float alpha) {

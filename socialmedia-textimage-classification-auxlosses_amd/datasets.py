@@ -195,6 +195,29 @@ class TxtOnly_Dataset(torch.utils.data.Dataset):
         return item
 
 
+class ImgOnly_Dataset(MM_Dataset):
+    """Item layout of the reference's ImgOnly_Dataset (models/datasets.py:64-91): `pixel_values` [1, 3, S, S] -- the ViT feature extractor's
+    defaults, computed by the host path this project already has (MM_Dataset._pixels: PIL BILINEAR resize, rescale, normalize) --, one-hot
+    `labels`, `data_id`; jpg -> png fallback.  `feature_extractor` is accepted for signature parity and not used."""
+
+    def __init__(self, data_ids, labels, feature_extractor, img_file_fmt, task_name=None, image=224):
+        super().__init__(data_ids, None, labels, None, 0, img_file_fmt, image=image)
+        self.task_name = task_name
+        if task_name == "poi":
+            self.data_ids_num = [float(str(x).split("_")[0]) for x in data_ids]
+        elif task_name in {"polid", "poladv"}:
+            self.data_ids_num = [float(str(x)[2:]) for x in data_ids]
+        else:
+            self.data_ids_num = data_ids
+
+    def __len__(self):
+        return len(self.labels)
+
+    def __getitem__(self, index):
+        return {"pixel_values": self._pixels(self.ids[index]), "labels": torch.as_tensor(self.labels[index], dtype=torch.long),
+                "data_id": torch.tensor(int(self.data_ids_num[index]), dtype=torch.long)}
+
+
 def lxmert_loaders_from_data_key(cfg, args, tokenizer, data_path=None):
     """reference MMEarly_Model.load_data, LXMERT branch (models/mm_early.py:228-258): prepare_data -> three Lxmert_Datasets -> loaders
     (train shuffled).  Data parallel: the training set is sharded by a DistributedSampler, validation / test stay whole."""
