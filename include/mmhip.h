@@ -33,7 +33,13 @@ enum { MMHIP_BF16 = 0, MMHIP_F16 = 1, MMHIP_F32 = 2, MMHIP_BF16X3 = 2,
                               [hi = bf16(x) (W) | lo = bf16(x - hi) (W)], the same bytes as the fp32 row (csrc/mmhip_kernels.h) */
 enum { MMHIP_TXT_BERT = 0, MMHIP_TXT_XLMR = 1 };
 enum { MMHIP_IMG_VIT = 0, MMHIP_IMG_CLIP = 1 };   /* HF ViTModel | HF CLIPVisionModel (pre-LN, quick-GELU, bias-free patch conv, pre_layrnorm) */
-enum { MMHIP_FUSION_CONCAT = 0, MMHIP_FUSION_ATTENTION = 1 };
+/* MMHIP_FUSION_ASPECT = 2: --fusion_name aspect-att (models/mm_late.py:115-131): V = reshape(stack(t_pool, v_pool), [B, 2, H]) -- slot j of post n is
+ * row 2 n + j of [t_pool; v_pool], a reshape and not a transpose, so only B = 1 pairs a post's own text and image; reproduced as it is -- then
+ * relu(softmax_j(tanh(V a + b)) . V).  Such a handle needs equally wide towers (mmhip_create: MMHIP_E_INVALID otherwise) and has its own parameter
+ * order and groups: aspectattention.* and the text pooler are MMHIP_G_ALWAYS, fc_Q / fc_K / fc_V and linear_fusion MMHIP_G_NEVER, all active
+ * parameters of the heads inside stage 0's range.  It has no ITM pass (the reference's own call at models/mm_late.py:181 raises): tim_ids != NULL or
+ * use_itm != 0 answer MMHIP_E_INVALID before anything is enqueued.  Handles of the other two values keep every name, offset and group. */
+enum { MMHIP_FUSION_CONCAT = 0, MMHIP_FUSION_ATTENTION = 1, MMHIP_FUSION_ASPECT = 2 };
 /* gradient groups: which parameters receive a gradient for a given flag set */
 enum { MMHIP_G_NEVER = 0, MMHIP_G_ITC = 1, MMHIP_G_ITM = 2, MMHIP_G_FUSION_ATT = 3, MMHIP_G_ALWAYS = 4, MMHIP_G_FROZEN = 5 };
 
@@ -553,6 +559,18 @@ int mmhip_op_cls_head_fwd(int x_dtype, const void* x, uint64_t x_stride, const f
                           float* logits, const int64_t* onehot, const float* class_w, float* loss, int32_t* n_correct, float* d_logits, void* stream);
 int mmhip_op_cls_head_bwd(int x_dtype, const void* x, uint64_t x_stride, const float* W, const float* d_logits, int B, int C, int H, float p, uint64_t seed,
                           float* dW, float* db, int dx_dtype, void* dx, uint64_t dx_stride, float dx_scale, int accumulate, void* stream);
+/* the aspect-att fusion head's launches alone (operator tests), fp32 on caller-owned buffers.  t_pool / v_pool [B,H], a [H], b [1]; slot j of post n is row
+ * 2 n + j of [t_pool; v_pool] (MMHIP_FUSION_ASPECT).  Limits: B >= 1, H % 64 == 0, 64 <= H <= 1024, else MMHIP_E_INVALID with nothing written.
+ *   fwd: feats [B,H] = relu(w_0 V_0 + w_1 V_1), w [B,2] the softmax weights, e [B,2] = tanh(V_j . a + b).
+ *   bwd: from d_feats [B,H] and the forward's feats / w / e: d_tpool [B,H] (every row written; accumulate != 0: added to what is there -- ITC's share),
+ *        d_a [H], d_b [1] (accumulate_dw != 0: added).  Rows of v_pool get no gradient (the image tower is frozen).  ws: scratch of
+ *        mmhip_op_aspect_fusion_ws_bytes(B, H) bytes (too small: MMHIP_E_CAPACITY).  No atomics: the same bits on every call. */
+uint64_t mmhip_op_aspect_fusion_ws_bytes(int B, int H);
+int mmhip_op_aspect_fusion_fwd(const float* t_pool, const float* v_pool, const float* a, const float* b, int B, int H, float* feats, float* w, float* e,
+                               void* stream);
+int mmhip_op_aspect_fusion_bwd(const float* t_pool, const float* v_pool, const float* a, const float* b, int B, int H, const float* feats, const float* w,
+                               const float* e, const float* d_feats, float* d_tpool, float* d_a, float* d_b, int accumulate, int accumulate_dw, void* ws,
+                               uint64_t ws_bytes, void* stream);
 
 /* ==== image-only handle: the reference's image-only trainer (models/image_only.py, models/run_img.py --model_name vit) =====================
  * HF ViTForImageClassification -- ViT without a pooler, classifier(layernorm(x)[:, 0, :]) -- as a TRAINABLE pre-LN tower on this engine's kernels:

@@ -10,7 +10,7 @@ BF16, F16, F32 = 0, 1, 2
 BF16X3 = 2          # as an engine dtype: the strict-parity mode (fp32 activations, bf16x3 matrix products; include/mmhip.h)
 PAIR = 3            # op-level entry points that say so only: the parity mode's tensors as bf16 plane pairs (MMHIP_PAIR)
 TXT_BERT, TXT_XLMR = 0, 1
-FUSION_CONCAT, FUSION_ATTENTION = 0, 1
+FUSION_CONCAT, FUSION_ATTENTION, FUSION_ASPECT = 0, 1, 2      # include/mmhip.h MMHIP_FUSION_*: concat | attention | aspect-att
 IMG_VIT, IMG_CLIP = 0, 1
 G_NEVER, G_ITC, G_ITM, G_FUSION_ATT, G_ALWAYS, G_FROZEN = range(6)
 
@@ -171,6 +171,9 @@ _SIGS = {
     "mmhip_txt_train_step": (I, [P, P, P, P, P, P, I, I, U64, P, P, F, F, F, F, F, I, P, P, P]),
     "mmhip_op_cls_head_fwd": (I, [I, P, U64, P, P, I, I, I, F, U64, P, P, P, P, P, P, P]),
     "mmhip_op_cls_head_bwd": (I, [I, P, U64, P, P, I, I, I, F, U64, P, P, I, P, U64, F, I, P]),
+    "mmhip_op_aspect_fusion_ws_bytes": (U64, [I, I]),
+    "mmhip_op_aspect_fusion_fwd": (I, [P, P, P, P, I, I, P, P, P, P]),
+    "mmhip_op_aspect_fusion_bwd": (I, [P, P, P, P, I, I, P, P, P, P, P, P, P, I, I, P, U64, P]),
     "mmhip_img_create": (I, [C.POINTER(ImgConfig), C.POINTER(P)]),
     "mmhip_img_destroy": (None, [P]),
     "mmhip_img_param_count": (I, [P]),

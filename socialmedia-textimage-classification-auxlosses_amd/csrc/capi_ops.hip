@@ -409,6 +409,24 @@ int mmhip_op_cls_head_bwd(int x_dtype, const void* x, uint64_t x_stride, const f
     return r == hipErrorInvalidValue ? MMHIP_E_INVALID : (int)r;
 }
 
+// ------------------------------------------------------------------------------------------------ aspect-att fusion head
+uint64_t mmhip_op_aspect_fusion_ws_bytes(int B, int H) { return B < 1 || H < 1 ? 0 : (uint64_t)aspect_fusion_partial_floats(B, H) * 4; }
+int mmhip_op_aspect_fusion_fwd(const float* t_pool, const float* v_pool, const float* a, const float* b, int B, int H, float* feats, float* w, float* e,
+                               void* stream) {
+    const hipError_t r = launch_aspect_fusion_fwd(aspect_fusion(t_pool, v_pool, a, b, B, H, feats, w, e), (hipStream_t)stream);
+    return r == hipErrorInvalidValue ? MMHIP_E_INVALID : (int)r;
+}
+int mmhip_op_aspect_fusion_bwd(const float* t_pool, const float* v_pool, const float* a, const float* b, int B, int H, const float* feats, const float* w,
+                               const float* e, const float* d_feats, float* d_tpool, float* d_a, float* d_b, int accumulate, int accumulate_dw, void* ws,
+                               uint64_t ws_bytes, void* stream) {
+    if (B < 1 || H < 64 || H > 1024 || H % 64 || !ws) return MMHIP_E_INVALID;
+    if (ws_bytes < mmhip_op_aspect_fusion_ws_bytes(B, H)) return MMHIP_E_CAPACITY;
+    AspectFusionArgs f = aspect_fusion(t_pool, v_pool, a, b, B, H, const_cast<float*>(feats), const_cast<float*>(w), const_cast<float*>(e));
+    f.d_feats = d_feats; f.d_tpool = d_tpool; f.da = d_a; f.db = d_b; f.partial = (float*)ws; f.accumulate = accumulate; f.accumulate_dw = accumulate_dw;
+    const hipError_t r = launch_aspect_fusion_bwd(f, (hipStream_t)stream);
+    return r == hipErrorInvalidValue ? MMHIP_E_INVALID : (int)r;
+}
+
 // ------------------------------------------------------------------------------------------------ ViT embedding backward (image-only model)
 uint64_t mmhip_op_vit_embed_bwd_ws_bytes(int B, int P, int H) { return B < 1 || P < 1 || H < 1 ? 0 : (uint64_t)partial_floats_vit_embed(B, P, H) * 4; }
 int mmhip_op_vit_embed_bwd(int dtype, const void* dx, int B, int P, int H, float alpha, float* dpos, float* dcls, void* dpe, int pair_hi_only, void* ws,

@@ -39,6 +39,7 @@ struct mmhip_engine {
     size_t t_word, t_pos, t_type, t_eln_w, t_eln_b, t_pool_w, t_pool_b;                     // train
     size_t logit_scale, vproj_w, tproj_w;
     size_t fq_w, fq_b, fk_w, fk_b, fv_w, fv_b, fus_w, fus_b, cls_w, cls_b, tim_w, tim_b;
+    size_t asp_w = 0, asp_b = 0;         // aspectattention.* (MMHIP_FUSION_ASPECT)
     size_t heads_begin, heads_end, emb_begin, emb_end;
     // bound buffers --------------------------------------------------------------------
     float* frozen = nullptr; float* train = nullptr; float* grad = nullptr;
@@ -73,6 +74,7 @@ struct mmhip_engine {
                                                                            // GEMMs may run side by side
     size_t h_d_out_cls, h_d_logits, h_d_out_tim, h_dfeats, h_dpre, h_dz, h_dxcls, h_dxbar, h_dqk, h_dq, h_dtxt_e, h_dimg_e,
         h_dtpool, h_dprepool, h_loss;
+    size_t h_asp_w = 0, h_asp_e = 0, h_asp_partial = 0;      // aspect-att fusion: softmax weights and tanh outputs [B, 2] of the forward; d a / d b partials
     // state of the last forward --------------------------------------------------------
     int B = 0, T = 0, Bt = 0; bool itm = false, train_mode = false, fwd_done = false, bwd_begun = false;
     bool skip_itc = false, itc_done = false;   // mmhip_train_step without the ITC loss: the dual-encoder similarity head (text pooler, both projections,
@@ -146,6 +148,7 @@ struct mmhip_engine {
     int dt() const { return cfg.dtype; }
     // image tower geometry: its own width for CLIP-ViT-L/14 (BASELINE config 4), the text tower's otherwise
     bool clip() const { return cfg.img_kind == MMHIP_IMG_CLIP; }
+    bool aspect() const { return cfg.fusion == MMHIP_FUSION_ASPECT; }
     int Hv() const { return cfg.hidden_img > 0 ? cfg.hidden_img : cfg.hidden; }
     int Iv() const { return cfg.inter_img > 0 ? cfg.inter_img : cfg.inter; }
     int heads_v() const { return cfg.heads_img > 0 ? cfg.heads_img : cfg.heads; }
@@ -281,28 +284,41 @@ void build_layout(mmhip_engine& e) {
         e.v_pool_b = b.add(vm + "pooler.dense.bias", 0, MMHIP_G_FROZEN, {Hv});
     }
     // ---- trainable, ordered [never | ITC | ITM | fusion-attention | always: heads, layers last->first, embeddings]
+    // An aspect-att handle (MMHIP_FUSION_ASPECT) has its own order: fc_Q / fc_K / fc_V and linear_fusion join the never group in front of the heads'
+    // range (mm_late.py:115-131 reads none of them), aspectattention.* leaves it for the always group, and the text pooler -- consumed by the fusion
+    // itself, not by ITC alone -- is tagged always.  Concat / attention handles keep every name, offset and group as they were.
+    const bool aspect = e.aspect();
     for (const char* n : {"aspectattention", "linear_iadds", "linear_gmu_t", "linear_gmu_v"}) {
+        if (aspect && !strcmp(n, "aspectattention")) continue;
         const int out = !strcmp(n, "aspectattention") ? 1 : (!strcmp(n, "linear_iadds") ? 2 : 2 * H);
         b.add(std::string(n) + ".weight", 1, MMHIP_G_NEVER, {out, H});
         b.add(std::string(n) + ".bias", 1, MMHIP_G_NEVER, {out});
     }
+    auto add_attention_and_fusion = [&](int g_att, int g_fus) {
+        e.fq_w = b.add("fc_Q.weight", 1, g_att, {H, H});
+        e.fq_b = b.add("fc_Q.bias", 1, g_att, {H});
+        e.fk_w = b.add("fc_K.weight", 1, g_att, {H, H});
+        e.fk_b = b.add("fc_K.bias", 1, g_att, {H});
+        e.fv_w = b.add("fc_V.weight", 1, g_att, {H, H});
+        e.fv_b = b.add("fc_V.bias", 1, g_att, {H});
+        // 'concat' takes [x_t CLS | x_v CLS]: H + Hv wide (the reference hard-wires 768 + 768, models/config.py:82-84, mm_late.py:81)
+        e.fus_w = b.add("linear_fusion.weight", 1, g_fus, {H, H + Hv});
+        e.fus_b = b.add("linear_fusion.bias", 1, g_fus, {H});
+    };
+    if (aspect) add_attention_and_fusion(MMHIP_G_NEVER, MMHIP_G_NEVER);
     e.heads_begin = b.off[1];
     e.logit_scale = b.add("dual_encoder.logit_scale", 1, MMHIP_G_ITC, {});
     e.vproj_w = b.add("dual_encoder.visual_projection.weight", 1, MMHIP_G_ITC, {E, Hv});
     e.tproj_w = b.add("dual_encoder.text_projection.weight", 1, MMHIP_G_ITC, {E, H});
-    e.t_pool_w = b.add("dual_encoder.text_model.pooler.dense.weight", 1, MMHIP_G_ITC, {H, H});
-    e.t_pool_b = b.add("dual_encoder.text_model.pooler.dense.bias", 1, MMHIP_G_ITC, {H});
+    e.t_pool_w = b.add("dual_encoder.text_model.pooler.dense.weight", 1, aspect ? MMHIP_G_ALWAYS : MMHIP_G_ITC, {H, H});
+    e.t_pool_b = b.add("dual_encoder.text_model.pooler.dense.bias", 1, aspect ? MMHIP_G_ALWAYS : MMHIP_G_ITC, {H});
     e.tim_w = b.add("linear_tim.weight", 1, MMHIP_G_ITM, {2, H});
     e.tim_b = b.add("linear_tim.bias", 1, MMHIP_G_ITM, {2});
-    e.fq_w = b.add("fc_Q.weight", 1, MMHIP_G_FUSION_ATT, {H, H});
-    e.fq_b = b.add("fc_Q.bias", 1, MMHIP_G_FUSION_ATT, {H});
-    e.fk_w = b.add("fc_K.weight", 1, MMHIP_G_FUSION_ATT, {H, H});
-    e.fk_b = b.add("fc_K.bias", 1, MMHIP_G_FUSION_ATT, {H});
-    e.fv_w = b.add("fc_V.weight", 1, MMHIP_G_FUSION_ATT, {H, H});
-    e.fv_b = b.add("fc_V.bias", 1, MMHIP_G_FUSION_ATT, {H});
-    // 'concat' takes [x_t CLS | x_v CLS]: H + Hv wide (the reference hard-wires 768 + 768, models/config.py:82-84, mm_late.py:81)
-    e.fus_w = b.add("linear_fusion.weight", 1, MMHIP_G_ALWAYS, {H, H + Hv});
-    e.fus_b = b.add("linear_fusion.bias", 1, MMHIP_G_ALWAYS, {H});
+    if (!aspect) add_attention_and_fusion(MMHIP_G_FUSION_ATT, MMHIP_G_ALWAYS);
+    if (aspect) {
+        e.asp_w = b.add("aspectattention.weight", 1, MMHIP_G_ALWAYS, {1, H});
+        e.asp_b = b.add("aspectattention.bias", 1, MMHIP_G_ALWAYS, {1});
+    }
     e.cls_w = b.add("linear_cls.weight", 1, MMHIP_G_ALWAYS, {C, H});
     e.cls_b = b.add("linear_cls.bias", 1, MMHIP_G_ALWAYS, {C});
     e.heads_end = b.off[1];
@@ -507,6 +523,7 @@ void build_workspace(mmhip_engine& e) {
     e.h_d_out_cls = f(Bm * C); e.h_d_logits = f(Bm * Bm); e.h_d_out_tim = f(Bm * 2); e.h_dfeats = f(Bt * H); e.h_dpre = f(Bt * H);
     e.h_dz = f(Bt * (H + Hv)); e.h_dxcls = f(Bt * H); e.h_dxbar = f(Bt * H); e.h_dqk = f(Bt * H); e.h_dq = f(Bt * H);
     e.h_dtxt_e = f(Bm * E); e.h_dimg_e = f(Bm * E); e.h_dtpool = f(Bm * H); e.h_dprepool = f(Bm * H); e.h_loss = f(8);
+    if (e.aspect()) { e.h_asp_w = f(Bm * 2); e.h_asp_e = f(Bm * 2); e.h_asp_partial = f(aspect_fusion_partial_floats((int)Bm, (int)H)); }
     e.ws_need = e.ws_base = w.off;
 }
 
@@ -924,8 +941,10 @@ int heads_forward(mmhip_engine& e, float* out_cls, float* logits, float* out_tim
     CHECK_HIP(launch_gather_rows_f32(xt, (size_t)cs, z, ZW, Bt, H, dt, s));
     // text pooler (first B posts) and ITC similarity -- HF dual encoder :261-274
     e.itc_done = !(e.skip_itc && logits == nullptr);
-    if (e.itc_done) {
+    const bool aspect = e.aspect();          // the aspect-att fusion consumes the text pooler's output itself: computed with or without ITC
+    if (e.itc_done || aspect)
         CHECK_HIP(launch_small_nt(small(z, ZW, W + e.t_pool_w, H, W + e.t_pool_b, e.wsp<float>(e.h_tpool), H, B, H, H, ACT_TANH), DT_F32, s));
+    if (e.itc_done) {
         CHECK_HIP(launch_small_nt(small(e.wsp<float>(e.h_tpool), H, W + e.tproj_w, H, nullptr, e.wsp<float>(e.h_txt_e), E, B, E, H), DT_F32, s));
         CHECK_HIP(launch_small_nt(small(e.wsp<float>(e.h_vpool), Hv, W + e.vproj_w, Hv, nullptr, e.wsp<float>(e.h_img_e), E, B, E, Hv), DT_F32, s));
         ItcArgs it{e.wsp<float>(e.h_txt_e), e.wsp<float>(e.h_img_e), W + e.logit_scale, e.wsp<float>(e.h_txt_n), e.wsp<float>(e.h_img_n),
@@ -938,13 +957,17 @@ int heads_forward(mmhip_engine& e, float* out_cls, float* logits, float* out_tim
         FusionAttnArgs fa{e.wsp<float>(e.h_qk), e.ws + e.v_out, e.wsp<float>(e.h_prob), e.wsp<float>(e.h_xbar), Bt, B, P, H, 1.0f / sqrtf((float)H)};
         CHECK_HIP(launch_fusion_attn_fwd(fa, dt, s));
         CHECK_HIP(launch_small_nt(small(e.wsp<float>(e.h_xbar), H, W + e.fv_w, H, W + e.fv_b, z + H, ZW, Bt, H, H), DT_F32, s));
+    } else if (aspect) {
+        // mm_late.py:115-131 on the two pooler outputs (Bt == B: mmhip_forward refuses ITM rows); writes feats directly -- no linear_fusion
+        CHECK_HIP(launch_aspect_fusion_fwd(aspect_fusion(e.wsp<float>(e.h_tpool), e.wsp<float>(e.h_vpool), W + e.asp_w, W + e.asp_b, B, H,
+                                                         e.wsp<float>(e.h_feats), e.wsp<float>(e.h_asp_w), e.wsp<float>(e.h_asp_e)), s));
     } else {
         // concat: image CLS row of post bt % B -- two strided copies (original rows, ITM rows)
         CHECK_HIP(launch_gather_rows_f32(e.ws + e.v_out, (size_t)P * Hv, z + H, ZW, B, Hv, dt, s));
         if (Bt > B) CHECK_HIP(launch_gather_rows_f32(e.ws + e.v_out, (size_t)P * Hv, z + (size_t)B * ZW + H, ZW, B, Hv, dt, s));
     }
     float* feats = e.wsp<float>(e.h_feats);
-    CHECK_HIP(launch_small_nt(small(z, ZW, W + e.fus_w, ZW, W + e.fus_b, feats, H, Bt, H, ZW, ACT_RELU), DT_F32, s));
+    if (!aspect) CHECK_HIP(launch_small_nt(small(z, ZW, W + e.fus_w, ZW, W + e.fus_b, feats, H, Bt, H, ZW, ACT_RELU), DT_F32, s));
     CHECK_HIP(launch_elementwise(EW_DROPOUT, feats, nullptr, e.wsp<float>(e.h_featd), (size_t)B * H, 0.f,
                                  make_drop(c.p_head, e.seed, STREAM_HEAD, e.train_mode), s));
     CHECK_HIP(launch_small_nt(small(e.wsp<float>(e.h_featd), H, W + e.cls_w, H, W + e.cls_b, e.wsp<float>(e.h_out_cls), C, B, C, H), DT_F32, s));
@@ -957,6 +980,49 @@ int heads_forward(mmhip_engine& e, float* out_cls, float* logits, float* out_tim
 }
 
 // ------------------------------------------------------------------------------------------------ backward pieces
+// ITC similarity backward down to the text pooler's output: logit_scale and both projections' gradients, d t_pool written (not added) to h_dtpool
+int itc_backward_to_tpool(mmhip_engine& e, hipStream_t s) {
+    const mmhip_config& c = e.cfg;
+    const int H = c.hidden, E = c.proj_dim, B = e.B, Hv = e.Hv();
+    const float* W = e.train;
+    float* Gd = e.grad;
+    if (e.bd_itc_global) {
+        // gathered form: this rank's rows of d T_n / d I_n collect both cross-entropy directions over all G posts.  Seed: the loss is the SAME
+        // global clip_loss on every rank and each rank differentiates it through its own rows only, so the ranks' parameter gradients sum to
+        // the single-process gradient; the exchange then averages (1 / world), hence the factor `world` here
+        const int G = e.itc_world * B;
+        ItcGlobalBwdArgs gb{};
+        gb.txt_n = e.wsp<float>(e.h_g_txt); gb.img_n = e.wsp<float>(e.h_g_img); gb.logit_scale = W + e.logit_scale;
+        gb.rowlse = e.wsp<float>(e.h_g_rowlse); gb.collse = e.wsp<float>(e.h_g_collse);
+        gb.txt_inv = e.wsp<float>(e.h_txt_inv); gb.img_inv = e.wsp<float>(e.h_img_inv);
+        gb.d_txt_n = e.wsp<float>(e.h_g_dtn); gb.d_img_n = e.wsp<float>(e.h_g_din);
+        gb.dtxt_e = e.wsp<float>(e.h_dtxt_e); gb.dimg_e = e.wsp<float>(e.h_dimg_e); gb.dlogit_scale = Gd + e.logit_scale;
+        gb.ws = e.wsp<float>(e.h_g_ws); gb.G = G; gb.E = E; gb.Bl = B; gb.r0 = e.itc_rank * B;
+        gb.scale = e.bd_w_itc * (float)e.itc_world / (2.f * (float)G);
+        CHECK_HIP(launch_itc_global_bwd(gb, s));
+    } else {
+        ItcBwdArgs ib{e.bd_logits, e.wsp<float>(e.h_logits), e.wsp<float>(e.h_txt_n), e.wsp<float>(e.h_img_n), e.wsp<float>(e.h_txt_inv),
+                      e.wsp<float>(e.h_img_inv), W + e.logit_scale, e.wsp<float>(e.h_dtxt_e), e.wsp<float>(e.h_dimg_e), Gd + e.logit_scale, B, E};
+        CHECK_HIP(launch_itc_bwd(ib, s));
+    }
+    CHECK_HIP(launch_small_tn(small(e.wsp<float>(e.h_dtxt_e), E, e.wsp<float>(e.h_tpool), H, nullptr, Gd + e.tproj_w, H, B, H, 0, 0, 1), DT_F32, E, s));
+    CHECK_HIP(launch_small_tn(small(e.wsp<float>(e.h_dimg_e), E, e.wsp<float>(e.h_vpool), Hv, nullptr, Gd + e.vproj_w, Hv, B, Hv, 0, 0, 1), DT_F32, E, s));
+    CHECK_HIP(launch_small_nn(small(e.wsp<float>(e.h_dtxt_e), E, W + e.tproj_w, H, nullptr, e.wsp<float>(e.h_dtpool), H, B, H, E), s));
+    return 0;
+}
+// t_pool = tanh(dense(CLS)) backward from h_dtpool: the pooler's gradients, and d CLS added to (accumulate) or written into h_dxcls
+int text_pooler_backward(mmhip_engine& e, int accumulate, hipStream_t s) {
+    const int H = e.cfg.hidden, B = e.B, ZW = H + e.Hv();
+    const float* W = e.train;
+    float* Gd = e.grad;
+    const float* z = e.wsp<float>(e.h_z);
+    CHECK_HIP(launch_elementwise(EW_TANH_BWD, e.wsp<float>(e.h_dtpool), e.wsp<float>(e.h_tpool), e.wsp<float>(e.h_dprepool), (size_t)B * H, 0.f,
+                                 make_drop(0.f, 0, 0, false), s));
+    CHECK_HIP(launch_small_tn(small(e.wsp<float>(e.h_dprepool), H, z, ZW, nullptr, Gd + e.t_pool_w, H, B, H, 0, 0, 1), DT_F32, H, s));
+    CHECK_HIP(launch_bias_grad_f32(e.wsp<float>(e.h_dprepool), B, H, H, Gd + e.t_pool_b, 1, s));
+    CHECK_HIP(launch_small_nn(small(e.wsp<float>(e.h_dprepool), H, W + e.t_pool_w, H, nullptr, e.wsp<float>(e.h_dxcls), H, B, H, H, ACT_NONE, accumulate), s));
+    return 0;
+}
 int heads_backward(mmhip_engine& e, hipStream_t s) {
     const mmhip_config& c = e.cfg;
     const int H = c.hidden, E = c.proj_dim, C = c.num_labels, T = e.T, B = e.B, Bt = e.Bt, dt = e.dt();
@@ -986,6 +1052,20 @@ int heads_backward(mmhip_engine& e, hipStream_t s) {
             CHECK_HIP(hipMemsetAsync(dfeats + (size_t)B * H, 0, (size_t)B * H * 4, s));
         }
     }
+    if (e.aspect()) {
+        // feats = relu(sum_j w_j V_j) over the stacked pooler outputs: ITC's gradient of t_pool first (a plain write), the fusion's added to it by the
+        // rows' one writer; then the text pooler's backward, which OPENS dxcls here (nothing else reaches the CLS rows under this fusion)
+        const bool itc = d_logits || e.bd_itc_global;
+        if (itc) CHECK_RC(itc_backward_to_tpool(e, s));
+        AspectFusionArgs ab = aspect_fusion(e.wsp<float>(e.h_tpool), e.wsp<float>(e.h_vpool), W + e.asp_w, W + e.asp_b, B, H, feats,
+                                            e.wsp<float>(e.h_asp_w), e.wsp<float>(e.h_asp_e));
+        ab.d_feats = dfeats; ab.d_tpool = e.wsp<float>(e.h_dtpool); ab.da = Gd + e.asp_w; ab.db = Gd + e.asp_b;
+        ab.partial = e.wsp<float>(e.h_asp_partial); ab.accumulate = itc; ab.accumulate_dw = 1;
+        CHECK_HIP(launch_aspect_fusion_bwd(ab, s));
+        CHECK_RC(text_pooler_backward(e, 0, s));
+        CHECK_HIP(launch_scatter_cls_rows(dxcls, e.ws + e.g_dx, Bt, e.cls_compact ? 1 : T, H, dt, s, e.gscale()));
+        return 0;
+    }
     // feats = relu(linear_fusion(z))
     float* dpre = e.wsp<float>(e.h_dpre);
     CHECK_HIP(launch_elementwise(EW_RELU_BWD, dfeats, feats, dpre, (size_t)Bt * H, 0.f, nodrop, s));
@@ -1011,32 +1091,8 @@ int heads_backward(mmhip_engine& e, hipStream_t s) {
         CHECK_HIP(launch_small_nn(small(e.wsp<float>(e.h_dq), H, W + e.fq_w, H, nullptr, dxcls, H, Bt, H, H, ACT_NONE, 1), s));
     }
     if (d_logits || e.bd_itc_global) {
-        if (e.bd_itc_global) {
-            // gathered form: this rank's rows of d T_n / d I_n collect both cross-entropy directions over all G posts.  Seed: the loss is the SAME
-            // global clip_loss on every rank and each rank differentiates it through its own rows only, so the ranks' parameter gradients sum to
-            // the single-process gradient; the exchange then averages (1 / world), hence the factor `world` here
-            const int G = e.itc_world * B;
-            ItcGlobalBwdArgs gb{};
-            gb.txt_n = e.wsp<float>(e.h_g_txt); gb.img_n = e.wsp<float>(e.h_g_img); gb.logit_scale = W + e.logit_scale;
-            gb.rowlse = e.wsp<float>(e.h_g_rowlse); gb.collse = e.wsp<float>(e.h_g_collse);
-            gb.txt_inv = e.wsp<float>(e.h_txt_inv); gb.img_inv = e.wsp<float>(e.h_img_inv);
-            gb.d_txt_n = e.wsp<float>(e.h_g_dtn); gb.d_img_n = e.wsp<float>(e.h_g_din);
-            gb.dtxt_e = e.wsp<float>(e.h_dtxt_e); gb.dimg_e = e.wsp<float>(e.h_dimg_e); gb.dlogit_scale = Gd + e.logit_scale;
-            gb.ws = e.wsp<float>(e.h_g_ws); gb.G = G; gb.E = E; gb.Bl = B; gb.r0 = e.itc_rank * B;
-            gb.scale = e.bd_w_itc * (float)e.itc_world / (2.f * (float)G);
-            CHECK_HIP(launch_itc_global_bwd(gb, s));
-        } else {
-            ItcBwdArgs ib{d_logits, e.wsp<float>(e.h_logits), e.wsp<float>(e.h_txt_n), e.wsp<float>(e.h_img_n), e.wsp<float>(e.h_txt_inv),
-                          e.wsp<float>(e.h_img_inv), W + e.logit_scale, e.wsp<float>(e.h_dtxt_e), e.wsp<float>(e.h_dimg_e), Gd + e.logit_scale, B, E};
-            CHECK_HIP(launch_itc_bwd(ib, s));
-        }
-        CHECK_HIP(launch_small_tn(small(e.wsp<float>(e.h_dtxt_e), E, e.wsp<float>(e.h_tpool), H, nullptr, Gd + e.tproj_w, H, B, H, 0, 0, 1), DT_F32, E, s));
-        CHECK_HIP(launch_small_tn(small(e.wsp<float>(e.h_dimg_e), E, e.wsp<float>(e.h_vpool), Hv, nullptr, Gd + e.vproj_w, Hv, B, Hv, 0, 0, 1), DT_F32, E, s));
-        CHECK_HIP(launch_small_nn(small(e.wsp<float>(e.h_dtxt_e), E, W + e.tproj_w, H, nullptr, e.wsp<float>(e.h_dtpool), H, B, H, E), s));
-        CHECK_HIP(launch_elementwise(EW_TANH_BWD, e.wsp<float>(e.h_dtpool), e.wsp<float>(e.h_tpool), e.wsp<float>(e.h_dprepool), (size_t)B * H, 0.f, nodrop, s));
-        CHECK_HIP(launch_small_tn(small(e.wsp<float>(e.h_dprepool), H, z, ZW, nullptr, Gd + e.t_pool_w, H, B, H, 0, 0, 1), DT_F32, H, s));
-        CHECK_HIP(launch_bias_grad_f32(e.wsp<float>(e.h_dprepool), B, H, H, Gd + e.t_pool_b, 1, s));
-        CHECK_HIP(launch_small_nn(small(e.wsp<float>(e.h_dprepool), H, W + e.t_pool_w, H, nullptr, dxcls, H, B, H, H, ACT_NONE, 1), s));
+        CHECK_RC(itc_backward_to_tpool(e, s));
+        CHECK_RC(text_pooler_backward(e, 1, s));
     }
     // gradient of the last hidden state: CLS rows only
     // gradient of the last hidden state: CLS rows only (compact [Bt, H] when the last layer ran on CLS rows)
@@ -1445,6 +1501,7 @@ int mmhip_create(const mmhip_config* cfg, mmhip_handle* out) {
         if (c.img_kind != MMHIP_IMG_VIT && c.img_kind != MMHIP_IMG_CLIP) return MMHIP_E_INVALID;
         if (hv % 128 || hv > 1024 || nh * 64 != hv || iv % 128 || c.patch < 2 || c.image % c.patch) return MMHIP_E_INVALID;
         if (c.fusion == MMHIP_FUSION_ATTENTION && hv != c.hidden) return MMHIP_E_INVALID;       // fc_K / fc_V are hidden x hidden (mm_late.py:74-75)
+        if (c.fusion == MMHIP_FUSION_ASPECT && hv != c.hidden) return MMHIP_E_INVALID;          // the two pooler outputs are stacked into one matrix (mm_late.py:120)
         // attention keeps the K / V of a head in LDS: 608 keys of 64 x 16 bit fill the 160 KB of a CU (336 / 14 -> 577 tokens);
         // the fp32 parity-mode attention holds 4-byte K / V: 288 keys
         const int P = (c.image / c.patch) * (c.image / c.patch) + 1;
@@ -1550,6 +1607,8 @@ int mmhip_forward(mmhip_handle h, const int64_t* ids, const int64_t* mask, const
     if (!ids || !mask || B < 1 || T < 1) return MMHIP_E_INVALID;
     if ((tim_ids == nullptr) != (tim_mask == nullptr)) return MMHIP_E_INVALID;
     mmhip_engine& e = *h;
+    // aspect-att has no ITM pass: the reference's second mm_fusion call (models/mm_late.py:181) comes without the pooled inputs and raises
+    if (e.aspect() && tim_ids) return MMHIP_E_INVALID;
     const bool imported = pixels == nullptr;           // image tower outputs come from the caller's cache (mmhip_vision_import)
     if (imported && e.vision_ready_B != B) return MMHIP_E_STATE;
     e.vision_ready_B = 0;
@@ -1866,6 +1925,7 @@ static int train_step_impl(mmhip_handle h, const int64_t* ids, const int64_t* ma
     if (!adam_m || !adam_v || !onehot || step < 1) return MMHIP_E_INVALID;
     if (use_itm && (!tim_ids || !lbl_tim)) return MMHIP_E_INVALID;
     mmhip_engine& e = *h;
+    if (e.aspect() && (use_itm || tim_ids)) return MMHIP_E_INVALID;      // models/mm_late.py:181 (mmhip_forward)
     e.skip_itc = !use_itc;
     const int rf = mmhip_forward(h, ids, mask, pixels, use_itm ? tim_ids : nullptr, use_itm ? tim_mask : nullptr, B, T, 1, seed, nullptr, nullptr,
                                  nullptr, nullptr, stream);

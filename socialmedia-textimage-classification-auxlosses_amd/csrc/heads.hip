@@ -3,6 +3,8 @@
 //     only row 0 of softmax(Q K^T) V is consumed, and K = x_v W_K^T + b_K, V = x_v W_V^T + b_V are affine in the
 //     frozen image tokens, so   scores_j = (W_K^T q) . x_v[j] (+ const),  ctx = W_V (sum_j p_j x_v[j]) + b_V
 //     -- exact algebra, 0.47 GF/post of fc_K/fc_V GEMMs become two [B,768]x[768,768] products.
+//   * aspect-att fusion (reference models/mm_late.py:115-131) on the two pooler outputs: a two-slot tanh / softmax mix per post, one wave per
+//     post, and its backward with ordered partial sums for the two parameter gradients (at the end of this file)
 //   * ITC similarity (HF vision_text_dual_encoder :261-274) and its backward
 //   * fused loss forward+backward: weighted soft-target CE (run_mm_late.py:85), clip_loss (utils.py:225-231),
 //     ITM CE (run_mm_late.py:97), mixed as models/mm_late.py:473-487
@@ -851,6 +853,143 @@ hipError_t launch_cls_head_bwd(const ClsHeadArgs& a, hipStream_t s) {
     if (!cls_head_shape_ok(a) || !a.d_logits) return hipErrorInvalidValue;
     if (a.dx && (a.dx_stride < (size_t)a.H || (a.dx_dtype != DT_BF16 && a.dx_dtype != DT_F16 && a.dx_dtype != DT_F32))) return hipErrorInvalidValue;
     hipLaunchKernelGGL(cls_head_bwd_kernel, dim3(a.H / 64), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------ aspect-att fusion (reference models/mm_late.py:115-131)
+// V = reshape(cat(t_pool, v_pool), [B, 2, H]): slot j of post n is row 2 n + j of the [2 B, H] matrix [t_pool; v_pool] -- a RESHAPE, so for B > 1 a
+// post pairs two text rows, a text and an image row of different posts, or two image rows.  That is the reference's behaviour and the parity target.
+//   e_j = tanh(V_j . a + b),  w = softmax(e_0, e_1),  feats = relu(w_0 V_0 + w_1 V_1)
+// Latency-bound like the CLS head: one wave per post, a lane keeps its H / 64 elements of both rows in registers.  fp32, tanhf / expf of the device
+// library, no atomics: every output word has one writer and every sum a fixed order.
+static constexpr int ASPECT_WAVES = 8;
+__device__ __forceinline__ const float* aspect_row(const AspectFusionArgs& a, int r) {
+    return r < a.B ? a.t_pool + (size_t)r * a.H : a.v_pool + (size_t)(r - a.B) * a.H;
+}
+__global__ __launch_bounds__(64 * ASPECT_WAVES) void aspect_fusion_fwd_kernel(AspectFusionArgs a) {
+    const int lane = threadIdx.x & 63, n = blockIdx.x * ASPECT_WAVES + (threadIdx.x >> 6), H = a.H;
+    if (n >= a.B) return;
+    const float* v0 = aspect_row(a, 2 * n);
+    const float* v1 = aspect_row(a, 2 * n + 1);
+    float x0[16], x1[16], d0 = 0.f, d1 = 0.f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const int c = lane + 64 * j;
+        x0[j] = x1[j] = 0.f;
+        if (c < H) {
+            const float aw = a.a[c];
+            x0[j] = v0[c]; x1[j] = v1[c];
+            d0 = fmaf(x0[j], aw, d0);
+            d1 = fmaf(x1[j], aw, d1);
+        }
+    }
+    const float bias = a.b[0];
+    const float e0 = tanhf(wave_sum(d0) + bias), e1 = tanhf(wave_sum(d1) + bias);
+    const float mx = fmaxf(e0, e1), p0 = expf(e0 - mx), p1 = expf(e1 - mx);
+    const float w0 = p0 / (p0 + p1), w1 = p1 / (p0 + p1);
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const int c = lane + 64 * j;
+        if (c < H) a.feats[(size_t)n * H + c] = fmaxf(fmaf(w1, x1[j], w0 * x0[j]), 0.f);
+    }
+    if (lane == 0) {
+        a.w[2 * n] = w0; a.w[2 * n + 1] = w1;
+        a.e[2 * n] = e0; a.e[2 * n + 1] = e1;
+    }
+}
+// Backward.  With g = d feats . (feats > 0) and dw_j = g . V_j the two-slot softmax gives ds_0 = w_0 (dw_0 - sum_k w_k dw_k) = w_0 w_1 (dw_0 - dw_1)
+// = -ds_1 (the difference form: no cancellation against the weighted mean); dpre_j = ds_j (1 - e_j^2); dV_j = w_j g + dpre_j a.  Text rows of
+// d t_pool are written by the one wave that owns them, image rows (the tower is frozen) not at all.  d a = sum dpre_j V_j and d b = sum dpre_j: the
+// eight waves of a block add their posts' terms through LDS in wave order into the block's row of `partial`; aspect_fusion_reduce_kernel adds
+// the rows in block order.
+__global__ __launch_bounds__(64 * ASPECT_WAVES) void aspect_fusion_bwd_kernel(AspectFusionArgs a) {
+    __shared__ float red[ASPECT_WAVES][1024];
+    __shared__ float redb[ASPECT_WAVES];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, n = blockIdx.x * ASPECT_WAVES + w, H = a.H;
+    float x0[16], x1[16], g[16], dp0 = 0.f, dp1 = 0.f, w0 = 0.f, w1 = 0.f;
+    if (n < a.B) {          // wave-uniform
+        const float* v0 = aspect_row(a, 2 * n);
+        const float* v1 = aspect_row(a, 2 * n + 1);
+        float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int c = lane + 64 * j;
+            x0[j] = x1[j] = g[j] = 0.f;
+            if (c < H) {
+                x0[j] = v0[c]; x1[j] = v1[c];
+                g[j] = a.feats[(size_t)n * H + c] > 0.f ? a.d_feats[(size_t)n * H + c] : 0.f;
+                s0 = fmaf(g[j], x0[j], s0);
+                s1 = fmaf(g[j], x1[j], s1);
+            }
+        }
+        w0 = a.w[2 * n]; w1 = a.w[2 * n + 1];
+        const float e0 = a.e[2 * n], e1 = a.e[2 * n + 1];
+        const float ds0 = w0 * w1 * (wave_sum(s0) - wave_sum(s1));
+        dp0 = ds0 * (1.f - e0 * e0);
+        dp1 = -ds0 * (1.f - e1 * e1);
+    }
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const int c = lane + 64 * j;
+        if (c < H) {
+            float da = 0.f;
+            if (n < a.B) {
+                const float aw = a.a[c];
+                if (2 * n < a.B) {
+                    float* dst = a.d_tpool + (size_t)(2 * n) * H + c;
+                    const float v = fmaf(dp0, aw, w0 * g[j]);
+                    *dst = a.accumulate ? *dst + v : v;
+                }
+                if (2 * n + 1 < a.B) {
+                    float* dst = a.d_tpool + (size_t)(2 * n + 1) * H + c;
+                    const float v = fmaf(dp1, aw, w1 * g[j]);
+                    *dst = a.accumulate ? *dst + v : v;
+                }
+                da = fmaf(dp1, x1[j], dp0 * x0[j]);
+            }
+            red[w][c] = da;
+        }
+    }
+    if (lane == 0) redb[w] = n < a.B ? dp0 + dp1 : 0.f;
+    __syncthreads();
+    float* prow = a.partial + (size_t)blockIdx.x * (H + 4);
+    for (int c = threadIdx.x; c < H; c += 64 * ASPECT_WAVES) {
+        float v = red[0][c];
+#pragma unroll
+        for (int i = 1; i < ASPECT_WAVES; ++i) v += red[i][c];
+        prow[c] = v;
+    }
+    if (threadIdx.x == 0) {
+        float v = redb[0];
+#pragma unroll
+        for (int i = 1; i < ASPECT_WAVES; ++i) v += redb[i];
+        prow[H] = v;
+    }
+}
+__global__ __launch_bounds__(256) void aspect_fusion_reduce_kernel(AspectFusionArgs a, int blocks) {
+    const int c = blockIdx.x * 256 + threadIdx.x, H = a.H;
+    if (c > H) return;
+    float v = a.partial[c];
+    for (int i = 1; i < blocks; ++i) v += a.partial[(size_t)i * (H + 4) + c];
+    float* dst = c < H ? a.da + c : a.db;
+    *dst = a.accumulate_dw ? *dst + v : v;
+}
+static bool aspect_shape_ok(const AspectFusionArgs& a) {
+    return a.B >= 1 && a.H >= 64 && a.H <= 1024 && a.H % 64 == 0 && a.t_pool && a.v_pool && a.a && a.b && a.feats && a.w && a.e;
+}
+size_t aspect_fusion_partial_floats(int B, int H) { return (size_t)((B + ASPECT_WAVES - 1) / ASPECT_WAVES) * (size_t)(H + 4); }
+hipError_t launch_aspect_fusion_fwd(const AspectFusionArgs& a, hipStream_t s) {
+    if (!aspect_shape_ok(a)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(aspect_fusion_fwd_kernel, dim3((a.B + ASPECT_WAVES - 1) / ASPECT_WAVES), dim3(64 * ASPECT_WAVES), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t launch_aspect_fusion_bwd(const AspectFusionArgs& a, hipStream_t s) {
+    if (!aspect_shape_ok(a) || !a.d_feats || !a.d_tpool || !a.da || !a.db || !a.partial) return hipErrorInvalidValue;
+    const int blocks = (a.B + ASPECT_WAVES - 1) / ASPECT_WAVES;
+    hipLaunchKernelGGL(aspect_fusion_bwd_kernel, dim3(blocks), dim3(64 * ASPECT_WAVES), 0, s, a);
+    hipError_t r = hipGetLastError();
+    if (r != hipSuccess) return r;
+    hipLaunchKernelGGL(aspect_fusion_reduce_kernel, dim3((a.H + 1 + 255) / 256), dim3(256), 0, s, a, blocks);
     return hipGetLastError();
 }
 

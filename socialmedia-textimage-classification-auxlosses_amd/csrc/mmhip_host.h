@@ -89,6 +89,14 @@ inline ClsHeadArgs cls_head(const void* x, size_t x_stride, int x_dtype, const f
     return a;
 }
 
+// ------------------------------------------------------------------------------------------------ aspect-att fusion head
+// the part both launches share: the two pooler outputs, aspectattention.*, and what the forward leaves for the backward
+inline AspectFusionArgs aspect_fusion(const float* t_pool, const float* v_pool, const float* a, const float* b, int B, int H, float* feats, float* w, float* e) {
+    AspectFusionArgs f{};
+    f.t_pool = t_pool; f.v_pool = v_pool; f.a = a; f.b = b; f.B = B; f.H = H; f.feats = feats; f.w = w; f.e = e;
+    return f;
+}
+
 // ------------------------------------------------------------------------------------------------ attention
 // qkv is [rows, 3 hidden] packed q | k | v, ctx [rows, hidden]; scores are scaled by 1 / sqrt(head width).  Every model here has 64-wide heads
 // (mmhip_create / mmhip_early_create insist on heads * 64 == hidden; the op entry points pass hidden = heads * 64), and 1 / sqrtf(64.f) is exactly

@@ -359,6 +359,25 @@ struct ClsHeadArgs {
 hipError_t launch_cls_head_fwd(const ClsHeadArgs& a, hipStream_t s);
 hipError_t launch_cls_head_bwd(const ClsHeadArgs& a, hipStream_t s);
 
+// aspect-att fusion head (reference models/mm_late.py:115-131), fp32: V = reshape([t_pool; v_pool], [B, 2, H]) -- slot j of post n is row 2 n + j of
+// the stacked [2 B, H] matrix, read through the two base pointers -- e = tanh(V a + b), w = softmax over the two slots, feats = relu(sum_j w_j V_j).
+// Limits: B >= 1, H % 64 == 0, 64 <= H <= 1024.  No atomics: every output word has one writer, every sum a fixed order.
+struct AspectFusionArgs {
+    const float* t_pool; const float* v_pool;     // [B, H] each
+    const float* a; const float* b;               // aspectattention.weight [H], .bias [1]
+    int B, H;
+    float* feats; float* w; float* e;             // [B, H], [B, 2], [B, 2]: written by the forward, read by the backward
+    // backward
+    const float* d_feats;                         // [B, H]
+    float* d_tpool;                               // [B, H]: every row written (accumulate != 0: added to); rows of v_pool get no gradient
+    float* da; float* db;                         // [H], [1] (accumulate_dw != 0: added to)
+    float* partial;                               // scratch of aspect_fusion_partial_floats(B, H) floats
+    int accumulate, accumulate_dw;
+};
+size_t aspect_fusion_partial_floats(int B, int H);
+hipError_t launch_aspect_fusion_fwd(const AspectFusionArgs& a, hipStream_t s);
+hipError_t launch_aspect_fusion_bwd(const AspectFusionArgs& a, hipStream_t s);
+
 // ---------------------------------------------------------------- optimizer
 struct AdamWArgs {
     float* p; float* g; float* m; float* v; size_t n;

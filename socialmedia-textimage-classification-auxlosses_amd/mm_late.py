@@ -37,6 +37,12 @@ class Scaled_Dot_Product_Attention(nn.Module):
         return torch.matmul(attention, V), scores
 
 
+_FUSIONS = {"concat": _lib.FUSION_CONCAT, "attention": _lib.FUSION_ATTENTION, "aspect-att": _lib.FUSION_ASPECT}
+# the reference's ITM pass calls mm_fusion without the pooled inputs that aspect-att stacks, and raises inside torch.stack
+ASPECT_ITM_MESSAGE = ("fusion 'aspect-att' has no image-text matching pass: the reference's second mm_fusion call (models/mm_late.py:181) comes "
+                      "without the pooler outputs and raises; run it without --use_tim_loss / tim_inputs")
+
+
 def default_arch(txt_model_name, img_model_name):
     if txt_model_name not in TEXT_ARCH:
         raise ValueError(f"text model {txt_model_name!r}: late-fusion path supports {sorted(TEXT_ARCH)}")
@@ -112,9 +118,9 @@ class MM_Model(WordTableEngineModule):
         self.itc_global = bool(itc_global)
         if not torch.cuda.is_available():
             raise _lib.MMHipError("MM_Model needs an MI355X (gfx950) GPU: the HIP path has no CPU fallback")
-        if fusion_name not in ("concat", "attention"):
-            raise NotImplementedError(f"fusion {fusion_name!r}: the HIP late-fusion path implements 'attention' and 'concat' "
-                                      "(reference models/mm_late.py:92-113)")
+        if fusion_name not in _FUSIONS:
+            raise NotImplementedError(f"fusion {fusion_name!r}: the HIP late-fusion path implements 'attention', 'concat' and 'aspect-att' "
+                                      "(reference models/mm_late.py:92-131)")
         self.num_labels, self.fusion_name = num_labels, fusion_name
         self.txt_model_name, self.img_model_name = txt_model_name, img_model_name
         self.device_ = torch.device(device if device is not None else f"cuda:{int(os.environ.get('LOCAL_RANK', 0))}")
@@ -137,6 +143,9 @@ class MM_Model(WordTableEngineModule):
         if fusion_name == "attention" and a["hidden_img"] not in (0, a["hidden"]):
             raise NotImplementedError("attention fusion needs image tokens as wide as the text tower (fc_K / fc_V are 768 x 768, reference "
                                       "models/mm_late.py:74-75): use fusion_name='concat' with the CLIP-ViT-L/14 tower")
+        if fusion_name == "aspect-att" and a["hidden_img"] not in (0, a["hidden"]):
+            raise NotImplementedError("aspect-att fusion stacks the two pooler outputs into one matrix (reference models/mm_late.py:120): the towers "
+                                      "must be equally wide; use fusion_name='concat' with the CLIP-ViT-L/14 tower")
         self.arch = a
         self.dtype_name = dtype
         # parity mode only (include/mmhip.h mmhip_set_backward_products): MFMA products per reduction slice in the backward's matrix products;
@@ -149,7 +158,7 @@ class MM_Model(WordTableEngineModule):
                             txt_kind=_lib.TXT_XLMR if a["txt_kind"] == "xlmr" else _lib.TXT_BERT, pad_id=a["pad_id"],
                             ln_eps_txt=a["ln_eps_txt"], ln_eps_img=a["ln_eps_img"], image=a["image"], patch=a["patch"],
                             proj_dim=a["proj_dim"], num_labels=num_labels,
-                            fusion=_lib.FUSION_ATTENTION if fusion_name == "attention" else _lib.FUSION_CONCAT,
+                            fusion=_FUSIONS[fusion_name],
                             p_hidden=a["p_hidden"], p_attn=a["p_attn"], p_head=float(dropout),
                             img_kind=_lib.IMG_CLIP if a["img_kind"] == "clip" else _lib.IMG_VIT, hidden_img=int(a["hidden_img"]),
                             heads_img=int(a["heads_img"]), inter_img=int(a["inter_img"]),
@@ -353,6 +362,8 @@ class MM_Model(WordTableEngineModule):
         """-> (out_cls, logits_per_text, out_tim | None, out_iadds = None, mm_features)   (mm_late.py:148-193)"""
         if iadds_task:
             raise NotImplementedError("iadds head is deprecated in the reference (models/config.py:65,68)")
+        if tim_inputs is not None and self.fusion_name == "aspect-att":
+            raise NotImplementedError(ASPECT_ITM_MESSAGE)
         tim_ids, tim_mask = tim_inputs if tim_inputs is not None else (None, None)
         if torch.is_grad_enabled() and any(i["param"].requires_grad for i in self._train_params):
             params = [i["param"] for i in self._train_params]
@@ -376,6 +387,8 @@ class MMLate_Model(FlatTrainer):
     def __init__(self, config, txt_model_name, img_model_name, fusion_name, multilabel=False, **model_kw):
         if multilabel:
             raise NotImplementedError("multilabel BCE branch: no task enables it in the reference (models/config.py:10)")
+        if fusion_name == "aspect-att" and config.use_tim_loss:
+            raise NotImplementedError(ASPECT_ITM_MESSAGE)
         self.batch_size, self.num_labels = config.batch_size, config.num_labels
         self.multilabel = multilabel
         self.use_clip_loss, self.beta_itc = config.use_clip_loss, config.beta_itc
