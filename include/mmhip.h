@@ -409,8 +409,10 @@ int mmhip_op_attn_bwd_long(int dtype, const void* qkv, const float* maskbias, co
  *        strips of all ranks sum to the full derivative); txt_inv / img_inv [B_local] (1 / |e|) with d_txt_e / d_img_e [B_local, E]: the same
  *        through the normalisation (all four may be NULL). */
 uint64_t mmhip_op_itc_global_ws_bytes(int G, int B_local);
-/* the rank-local ITC pair the engine runs at world 1 (csrc/heads.hip launch_itc_fwd / launch_itc_bwd), for timing beside the global pair
- * (tools/itc_bench.py): normalisation + logits_per_text [B, B]; its backward from d_logits [B, B] (d_logit_scale accumulated, may be NULL) */
+/* the rank-local ITC pair both engines run unless global-batch ITC is on (csrc/heads.hip launch_itc_fwd / launch_itc_bwd), alone: the operator tests, and
+ * timing beside the global pair (tools/itc_bench.py).  fwd: txt_inv / img_inv [B] = 1 / |e|, txt_n / img_n [B, E] = e / |e|, logits [B, B] =
+ * exp(logit_scale) txt_n img_n^T, all overwritten.  bwd from d_logits [B, B] and the forward's outputs: d_txt_e / d_img_e [B, E] overwritten,
+ * d_logit_scale[0] += sum d_logits * logits (may be NULL).  MMHIP_E_INVALID before any launch: B < 1 or > 1024, E < 1 or > 1024, a NULL tensor. */
 int mmhip_op_itc_fwd(const float* txt_e, const float* img_e, const float* logit_scale, int B, int E, float* txt_n, float* img_n, float* txt_inv, float* img_inv,
                      float* logits, void* stream);
 int mmhip_op_itc_bwd(const float* d_logits, const float* logits, const float* txt_n, const float* img_n, const float* txt_inv, const float* img_inv,
@@ -626,6 +628,37 @@ int mmhip_img_train_step(mmhip_img_handle h, const float* pixels, const int64_t*
 uint64_t mmhip_op_vit_embed_bwd_ws_bytes(int B, int P, int H);
 int mmhip_op_vit_embed_bwd(int dtype, const void* dx, int B, int P, int H, float alpha, float* dpos, float* dcls, void* dpe, int pair_hi_only, void* ws,
                            uint64_t ws_bytes, void* stream);
+/* The text-embedding launches alone (operator tests; csrc/rowops.hip launch_embed_fwd / launch_embed_bwd), on caller-owned buffers.  dtype MMHIP_BF16 |
+ * _F16 | _F32 is the type of x, xhat and dx; tables, gamma, beta and every gradient are fp32; rows = posts * T.
+ *   fwd: ids / mask [rows] int64, type_ids [rows] int64 or NULL (NULL: every token takes row 0 of `type`), word / pos / type the three tables of
+ *        width H.  Every output is OVERWRITTEN, every element of it: pos_ids [rows] int32 (xlmr != 0: cumsum(ids != pad_id) * (ids != pad_id) +
+ *        pad_id per post; else the slot index), maskbias [rows] (0 where mask != 0, else -inf), xhat [rows, H] (optional) the normalised row
+ *        word[id] + type[tt] + pos[pos_id], rstd [rows] (optional), x [rows, H] = dropout_p(xhat * gamma + beta) with the engine's hash (stream 1,
+ *        element row * H + c).  _F32 only: x_pair (optional) receives x as bf16 planes, hi at row * ld_pair + c and lo `lo_pair` elements behind
+ *        (lo_pair >= H, ld_pair >= lo_pair + H, both multiples of 4).
+ *   bwd: from dx [rows, H], the forward's xhat, rstd, pos_ids and the same p / seed.  With alpha' = (alpha == 0 ? 1 : alpha) every gradient is ADDED
+ *        to what its buffer holds: dword[id] += alpha' d (id != pad_id), dpos[pos_id] += alpha' d (pos_id != pos_pad_id: pad_id for XLM-R, -1 for
+ *        BERT), dgamma += alpha' sum dy xhat, dbeta += alpha' sum dy (dy = dx after the dropout mask and scale), d the LayerNorm backward of the
+ *        row.  dtype_rows: without type_ids row 0 += alpha' sum d; with type_ids row 1 += the type-1 tokens' sum and -- type_rows == 2 only -- row 0
+ *        += the type-0 tokens'.  Rows no token names keep their bytes.  row_state (optional, 4-byte aligned, its length rounded up to 4): bit 0 of
+ *        byte id is OR-ed in for every id != pad_id that occurs.  status (optional) {counter, flag}: each wave that meets a non-finite row sum adds 1
+ *        and ORs 1 into the flag.  partial (optional): scratch of mmhip_op_embed_bwd_ws_bytes(posts, T, H, type_rows) bytes (3 vectors per block,
+ *        4 with type_rows == 2), overwritten; the column sums then go through it in two stages.  det_rows (optional, [rows, H] fp32, overwritten
+ *        with alpha' d per slot) with max_pos = the rows of dpos: the deterministic mode -- dword / dpos are summed from det_rows in slot order by one
+ *        writer per row, no atomics, the same bits on every call.
+ * MMHIP_E_INVALID before any launch, nothing written: a required pointer NULL, posts / T / H < 1, H % 4 != 0, H > 1024, p outside [0, 1), a dtype
+ * other than the three, type_rows == 2 without type_ids, det_rows without max_pos >= 1, x_pair with a 16-bit dtype or bad strides, word / pos / type
+ * / gamma / beta / x / xhat / x_pair / dx / det_rows off 16-byte alignment (row_state / status / partial: 4-byte).  MMHIP_E_CAPACITY: partial with
+ * fewer bytes than the query names.  The ids live on the device and are NOT checked here: ids must lie in [0, rows of word), type ids in [0, rows of
+ * type), and the position ids they give (at most pad_id + T for XLM-R, T - 1 otherwise) inside pos and below max_pos. */
+int mmhip_op_embed_fwd(int dtype, const int64_t* ids, const int64_t* mask, const int64_t* type_ids, const float* word, const float* pos, const float* type,
+                       const float* gamma, const float* beta, float eps, int posts, int T, int H, int xlmr, int pad_id, float p, uint64_t seed, void* x,
+                       void* xhat, float* rstd, int* pos_ids, float* maskbias, void* x_pair, int ld_pair, int lo_pair, void* stream);
+uint64_t mmhip_op_embed_bwd_ws_bytes(int posts, int T, int H, int type_rows);
+int mmhip_op_embed_bwd(int dtype, const void* dx, const void* xhat, const float* rstd, const float* gamma, const int64_t* ids, const int* pos_ids,
+                       const int64_t* type_ids, int type_rows, int posts, int T, int H, int pad_id, int pos_pad_id, float p, uint64_t seed, float alpha,
+                       float* dword, float* dpos, float* dtype_rows, float* dgamma, float* dbeta, void* partial, uint64_t partial_bytes, uint8_t* row_state,
+                       float* det_rows, int max_pos, unsigned* status, void* stream);
 
 #ifdef __cplusplus
 }

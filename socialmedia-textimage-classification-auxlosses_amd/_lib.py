@@ -188,6 +188,9 @@ _SIGS = {
     "mmhip_img_train_step": (I, [P, P, P, P, I, P, P, F, F, F, F, F, I, P, P, P]),
     "mmhip_op_vit_embed_bwd_ws_bytes": (U64, [I, I, I]),
     "mmhip_op_vit_embed_bwd": (I, [I, P, I, I, I, F, P, P, P, I, P, U64, P]),
+    "mmhip_op_embed_fwd": (I, [I, P, P, P, P, P, P, P, P, F, I, I, I, I, I, F, U64, P, P, P, P, P, P, I, I, P]),
+    "mmhip_op_embed_bwd_ws_bytes": (U64, [I, I, I, I]),
+    "mmhip_op_embed_bwd": (I, [I, P, P, P, P, P, P, P, I, I, I, I, I, I, F, U64, F, P, P, P, P, P, P, U64, P, P, I, P, P]),
     "mmhip_version": (C.c_char_p, []),
 }
 EXPORTS = tuple(_SIGS)

@@ -442,4 +442,56 @@ int mmhip_op_vit_embed_bwd(int dtype, const void* dx, int B, int P, int H, float
     return r == hipErrorInvalidValue ? MMHIP_E_INVALID : (int)r;
 }
 
+// ------------------------------------------------------------------------------------------------ text embeddings (forward, backward scatter)
+namespace {
+inline bool embed_shape_ok(int dtype, int posts, int T, int H) {
+    return (dtype == MMHIP_BF16 || dtype == MMHIP_F16 || dtype == MMHIP_F32) && posts >= 1 && T >= 1 && H >= 4 && H % 4 == 0 && H <= 1024;
+}
+inline bool off16(std::initializer_list<const void*> ps) {
+    uintptr_t v = 0;
+    for (const void* p : ps) v |= (uintptr_t)p;
+    return (v & 15) != 0;
+}
+}  // namespace
+
+int mmhip_op_embed_fwd(int dtype, const int64_t* ids, const int64_t* mask, const int64_t* type_ids, const float* word, const float* pos, const float* type,
+                       const float* gamma, const float* beta, float eps, int posts, int T, int H, int xlmr, int pad_id, float p, uint64_t seed, void* x,
+                       void* xhat, float* rstd, int* pos_ids, float* maskbias, void* x_pair, int ld_pair, int lo_pair, void* stream) {
+    if (!ids || !mask || !word || !pos || !type || !gamma || !beta || !x || !pos_ids || !maskbias) return MMHIP_E_INVALID;
+    if (!embed_shape_ok(dtype, posts, T, H) || !(p >= 0.f) || p >= 1.f) return MMHIP_E_INVALID;
+    if (off16({word, pos, type, gamma, beta, x, xhat, x_pair})) return MMHIP_E_INVALID;      // 16-byte row accesses (8-byte for the 16-bit rows)
+    if (x_pair && (dtype != MMHIP_F32 || lo_pair < H || ld_pair < lo_pair + H || ld_pair % 4 || lo_pair % 4)) return MMHIP_E_INVALID;
+    EmbedArgs a{};
+    a.ids = ids; a.mask = mask; a.type_ids = type_ids; a.word = word; a.pos = pos; a.type = type; a.gamma = gamma; a.beta = beta; a.eps = eps;
+    a.x = x; a.xhat = xhat; a.rstd = rstd; a.pos_ids = pos_ids; a.maskbias = maskbias;
+    a.posts = posts; a.T = T; a.H = H; a.xlmr = xlmr; a.pad_id = pad_id;
+    a.drop = make_drop(p, seed, STREAM_EMBED, 1);
+    if (x_pair) { a.x_pair = x_pair; a.ld_pair = ld_pair; a.lo_pair = lo_pair; }
+    const hipError_t r = launch_embed_fwd(a, dtype, (hipStream_t)stream);
+    return r == hipErrorInvalidValue ? MMHIP_E_INVALID : (int)r;
+}
+
+uint64_t mmhip_op_embed_bwd_ws_bytes(int posts, int T, int H, int type_rows) {
+    if (posts < 1 || T < 1 || H < 1) return 0;
+    return (uint64_t)(partial_floats_embed(posts, T, H) / 3 * (type_rows == 2 ? 4 : 3)) * 4;
+}
+int mmhip_op_embed_bwd(int dtype, const void* dx, const void* xhat, const float* rstd, const float* gamma, const int64_t* ids, const int* pos_ids,
+                       const int64_t* type_ids, int type_rows, int posts, int T, int H, int pad_id, int pos_pad_id, float p, uint64_t seed, float alpha,
+                       float* dword, float* dpos, float* dtype_rows, float* dgamma, float* dbeta, void* partial, uint64_t partial_bytes, uint8_t* row_state,
+                       float* det_rows, int max_pos, unsigned* status, void* stream) {
+    if (!dx || !xhat || !rstd || !gamma || !ids || !pos_ids || !dword || !dpos || !dtype_rows || !dgamma || !dbeta) return MMHIP_E_INVALID;
+    if (!embed_shape_ok(dtype, posts, T, H) || !(p >= 0.f) || p >= 1.f) return MMHIP_E_INVALID;
+    if ((type_rows == 2 && !type_ids) || (det_rows && max_pos < 1)) return MMHIP_E_INVALID;
+    if (off16({dx, xhat, gamma, det_rows}) || (((uintptr_t)row_state | (uintptr_t)status | (uintptr_t)partial) & 3)) return MMHIP_E_INVALID;
+    if (partial && partial_bytes < mmhip_op_embed_bwd_ws_bytes(posts, T, H, type_rows)) return MMHIP_E_CAPACITY;
+    EmbedBwdArgs b{};
+    b.dx = dx; b.xhat = xhat; b.rstd = rstd; b.gamma = gamma; b.ids = ids; b.pos_ids = pos_ids; b.type_ids = type_ids; b.type_rows = type_rows;
+    b.dword = dword; b.dpos = dpos; b.dtype = dtype_rows; b.dgamma = dgamma; b.dbeta = dbeta;
+    b.posts = posts; b.T = T; b.H = H; b.pad_id = pad_id; b.pos_pad_id = pos_pad_id;
+    b.drop = make_drop(p, seed, STREAM_EMBED, 1);
+    b.partial = (float*)partial; b.alpha = alpha; b.row_state = row_state; b.det_rows = det_rows; b.max_pos = max_pos; b.status = status;
+    const hipError_t r = launch_embed_bwd(b, dtype, (hipStream_t)stream);
+    return r == hipErrorInvalidValue ? MMHIP_E_INVALID : (int)r;
+}
+
 }  // extern "C"
