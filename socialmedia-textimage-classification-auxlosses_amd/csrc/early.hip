@@ -1021,11 +1021,7 @@ int mmhip_early_train_step(mmhip_early_handle h, const int64_t* ids, const int64
     CHECK_RC(forward_impl(h, ids, mask, token_type_ids, feats, boxes, nullptr, nullptr, nullptr, use_itm ? itm_src : nullptr, B, T, Nb, 1, seed, nullptr, nullptr, nullptr,
                           nullptr, stream));
     CHECK_RC(mmhip_early_loss(h, onehot, class_w, use_itm ? lbl_tim : nullptr, w_cls, use_itc ? w_itc : 0.f, use_itm ? w_itm : 0.f, loss, nullptr, stream));
-    AdamWArgs a{};
-    a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = weight_decay;
-    a.bc1 = (float)(1.0 - pow((double)beta1, step));
-    a.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, step));
-    a.zero_grad = 1; a.grad_scale = grad_scale;
+    AdamWArgs a = adamw_args(lr, beta1, beta2, eps, weight_decay, step, grad_scale, 1);
     const bool layer_opt = !on_stage && e.overlap != 0 && env_int("MMHIP_EARLY_ADAMW", 1) != 0;          // read per step
     StageOpt so{a, adam_m, adam_v};
     CHECK_RC(side_init(e));

@@ -94,9 +94,14 @@ struct mmhip_engine {
     hipEvent_t ev_fork = nullptr, ev_vit = nullptr, ev_ready[2] = {nullptr, nullptr}, ev_tn[2] = {nullptr, nullptr};
     hipEvent_t ev_layer[2] = {nullptr, nullptr}, ev_opt = nullptr;      // mmhip_train_step: per-layer AdamW on the side stream
     bool tn_pending[2] = {false, false};
+    // what the handle is: the late-fusion model (mmhip_create), or one tower under the fused CLS classifier head (mmhip_txt_create, mmhip_img_create)
+    enum Kind { LATE, TEXT, IMAGE };
+    Kind kind = LATE;
+    bool is_late() const { return kind == LATE; }
+    bool is_text() const { return kind == TEXT; }
+    bool is_image() const { return kind == IMAGE; }
     // text-only handle (mmhip_txt_create): the text tower and the fused CLS classifier head alone -- no image tower, pooler, ITC / ITM or fusion head,
     // none of their workspace; parameters under the reference's text_only.py keys (bert_model.*, linear.*)
-    bool txt_only = false;
     std::string tm_prefix = "dual_encoder.text_model.";      // state-dict prefix of the text tower
     size_t lin_w = 0, lin_b = 0;                             // text-only classifier
     size_t tt_all = 0; bool has_tt = false;                  // the engine's clamped copy of the token type ids; the last forward was given some
@@ -104,7 +109,6 @@ struct mmhip_engine {
                                                              // reads tt_all, which only a text-only workspace carves, on that handle kind only)
     // image-only handle (mmhip_img_create): the image tower, trainable, under the fused CLS classifier head -- parameters under the keys of HF
     // ViTForImageClassification (vit.*, classifier.*) in the trainable buffer, the tower's offsets in vit / v_*; no text tower, no frozen buffer
-    bool img_only = false;
     std::vector<ImgAct> iact;
     size_t i_xfin = 0, i_cls = 0, i_clsln = 0, i_mean = 0, i_rstd = 0, i_dcls = 0, i_dclsx = 0, i_dclsx_p = 0;      // last stream; CLS rows around the final LayerNorm
     size_t i_dxs[3] = {0, 0, 0}, i_dxs_p[3] = {0, 0, 0};      // residual-stream gradients (+ their plane pairs): layer l reads [(l + 1) % 3], writes [l % 3]
@@ -115,9 +119,9 @@ struct mmhip_engine {
     // every batch size.  Nothing ever writes those rows; they are cleared when the batch size changes (i_pad_B: the B they were cleared for).
     int i_pad_B = 0;
     static size_t pad64(size_t rows) { return (rows + 63) & ~(size_t)63; }
-    int nl() const { return img_only ? cfg.layers_img : cfg.layers_txt; }                 // layers with a backward stage
-    const std::vector<LayerOff>& lay() const { return img_only ? vit : txt; }
-    const std::vector<LayerW16>& lay_w16() const { return img_only ? vit_w16 : txt_w16; }
+    int nl() const { return is_image() ? cfg.layers_img : cfg.layers_txt; }                 // layers with a backward stage
+    const std::vector<LayerOff>& lay() const { return is_image() ? vit : txt; }
+    const std::vector<LayerW16>& lay_w16() const { return is_image() ? vit_w16 : txt_w16; }
     int cls_only = -1;         // -1 = read MMHIP_CLS_ONLY on first use; 1: the last text layer runs its post-attention part on CLS rows only
     bool cls_compact = false;  // state of the last forward
     int overlap = -1;          // -1 = read MMHIP_OVERLAP on first use
@@ -165,73 +169,57 @@ struct mmhip_engine {
 namespace {
 
 // ------------------------------------------------------------------------------------------------ layout
-void add_text_layer(ParamTable& b, const mmhip_config& c, const std::string& tm, int l, LayerOff& o) {
-    const int H = c.hidden, I = c.inter;
-    const std::string p = tm + "encoder.layer." + std::to_string(l) + ".";
-    const int g = MMHIP_G_ALWAYS;
-    o.begin = b.off[1];
-    o.qkv_w = b.add(p + "attention.self.query.weight", 1, g, {H, H});
-    b.add(p + "attention.self.key.weight", 1, g, {H, H});
-    b.add(p + "attention.self.value.weight", 1, g, {H, H});
-    o.qkv_b = b.add(p + "attention.self.query.bias", 1, g, {H});
-    b.add(p + "attention.self.key.bias", 1, g, {H});
-    b.add(p + "attention.self.value.bias", 1, g, {H});
-    o.ao_w = b.add(p + "attention.output.dense.weight", 1, g, {H, H});
-    o.ao_b = b.add(p + "attention.output.dense.bias", 1, g, {H});
-    o.ln1_w = b.add(p + "attention.output.LayerNorm.weight", 1, g, {H});
-    o.ln1_b = b.add(p + "attention.output.LayerNorm.bias", 1, g, {H});
-    o.fc1_w = b.add(p + "intermediate.dense.weight", 1, g, {I, H});
-    o.fc1_b = b.add(p + "intermediate.dense.bias", 1, g, {I});
-    o.fc2_w = b.add(p + "output.dense.weight", 1, g, {H, I});
-    o.fc2_b = b.add(p + "output.dense.bias", 1, g, {H});
-    o.ln2_w = b.add(p + "output.LayerNorm.weight", 1, g, {H});
-    o.ln2_b = b.add(p + "output.LayerNorm.bias", 1, g, {H});
-    o.end = b.off[1];
-}
+// One transformer layer's 16 parameters, per family: {key suffix, the LayerOff slot the row sets (none: key / value follow query, the fused QKV
+// operand reads the three as one [3H, H] block), shape}.  add_layer walks a table in its own order, so the table IS the layout of the layer.
+enum class Shape { HH, H, IH, I, HI };
+struct LayerKey { const char* suffix; size_t LayerOff::*slot; Shape shape; };
+struct LayerKeys { const char* stem; LayerKey rows[16]; };
+// BERT / XLM-R text layer (post-LN)
+const LayerKeys BERT_LAYER = {"encoder.layer.", {
+    {"attention.self.query.weight", &LayerOff::qkv_w, Shape::HH}, {"attention.self.key.weight", nullptr, Shape::HH},
+    {"attention.self.value.weight", nullptr, Shape::HH}, {"attention.self.query.bias", &LayerOff::qkv_b, Shape::H},
+    {"attention.self.key.bias", nullptr, Shape::H}, {"attention.self.value.bias", nullptr, Shape::H},
+    {"attention.output.dense.weight", &LayerOff::ao_w, Shape::HH}, {"attention.output.dense.bias", &LayerOff::ao_b, Shape::H},
+    {"attention.output.LayerNorm.weight", &LayerOff::ln1_w, Shape::H}, {"attention.output.LayerNorm.bias", &LayerOff::ln1_b, Shape::H},
+    {"intermediate.dense.weight", &LayerOff::fc1_w, Shape::IH}, {"intermediate.dense.bias", &LayerOff::fc1_b, Shape::I},
+    {"output.dense.weight", &LayerOff::fc2_w, Shape::HI}, {"output.dense.bias", &LayerOff::fc2_b, Shape::H},
+    {"output.LayerNorm.weight", &LayerOff::ln2_w, Shape::H}, {"output.LayerNorm.bias", &LayerOff::ln2_b, Shape::H}}};
 // CLIP vision layer, transformers 4.25.1 keys (CLIPVisionModel wraps the transformer as `.vision_model`):
 // HF:models/clip/modeling_clip.py (CLIPEncoderLayer: pre-LN, quick-GELU MLP)
-void add_clip_layer(ParamTable& b, int H, int I, int l, LayerOff& o) {
-    const std::string p = "dual_encoder.vision_model.vision_model.encoder.layers." + std::to_string(l) + ".";
-    const int g = MMHIP_G_FROZEN;
-    o.begin = b.off[0];
-    o.qkv_w = b.add(p + "self_attn.q_proj.weight", 0, g, {H, H});
-    b.add(p + "self_attn.k_proj.weight", 0, g, {H, H});
-    b.add(p + "self_attn.v_proj.weight", 0, g, {H, H});
-    o.qkv_b = b.add(p + "self_attn.q_proj.bias", 0, g, {H});
-    b.add(p + "self_attn.k_proj.bias", 0, g, {H});
-    b.add(p + "self_attn.v_proj.bias", 0, g, {H});
-    o.ao_w = b.add(p + "self_attn.out_proj.weight", 0, g, {H, H});
-    o.ao_b = b.add(p + "self_attn.out_proj.bias", 0, g, {H});
-    o.ln1_w = b.add(p + "layer_norm1.weight", 0, g, {H});
-    o.ln1_b = b.add(p + "layer_norm1.bias", 0, g, {H});
-    o.fc1_w = b.add(p + "mlp.fc1.weight", 0, g, {I, H});
-    o.fc1_b = b.add(p + "mlp.fc1.bias", 0, g, {I});
-    o.fc2_w = b.add(p + "mlp.fc2.weight", 0, g, {H, I});
-    o.fc2_b = b.add(p + "mlp.fc2.bias", 0, g, {H});
-    o.ln2_w = b.add(p + "layer_norm2.weight", 0, g, {H});
-    o.ln2_b = b.add(p + "layer_norm2.bias", 0, g, {H});
-    o.end = b.off[0];
-}
-// HF ViTLayer under `prefix` (the frozen tower of the dual encoder; the trainable one of the image-only model) in buffer `buf`, group `g`
-void add_vit_layer(ParamTable& b, const std::string& prefix, int buf, int g, int H, int I, int l, LayerOff& o) {
-    const std::string p = prefix + "encoder.layer." + std::to_string(l) + ".";
+const LayerKeys CLIP_LAYER = {"encoder.layers.", {
+    {"self_attn.q_proj.weight", &LayerOff::qkv_w, Shape::HH}, {"self_attn.k_proj.weight", nullptr, Shape::HH},
+    {"self_attn.v_proj.weight", nullptr, Shape::HH}, {"self_attn.q_proj.bias", &LayerOff::qkv_b, Shape::H},
+    {"self_attn.k_proj.bias", nullptr, Shape::H}, {"self_attn.v_proj.bias", nullptr, Shape::H},
+    {"self_attn.out_proj.weight", &LayerOff::ao_w, Shape::HH}, {"self_attn.out_proj.bias", &LayerOff::ao_b, Shape::H},
+    {"layer_norm1.weight", &LayerOff::ln1_w, Shape::H}, {"layer_norm1.bias", &LayerOff::ln1_b, Shape::H},
+    {"mlp.fc1.weight", &LayerOff::fc1_w, Shape::IH}, {"mlp.fc1.bias", &LayerOff::fc1_b, Shape::I},
+    {"mlp.fc2.weight", &LayerOff::fc2_w, Shape::HI}, {"mlp.fc2.bias", &LayerOff::fc2_b, Shape::H},
+    {"layer_norm2.weight", &LayerOff::ln2_w, Shape::H}, {"layer_norm2.bias", &LayerOff::ln2_b, Shape::H}}};
+// HF ViTLayer (the frozen tower of the dual encoder; the trainable one of the image-only model): its two LayerNorms come last
+const LayerKeys VIT_LAYER = {"encoder.layer.", {
+    {"attention.attention.query.weight", &LayerOff::qkv_w, Shape::HH}, {"attention.attention.key.weight", nullptr, Shape::HH},
+    {"attention.attention.value.weight", nullptr, Shape::HH}, {"attention.attention.query.bias", &LayerOff::qkv_b, Shape::H},
+    {"attention.attention.key.bias", nullptr, Shape::H}, {"attention.attention.value.bias", nullptr, Shape::H},
+    {"attention.output.dense.weight", &LayerOff::ao_w, Shape::HH}, {"attention.output.dense.bias", &LayerOff::ao_b, Shape::H},
+    {"intermediate.dense.weight", &LayerOff::fc1_w, Shape::IH}, {"intermediate.dense.bias", &LayerOff::fc1_b, Shape::I},
+    {"output.dense.weight", &LayerOff::fc2_w, Shape::HI}, {"output.dense.bias", &LayerOff::fc2_b, Shape::H},
+    {"layernorm_before.weight", &LayerOff::ln1_w, Shape::H}, {"layernorm_before.bias", &LayerOff::ln1_b, Shape::H},
+    {"layernorm_after.weight", &LayerOff::ln2_w, Shape::H}, {"layernorm_after.bias", &LayerOff::ln2_b, Shape::H}}};
+// layer l of a tower under `prefix`, in buffer `buf` and group `g`
+void add_layer(ParamTable& b, const LayerKeys& keys, const std::string& prefix, int l, int buf, int g, int H, int I, LayerOff& o) {
+    const std::string p = prefix + keys.stem + std::to_string(l) + ".";
     o.begin = b.off[buf];
-    o.qkv_w = b.add(p + "attention.attention.query.weight", buf, g, {H, H});
-    b.add(p + "attention.attention.key.weight", buf, g, {H, H});
-    b.add(p + "attention.attention.value.weight", buf, g, {H, H});
-    o.qkv_b = b.add(p + "attention.attention.query.bias", buf, g, {H});
-    b.add(p + "attention.attention.key.bias", buf, g, {H});
-    b.add(p + "attention.attention.value.bias", buf, g, {H});
-    o.ao_w = b.add(p + "attention.output.dense.weight", buf, g, {H, H});
-    o.ao_b = b.add(p + "attention.output.dense.bias", buf, g, {H});
-    o.fc1_w = b.add(p + "intermediate.dense.weight", buf, g, {I, H});
-    o.fc1_b = b.add(p + "intermediate.dense.bias", buf, g, {I});
-    o.fc2_w = b.add(p + "output.dense.weight", buf, g, {H, I});
-    o.fc2_b = b.add(p + "output.dense.bias", buf, g, {H});
-    o.ln1_w = b.add(p + "layernorm_before.weight", buf, g, {H});
-    o.ln1_b = b.add(p + "layernorm_before.bias", buf, g, {H});
-    o.ln2_w = b.add(p + "layernorm_after.weight", buf, g, {H});
-    o.ln2_b = b.add(p + "layernorm_after.bias", buf, g, {H});
+    for (const LayerKey& k : keys.rows) {
+        size_t at = 0;
+        switch (k.shape) {
+            case Shape::HH: at = b.add(p + k.suffix, buf, g, {H, H}); break;
+            case Shape::H: at = b.add(p + k.suffix, buf, g, {H}); break;
+            case Shape::IH: at = b.add(p + k.suffix, buf, g, {I, H}); break;
+            case Shape::I: at = b.add(p + k.suffix, buf, g, {I}); break;
+            case Shape::HI: at = b.add(p + k.suffix, buf, g, {H, I}); break;
+        }
+        if (k.slot) o.*k.slot = at;
+    }
     o.end = b.off[buf];
 }
 
@@ -240,7 +228,7 @@ void add_text_layers_and_embeddings(mmhip_engine& e, ParamTable& b) {
     const mmhip_config& c = e.cfg;
     const int H = c.hidden;
     e.txt.resize(c.layers_txt);
-    for (int l = c.layers_txt - 1; l >= 0; --l) add_text_layer(b, c, e.tm_prefix, l, e.txt[l]);
+    for (int l = c.layers_txt - 1; l >= 0; --l) add_layer(b, BERT_LAYER, e.tm_prefix, l, 1, MMHIP_G_ALWAYS, H, c.inter, e.txt[l]);
     const std::string tm = e.tm_prefix + "embeddings.";
     e.emb_begin = b.off[1];
     e.t_eln_w = b.add(tm + "LayerNorm.weight", 1, MMHIP_G_ALWAYS, {H});
@@ -267,7 +255,7 @@ void build_layout(mmhip_engine& e) {
         e.v_pos = b.add(vm + "embeddings.position_embedding.weight", 0, MMHIP_G_FROZEN, {P, Hv});
         e.v_pre_ln_w = b.add(vm + "pre_layrnorm.weight", 0, MMHIP_G_FROZEN, {Hv});
         e.v_pre_ln_b = b.add(vm + "pre_layrnorm.bias", 0, MMHIP_G_FROZEN, {Hv});
-        for (int l = 0; l < c.layers_img; ++l) add_clip_layer(b, Hv, e.Iv(), l, e.vit[l]);
+        for (int l = 0; l < c.layers_img; ++l) add_layer(b, CLIP_LAYER, vm, l, 0, MMHIP_G_FROZEN, Hv, e.Iv(), e.vit[l]);
         e.v_ln_w = b.add(vm + "post_layernorm.weight", 0, MMHIP_G_FROZEN, {Hv});
         e.v_ln_b = b.add(vm + "post_layernorm.bias", 0, MMHIP_G_FROZEN, {Hv});
         e.v_pool_w = e.v_pool_b = 0;
@@ -277,7 +265,7 @@ void build_layout(mmhip_engine& e) {
         e.v_pos = b.add(vm + "embeddings.position_embeddings", 0, MMHIP_G_FROZEN, {1, P, Hv});
         e.v_patch_w = b.add(vm + "embeddings.patch_embeddings.projection.weight", 0, MMHIP_G_FROZEN, {Hv, 3, c.patch, c.patch});
         e.v_patch_b = b.add(vm + "embeddings.patch_embeddings.projection.bias", 0, MMHIP_G_FROZEN, {Hv});
-        for (int l = 0; l < c.layers_img; ++l) add_vit_layer(b, vm, 0, MMHIP_G_FROZEN, Hv, e.Iv(), l, e.vit[l]);
+        for (int l = 0; l < c.layers_img; ++l) add_layer(b, VIT_LAYER, vm, l, 0, MMHIP_G_FROZEN, Hv, e.Iv(), e.vit[l]);
         e.v_ln_w = b.add(vm + "layernorm.weight", 0, MMHIP_G_FROZEN, {Hv});
         e.v_ln_b = b.add(vm + "layernorm.bias", 0, MMHIP_G_FROZEN, {Hv});
         e.v_pool_w = b.add(vm + "pooler.dense.weight", 0, MMHIP_G_FROZEN, {Hv, Hv});
@@ -359,7 +347,7 @@ void build_layout_img(mmhip_engine& e) {
     e.v_ln_b = b.add("vit.layernorm.bias", 1, g, {H});
     e.heads_end = b.off[1];
     e.vit.resize(c.layers_img);
-    for (int l = c.layers_img - 1; l >= 0; --l) add_vit_layer(b, "vit.", 1, g, H, e.Iv(), l, e.vit[l]);
+    for (int l = c.layers_img - 1; l >= 0; --l) add_layer(b, VIT_LAYER, "vit.", l, 1, g, H, e.Iv(), e.vit[l]);
     e.emb_begin = b.off[1];
     e.v_patch_w = b.add("vit.embeddings.patch_embeddings.projection.weight", 1, g, {H, 3, c.patch, c.patch});
     e.v_patch_b = b.add("vit.embeddings.patch_embeddings.projection.bias", 1, g, {H});
@@ -371,17 +359,37 @@ void build_layout_img(mmhip_engine& e) {
     e.n_train = b.off[1];
 }
 
+// ------------------------------------------------------------------------------------------------ workspace sizing shared by every handle kind
+// 16-bit (parity mode: Z = 4) GEMM operand copies of n layers of a tower, H wide with an I-wide MLP; transposed: the copies the backward reads too
+void carve_w16(Carver& w, std::vector<LayerW16>& v, int n, bool transposed, size_t H, size_t I, size_t Z) {
+    v.resize(n);
+    for (auto& L : v) {
+        L.qkv = w.take(3 * H * H * Z); L.ao = w.take(H * H * Z); L.fc1 = w.take(I * H * Z); L.fc2 = w.take(H * I * Z);
+        if (transposed) { L.qkvT = w.take(3 * H * H * Z); L.aoT = w.take(H * H * Z); L.fc1T = w.take(I * H * Z); L.fc2T = w.take(H * I * Z); }
+    }
+}
+// fp32 scratch of the split-K path of the <= 128-row GEMMs of a tower: what run_gemm may hand to launch_nt_splitk
+size_t splitk_floats(size_t H, size_t I) { return (size_t)(I / 384 + 1) * 128 * (size_t)(I > 3 * H ? I : 3 * H); }
+// parity mode without plane pairs: split planes of the operands of one GEMM call at a time per stream (x3.hip) -- the widest NT problem of a
+// tower's layer over M rows, and the four weight-gradient problems of a layer together
+size_t x3_nt_bytes(size_t M, size_t H, size_t I) {
+    size_t b = 0;
+    const size_t nk[5][2] = {{3 * H, H}, {H, H}, {I, H}, {H, I}, {H, 3 * H}};
+    for (auto& q : nk) { const size_t v = x3_nt_scratch_bytes((int)M, (int)q[0], (int)q[1]); if (v > b) b = v; }
+    return b;
+}
+size_t x3_tn_bytes(size_t M, size_t H, size_t I) {
+    return x3_tn_scratch_bytes((int)M, (int)H, (int)I) + x3_tn_scratch_bytes((int)M, (int)I, (int)H) + x3_tn_scratch_bytes((int)M, (int)(3 * H), (int)H) +
+           x3_tn_scratch_bytes((int)M, (int)H, (int)H);
+}
+
 // the image tower's share alone: operand copies with transposes, the activations a pre-LN backward needs, its gradient temporaries, the head's words
 void build_workspace_img(mmhip_engine& e) {
     const mmhip_config& c = e.cfg;
     const size_t H = e.Hv(), I = e.Iv(), C = c.num_labels, Bm = c.max_posts, P = e.P(), Kpp = e.Kpp(), Z = e.esz();
     const size_t Mv = mmhip_engine::pad64(Bm * P), Mp = mmhip_engine::pad64(Bm * (P - 1));      // rows of every token / patch tensor: padded (i_pad_B)
     Carver w;
-    e.vit_w16.resize(c.layers_img);
-    for (auto& L : e.vit_w16) {
-        L.qkv = w.take(3 * H * H * Z); L.ao = w.take(H * H * Z); L.fc1 = w.take(I * H * Z); L.fc2 = w.take(H * I * Z);
-        L.qkvT = w.take(3 * H * H * Z); L.aoT = w.take(H * H * Z); L.fc1T = w.take(I * H * Z); L.fc2T = w.take(H * I * Z);
-    }
+    carve_w16(w, e.vit_w16, c.layers_img, true, H, I, Z);
     e.patch_w16 = w.take(H * Kpp * Z);
     e.v_patches = w.take(Mp * Kpp * Z); e.v_pe = w.take(Mp * H * Z);
     e.iact.resize(c.layers_img);
@@ -409,18 +417,13 @@ void build_workspace_img(mmhip_engine& e) {
     e.i_epartial = w.take(partial_floats_vit_embed((int)Bm, (int)P, (int)H) * 4);
     auto f = [&](size_t n) { return w.take(n * 4); };
     e.h_out_cls = f(Bm * C); e.h_d_out_cls = f(Bm * C); e.h_loss = f(8);
-    e.splitk_ws = f((size_t)(I / 384 + 1) * 128 * (size_t)(I > 3 * H ? I : 3 * H)); e.has_splitk = true;
+    e.splitk_ws = f(splitk_floats(H, I)); e.has_splitk = true;
     if (c.dtype == MMHIP_BF16X3 && !e.px) {
         // parity mode without plane pairs: split planes of one GEMM call at a time per stream -- the widest NT problem (the patch GEMM included),
         // the four weight-gradient problems of a layer together, or the patch weight's
         size_t b = x3_nt_scratch_bytes((int)Mp, (int)H, (int)Kpp);
-        const size_t nk[5][2] = {{3 * H, H}, {H, H}, {I, H}, {H, I}, {H, 3 * H}};
-        for (auto& q : nk) { const size_t v = x3_nt_scratch_bytes((int)Mv, (int)q[0], (int)q[1]); if (v > b) b = v; }
-        const size_t tn = x3_tn_scratch_bytes((int)Mv, (int)H, (int)I) + x3_tn_scratch_bytes((int)Mv, (int)I, (int)H) + x3_tn_scratch_bytes((int)Mv, (int)(3 * H), (int)H) +
-                          x3_tn_scratch_bytes((int)Mv, (int)H, (int)H);
-        if (tn > b) b = tn;
-        const size_t tp = x3_tn_scratch_bytes((int)Mp, (int)H, (int)Kpp);
-        if (tp > b) b = tp;
+        for (const size_t v : {x3_nt_bytes(Mv, H, I), x3_tn_bytes(Mv, H, I), x3_tn_scratch_bytes((int)Mp, (int)H, (int)Kpp)})
+            if (v > b) b = v;
         e.x3_bytes[0] = e.x3_bytes[1] = b; e.x3_bytes[2] = 0;
         for (int i = 0; i < 2; ++i) e.x3_ws[i] = w.take(b);
     }
@@ -431,19 +434,12 @@ void build_workspace(mmhip_engine& e) {
     const mmhip_config& c = e.cfg;
     const size_t H = c.hidden, I = c.inter, E = c.proj_dim, C = c.num_labels;
     const size_t Bm = c.max_posts, Tm = c.max_text_len, P = e.P(), Hv = e.Hv(), Iv = e.Iv(), Kpp = e.Kpp();
-    const bool mm = !e.txt_only;      // a text-only handle carves the text tower's share alone, for B (not 2 B: no ITM posts) rows of posts
+    const bool mm = e.is_late();      // a text-only handle carves the text tower's share alone, for B (not 2 B: no ITM posts) rows of posts
     const size_t Bt = (mm ? 2 : 1) * Bm, Mt = Bt * Tm, Mv = Bm * P;
     const size_t Z = e.esz();      // bytes per activation / GEMM-operand element: 2 (bf16, f16) or 4 (bf16x3 parity mode)
     Carver w;
-    auto w16 = [&](std::vector<LayerW16>& v, int n, bool transposed, size_t H, size_t I) {
-        v.resize(n);
-        for (auto& L : v) {
-            L.qkv = w.take(3 * H * H * Z); L.ao = w.take(H * H * Z); L.fc1 = w.take(I * H * Z); L.fc2 = w.take(H * I * Z);
-            if (transposed) { L.qkvT = w.take(3 * H * H * Z); L.aoT = w.take(H * H * Z); L.fc1T = w.take(I * H * Z); L.fc2T = w.take(H * I * Z); }
-        }
-    };
-    w16(e.vit_w16, mm ? c.layers_img : 0, false, Hv, Iv);
-    w16(e.txt_w16, c.layers_txt, true, H, I);
+    carve_w16(w, e.vit_w16, mm ? c.layers_img : 0, false, Hv, Iv, Z);
+    carve_w16(w, e.txt_w16, c.layers_txt, true, H, I, Z);
     if (mm) e.patch_w16 = w.take(Hv * Kpp * Z);
     else e.tt_all = w.take(Bt * Tm * 8);
     e.ids_all = w.take(Bt * Tm * 8); e.mask_all = w.take(Bt * Tm * 8); e.pos_ids = w.take(Bt * Tm * 4); e.maskbias = w.take(Bt * Tm * 4);
@@ -480,20 +476,9 @@ void build_workspace(mmhip_engine& e) {
             for (int j = 0; j < 2; ++j) e.g_lnp[i][j] = w.take(partial_floats_rows((int)Mt, (int)H, 2) * 4);
     }
     auto f = [&](size_t n) { return w.take(n * 4); };
-    // sizing shared by both handle kinds.  Split-K scratch of the <= 128-row GEMMs of a tower; parity mode without plane pairs: split planes of the
-    // operands of one GEMM call at a time per stream (x3.hip) -- the widest NT problem of a tower, or the four weight-gradient problems of a
-    // text layer together
-    auto splitk_floats = [](size_t H, size_t I) { return (size_t)(I / 384 + 1) * 128 * (size_t)(I > 3 * H ? I : 3 * H); };
-    auto x3_nt = [](size_t M, size_t H, size_t I) {
-        size_t b = 0;
-        const size_t nk[5][2] = {{3 * H, H}, {H, H}, {I, H}, {H, I}, {H, 3 * H}};
-        for (auto& q : nk) { const size_t v = x3_nt_scratch_bytes((int)M, (int)q[0], (int)q[1]); if (v > b) b = v; }
-        return b;
-    };
+    // the text tower's split-plane scratch: its widest NT problem, or the four weight-gradient problems of a layer together
     auto x3_txt = [&]() {
-        const size_t tn = x3_tn_scratch_bytes((int)Mt, (int)H, (int)I) + x3_tn_scratch_bytes((int)Mt, (int)I, (int)H) + x3_tn_scratch_bytes((int)Mt, (int)(3 * H), (int)H) +
-                          x3_tn_scratch_bytes((int)Mt, (int)H, (int)H);
-        const size_t nt = x3_nt(Mt, H, I);
+        const size_t tn = x3_tn_bytes(Mt, H, I), nt = x3_nt_bytes(Mt, H, I);
         return tn > nt ? tn : nt;
     };
     const bool x3_split = c.dtype == MMHIP_BF16X3 && !e.px;
@@ -514,7 +499,7 @@ void build_workspace(mmhip_engine& e) {
     e.splitk_ws = f(splitk_floats(H, I)); e.has_splitk = true;
     e.splitk_ws_vit = f(splitk_floats(Hv, Iv));
     if (x3_split) {
-        size_t vit = x3_nt(Mv, Hv, Iv);
+        size_t vit = x3_nt_bytes(Mv, Hv, Iv);
         { const size_t pe = x3_nt_scratch_bytes((int)(Bm * (P - 1)), (int)Hv, (int)Kpp); if (pe > vit) vit = pe; }
         const size_t txt = x3_txt();
         e.x3_bytes[0] = txt > vit ? txt : vit; e.x3_bytes[1] = txt; e.x3_bytes[2] = vit;
@@ -537,18 +522,26 @@ inline void part_gemm(const mmhip_engine& e, G& g, int which) {
     const int n = e.cur_part[which];
     if (n > 0 && !g.a.tile && g.a.M >= 2048 && g.a.N % 256 == 0 && g.a.K % 64 == 0 && (e.dt() == DT_BF16 || e.dt() == DT_F16)) g.tile(15).grid(n);
 }
+inline bool on_vit_stream(const mmhip_engine& e, hipStream_t s) { return e.side_vit[0] != nullptr && (s == e.side_vit[0] || s == e.side_vit[1]); }
+// parity mode without plane pairs: the split-plane scratch of the stream a GEMM launch goes to -- the image tower's, the side stream's (only when the
+// launch really is on it), else the caller's; {nullptr, 0} in every other mode
+struct X3Scratch { char* ws; size_t bytes; };
+inline X3Scratch x3_scratch(const mmhip_engine& e, hipStream_t s) {
+    const int i = on_vit_stream(e, s) ? 2 : (e.side && s == e.side ? 1 : 0);
+    return X3Scratch{e.x3_bytes[i] ? e.ws + e.x3_ws[i] : nullptr, e.x3_bytes[i]};
+}
 int run_gemm(mmhip_engine& e, G& g, hipStream_t s) {
     // GEMMs of <= 128 rows with K >= 1536 (the CLS-row GEMMs of the last text layer; a tiny image tower) are split along K
     // (gemm.hip launch_nt_splitk) through an fp32 scratch: the image tower's side stream has its own, every other stream shares the caller's
     {
-        const bool on_vit = e.side_vit[0] != nullptr && (s == e.side_vit[0] || s == e.side_vit[1]);
-        const int h = on_vit ? e.Hv() : e.cfg.hidden, in = on_vit ? e.Iv() : e.cfg.inter;
-        if (e.has_splitk && g.a.M <= 128 && (size_t)(g.a.K / 384) * g.a.M * g.a.N <= (size_t)(in / 384 + 1) * 128 * (size_t)(in > 3 * h ? in : 3 * h))
+        const bool on_vit = on_vit_stream(e, s);
+        const size_t bound = on_vit ? splitk_floats(e.Hv(), e.Iv()) : splitk_floats(e.cfg.hidden, e.cfg.inter);
+        if (e.has_splitk && g.a.M <= 128 && (size_t)(g.a.K / 384) * g.a.M * g.a.N <= bound)
             g.a.splitk_ws = e.wsp<float>(on_vit ? e.splitk_ws_vit : e.splitk_ws);
         if (e.x3_bytes[0]) {
-            const int i = on_vit ? 2 : (e.side && s == e.side ? 1 : 0);
-            g.a.x3_ws = e.ws + e.x3_ws[i];
-            g.a.x3_ws_bytes = e.x3_bytes[i];
+            const X3Scratch x = x3_scratch(e, s);
+            g.a.x3_ws = x.ws;
+            g.a.x3_ws_bytes = x.bytes;
         }
     }
     if (e.timing) {
@@ -622,6 +615,11 @@ int refresh_layer(mmhip_engine& e, const float* base, const LayerOff& o, const L
                     {base + o.fc1_w, e.ws + w.fc1, transposed ? e.ws + w.fc1T : nullptr, I, H, 0},
                     {base + o.fc2_w, e.ws + w.fc2, transposed ? e.ws + w.fc2T : nullptr, H, I, 0}};
     CHECK_HIP(launch_cast_group(m, 4, e.px ? DT_PAIR : e.dt(), s));
+    return 0;
+}
+// patch-embedding weight [Hv, 3*p*p] of the tower whose parameters live in `base`, rows zero-padded to the GEMM's k-step (14 x 14 patches: 588 -> 640)
+int refresh_patch(mmhip_engine& e, const float* base, hipStream_t s) {
+    CHECK_HIP(launch_cast_pad(base + e.v_patch_w, e.ws + e.patch_w16, e.Hv(), e.Kp(), e.Kpp(), e.px ? DT_PAIR : e.dt(), s));
     return 0;
 }
 
@@ -706,8 +704,8 @@ struct TextLayer {
 int vit_embed(mmhip_engine& e, const float* pixels, hipStream_t s) {
     const mmhip_config& c = e.cfg;
     const int H = e.Hv(), B = e.B, P = e.P(), Kpp = e.Kpp(), dt = e.dt();
-    const float* F = e.img_only ? e.train : e.frozen;
-    char* x0 = e.ws + (!e.img_only ? e.v_x : (c.layers_img ? e.iact[0].x_in : e.i_xfin));
+    const float* F = e.is_image() ? e.train : e.frozen;
+    char* x0 = e.ws + (!e.is_image() ? e.v_x : (c.layers_img ? e.iact[0].x_in : e.i_xfin));
     CHECK_HIP(launch_patchify(pixels, e.ws + e.v_patches, B, c.image, c.patch, Kpp, e.px ? DT_PAIR : dt, s));
     G g(e.ws + e.v_patches, Kpp, e.ws + e.patch_w16, Kpp, e.ws + e.v_pe, H, B * (P - 1), H, Kpp);
     if (!e.clip()) g.bias(F + e.v_patch_b);           // CLIP's patch conv has no bias
@@ -801,10 +799,11 @@ int vit_close(mmhip_engine& e, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------------ the towers' forward: orderings of the pieces
-int vit_forward(mmhip_engine& e, const float* pixels, hipStream_t s) {
+// embeddings and every image layer in order; saved: each layer on its own buffer set (the trainable tower), else all on the shared one
+int image_layers_forward(mmhip_engine& e, const float* pixels, bool saved, hipStream_t s) {
     CHECK_RC(vit_embed(e, pixels, s));
     for (int l = 0; l < e.cfg.layers_img; ++l) {
-        const ImageLayer v(e, l);
+        const ImageLayer v(e, l, saved ? image_bufs_saved(e, l) : image_bufs_shared(e));
         CHECK_RC(v.ln1(s));
         CHECK_RC(run_gemm(e, v.qkv(), s));
         CHECK_RC(v.attention(s));
@@ -813,6 +812,11 @@ int vit_forward(mmhip_engine& e, const float* pixels, hipStream_t s) {
         CHECK_RC(run_gemm(e, v.fc1(), s));
         CHECK_RC(run_gemm(e, v.fc2(), s));
     }
+    return 0;
+}
+// the frozen tower of the late-fusion model
+int vit_forward(mmhip_engine& e, const float* pixels, hipStream_t s) {
+    CHECK_RC(image_layers_forward(e, pixels, false, s));
     return vit_close(e, s);
 }
 
@@ -1052,6 +1056,11 @@ int heads_backward(mmhip_engine& e, hipStream_t s) {
             CHECK_HIP(hipMemsetAsync(dfeats + (size_t)B * H, 0, (size_t)B * H * 4, s));
         }
     }
+    // every fusion ends here -- gradient of the last hidden state: CLS rows only (compact [Bt, H] when the last layer ran on CLS rows)
+    auto scatter_dxcls = [&]() -> int {
+        CHECK_HIP(launch_scatter_cls_rows(dxcls, e.ws + e.g_dx, Bt, e.cls_compact ? 1 : T, H, dt, s, e.gscale()));
+        return 0;
+    };
     if (e.aspect()) {
         // feats = relu(sum_j w_j V_j) over the stacked pooler outputs: ITC's gradient of t_pool first (a plain write), the fusion's added to it by the
         // rows' one writer; then the text pooler's backward, which OPENS dxcls here (nothing else reaches the CLS rows under this fusion)
@@ -1063,8 +1072,7 @@ int heads_backward(mmhip_engine& e, hipStream_t s) {
         ab.partial = e.wsp<float>(e.h_asp_partial); ab.accumulate = itc; ab.accumulate_dw = 1;
         CHECK_HIP(launch_aspect_fusion_bwd(ab, s));
         CHECK_RC(text_pooler_backward(e, 0, s));
-        CHECK_HIP(launch_scatter_cls_rows(dxcls, e.ws + e.g_dx, Bt, e.cls_compact ? 1 : T, H, dt, s, e.gscale()));
-        return 0;
+        return scatter_dxcls();
     }
     // feats = relu(linear_fusion(z))
     float* dpre = e.wsp<float>(e.h_dpre);
@@ -1094,22 +1102,18 @@ int heads_backward(mmhip_engine& e, hipStream_t s) {
         CHECK_RC(itc_backward_to_tpool(e, s));
         CHECK_RC(text_pooler_backward(e, 1, s));
     }
-    // gradient of the last hidden state: CLS rows only
-    // gradient of the last hidden state: CLS rows only (compact [Bt, H] when the last layer ran on CLS rows)
-    CHECK_HIP(launch_scatter_cls_rows(dxcls, e.ws + e.g_dx, Bt, e.cls_compact ? 1 : T, H, dt, s, e.gscale()));
-    return 0;
+    return scatter_dxcls();
 }
 
-// ---- text-only handle: the fused CLS classifier head (heads.hip), one launch per direction
+// ---- one-tower handles: the fused CLS classifier head (heads.hip), one launch per direction.  txt_head_args / img_head_args: where each kind's CLS rows are
 ClsHeadArgs txt_head_args(const mmhip_engine& e) {
     const mmhip_config& c = e.cfg;
     // parity mode keeps the fp32 form of the last hidden state beside its plane pair: the head reads that
     return cls_head(text_last(e), e.cls_compact ? (size_t)c.hidden : (size_t)e.T * c.hidden, e.dt(), e.train + e.lin_w, e.B, c.num_labels, c.hidden,
                     make_drop(c.p_head, e.seed, STREAM_HEAD, e.train_mode));
 }
-// logits (and, with labels, loss / correct count / d logits kept in the handle for the backward)
-int txt_head_forward(mmhip_engine& e, const int64_t* onehot, const float* class_w, float* logits, float* loss, int* n_correct, hipStream_t s) {
-    ClsHeadArgs a = txt_head_args(e);
+// logits of the head over the rows `a` names (and, with labels, loss / correct count / d logits kept in the handle for the backward)
+int cls_head_forward(mmhip_engine& e, ClsHeadArgs a, const int64_t* onehot, const float* class_w, float* logits, float* loss, int* n_correct, hipStream_t s) {
     a.bias = e.train + e.lin_b; a.logits = e.wsp<float>(e.h_out_cls);
     if (onehot) {
         a.onehot = onehot; a.class_w = class_w; a.loss = e.wsp<float>(e.h_loss); a.n_correct = n_correct; a.d_logits_out = e.wsp<float>(e.h_d_out_cls);
@@ -1133,6 +1137,42 @@ int txt_head_backward(mmhip_engine& e, hipStream_t s) {
     a.dx = e.wsp<float>(e.h_dxcls); a.dx_stride = H; a.dx_dtype = DT_F32; a.dx_scale = 1.f;
     CHECK_HIP(launch_cls_head_bwd(a, s));
     CHECK_HIP(launch_scatter_cls_rows(e.wsp<float>(e.h_dxcls), e.ws + e.g_dx, e.Bt, e.T, H, e.dt(), s, e.gscale()));
+    return 0;
+}
+
+// ---- the weight-gradient tail of a layer's backward, the same under both towers.  The temporaries the weight-gradient GEMMs read are double-buffered
+// per layer parity (`set`), so the side stream may still be consuming layer l's set while the caller's stream runs layer l - 1 on the other one.
+// join_set: `s` waits for the side work that last read `set` (layer l + 2's; at the end of a backward: every gradient final in the caller's order)
+int join_set(mmhip_engine& e, int set, hipStream_t s) {
+    if (e.tn_pending[set]) {
+        CHECK_HIP(hipStreamWaitEvent(s, e.ev_tn[set], 0));
+        e.tn_pending[set] = false;
+    }
+    return 0;
+}
+// everything the layer's parameter gradients read has been enqueued on `s`: ps = the stream they go to -- the side stream, made to wait for this
+// point of `s`, or `s` itself with the side stream off
+int fork_param_grads(mmhip_engine& e, int set, hipStream_t s, hipStream_t& ps) {
+    ps = s;
+    if (use_side(e)) {
+        CHECK_HIP(hipEventRecord(e.ev_ready[set], s));
+        CHECK_HIP(hipStreamWaitEvent(e.side, e.ev_ready[set], 0));
+        ps = e.side;
+    }
+    return 0;
+}
+// parameter gradients of the layer on ps, off the dX chain: the second stage of the two LayerNorm reductions, then all four weight gradients AND
+// their bias gradients (column sums of the dY operand, from the same tiles) in one grouped launch, no split-K, plain stores
+int layer_param_grads(mmhip_engine& e, int set, hipStream_t ps, const LNBwdArgs& b2, const LNBwdArgs& b1, GemmTNProblem (&pr)[4]) {
+    CHECK_HIP(launch_layernorm_bwd_reduce(b2, ps));
+    CHECK_HIP(launch_layernorm_bwd_reduce(b1, ps));
+    if (e.px) for (auto& q : pr) tn_pair(q, e.bwd_np);
+    const X3Scratch x = x3_scratch(e, ps);
+    CHECK_HIP(launch_gemm_tn(pr, 4, 0, e.dt(), 0, ps, 1.0f / e.gscale(), x.ws, x.bytes));
+    if (e.side && ps == e.side) {
+        CHECK_HIP(hipEventRecord(e.ev_tn[set], e.side));
+        e.tn_pending[set] = true;
+    }
     return 0;
 }
 
@@ -1160,10 +1200,7 @@ int text_layer_backward(mmhip_engine& e, int l, hipStream_t s) {
     char *dx = e.ws + e.g_dx, *dx2 = e.ws + e.g_dx2, *dctx = e.ws + e.g_dctx;
     char *dpre2 = e.ws + e.g_set[set][0], *ddrop2 = e.ws + e.g_set[set][1], *du = e.ws + e.g_set[set][2];
     char *dpre1 = e.ws + e.g_set[set][3], *ddrop1 = e.ws + e.g_set[set][4], *dqkv = e.ws + e.g_set[set][5];
-    if (side && e.tn_pending[set]) {           // the set was last read by layer l+2's side work
-        CHECK_HIP(hipStreamWaitEvent(s, e.ev_tn[set], 0));
-        e.tn_pending[set] = false;
-    }
+    CHECK_RC(join_set(e, set, s));           // the set was last read by layer l+2's side work
     // ---- x' = LN2(pre2), pre2 = drop(fc2(h)) + a1.  LN backward also emits the dropout-backward copy and the bias
     // gradient of the Linear that fed the LN
     const DropCfg d_ffn = make_drop(c.p_hidden, e.seed, stream_ffn_out(l), tr);
@@ -1214,14 +1251,9 @@ int text_layer_backward(mmhip_engine& e, int l, hipStream_t s) {
     attn_pair(ab, px, np);
     ab.q_tiles = compact ? 1 : 0;
     CHECK_HIP(launch_attn_bwd(ab, dt, s));
-    // ---- parameter gradients of the layer: off the critical path -> side stream: all four weight gradients AND their bias
-    // gradients in one grouped launch, no split-K, plain stores
-    hipStream_t ps = s;
-    if (side) {
-        CHECK_HIP(hipEventRecord(e.ev_ready[set], s));
-        CHECK_HIP(hipStreamWaitEvent(e.side, e.ev_ready[set], 0));
-        ps = e.side;
-    }
+    // ---- parameter gradients of the layer: off the critical path -> side stream, forked BEFORE the last dX GEMM (which they do not read)
+    hipStream_t ps;
+    CHECK_RC(fork_param_grads(e, set, s, ps));
     if (compact) {
         // dx_in = dqkv . Wqkv, plus d pre1 on the CLS rows (the residual branch of the CLS rows)
         { G g(dqkv, 3 * H, e.ws + w.qkvT, 3 * H, dx, H, Mt, H, 3 * H); g.px_in(px, np); CHECK_RC(run_gemm(e, g, s)); }
@@ -1233,36 +1265,17 @@ int text_layer_backward(mmhip_engine& e, int l, hipStream_t s) {
         part_bwd(g, 8);
         CHECK_RC(run_gemm(e, g, s));
     }
-    GemmTNProblem pr[4];
-    CHECK_HIP(launch_layernorm_bwd_reduce(b2, ps));
-    CHECK_HIP(launch_layernorm_bwd_reduce(b1, ps));
-    // each problem also yields its Linear's bias gradient (column sums of the dY operand) from the same tiles
-    pr[0] = GemmTNProblem{df, e.ws + a.h, Gd + o.fc2_w, Mr, H, I, H, I, I, 0, Gd + o.fc2_b};           // dW2[H,I]   = df^T h
-    pr[1] = GemmTNProblem{du, e.ws + a.a1, Gd + o.fc1_w, Mr, I, H, I, H, H, 0, Gd + o.fc1_b};          // dW1[I,H]   = du^T a1
-    pr[2] = GemmTNProblem{dqkv, x_in, Gd + o.qkv_w, Mt, 3 * H, H, 3 * H, H, H, 0, Gd + o.qkv_b};       // dWqkv[3H,H] = dqkv^T x_in
-    pr[3] = GemmTNProblem{dout, e.ws + a.ctx, Gd + o.ao_w, Mr, H, H, H, rs, H, 0, Gd + o.ao_b};        // dWo[H,H]   = dout^T ctx (CLS rows: stride T*H)
-    if (px) {
-        pr[1].B = e.ws + a.a1p;
-        for (auto& q : pr) tn_pair(q, np);
-    }
-    {
-        const int i = e.side && ps == e.side ? 1 : 0;
-        CHECK_HIP(launch_gemm_tn(pr, 4, 0, dt, 0, ps, 1.0f / e.gscale(), e.x3_bytes[i] ? e.ws + e.x3_ws[i] : nullptr, e.x3_bytes[i]));
-    }
-    if (side) {
-        CHECK_HIP(hipEventRecord(e.ev_tn[set], e.side));
-        e.tn_pending[set] = true;
-    }
-    return 0;
+    GemmTNProblem pr[4] = {
+        {df, e.ws + a.h, Gd + o.fc2_w, Mr, H, I, H, I, I, 0, Gd + o.fc2_b},                                  // dW2[H,I]   = df^T h
+        {du, e.ws + (px ? a.a1p : a.a1), Gd + o.fc1_w, Mr, I, H, I, H, H, 0, Gd + o.fc1_b},                  // dW1[I,H]   = du^T a1 (its plane pair)
+        {dqkv, x_in, Gd + o.qkv_w, Mt, 3 * H, H, 3 * H, H, H, 0, Gd + o.qkv_b},                              // dWqkv[3H,H] = dqkv^T x_in
+        {dout, e.ws + a.ctx, Gd + o.ao_w, Mr, H, H, H, rs, H, 0, Gd + o.ao_b}};                              // dWo[H,H]   = dout^T ctx (CLS rows: stride T*H)
+    return layer_param_grads(e, set, ps, b2, b1, pr);
 }
 
 // join the side stream: after this, every gradient is final in the caller's stream order
 int backward_finish(mmhip_engine& e, hipStream_t s) {
-    for (int set = 0; set < 2; ++set)
-        if (e.tn_pending[set]) {
-            CHECK_HIP(hipStreamWaitEvent(s, e.ev_tn[set], 0));
-            e.tn_pending[set] = false;
-        }
+    for (int set = 0; set < 2; ++set) CHECK_RC(join_set(e, set, s));
     return 0;
 }
 
@@ -1329,36 +1342,9 @@ int img_zero_pads(mmhip_engine& e, int B, hipStream_t s) {
     return 0;
 }
 
-// the tower on per-layer buffer sets (ImageLayer), the same launch order as vit_forward
-int img_tower_forward(mmhip_engine& e, const float* pixels, hipStream_t s) {
-    CHECK_RC(vit_embed(e, pixels, s));
-    for (int l = 0; l < e.cfg.layers_img; ++l) {
-        const ImageLayer v(e, l, image_bufs_saved(e, l));
-        CHECK_RC(v.ln1(s));
-        CHECK_RC(run_gemm(e, v.qkv(), s));
-        CHECK_RC(v.attention(s));
-        CHECK_RC(run_gemm(e, v.attn_out(), s));
-        CHECK_RC(v.ln2(s));
-        CHECK_RC(run_gemm(e, v.fc1(), s));
-        CHECK_RC(run_gemm(e, v.fc2(), s));
-    }
-    return 0;
-}
 // classifier(layernorm(x)[:, 0, :]): the B CLS rows gathered, the final LayerNorm on them alone (no other row of it is consumed), the fused head, p = 0
 ClsHeadArgs img_head_args(const mmhip_engine& e) {
     return cls_head(e.ws + e.i_clsln, (size_t)e.Hv(), e.dt(), e.train + e.lin_w, e.B, e.cfg.num_labels, e.Hv(), make_drop(0.f, 0, STREAM_HEAD, false));
-}
-int img_head_classify(mmhip_engine& e, const int64_t* onehot, const float* class_w, float* logits, float* loss, int* n_correct, hipStream_t s) {
-    ClsHeadArgs a = img_head_args(e);
-    a.bias = e.train + e.lin_b; a.logits = e.wsp<float>(e.h_out_cls);
-    if (onehot) {
-        a.onehot = onehot; a.class_w = class_w; a.loss = e.wsp<float>(e.h_loss); a.n_correct = n_correct; a.d_logits_out = e.wsp<float>(e.h_d_out_cls);
-    }
-    CHECK_HIP(launch_cls_head_fwd(a, s));
-    if (logits) CHECK_HIP(hipMemcpyAsync(logits, a.logits, (size_t)e.B * e.cfg.num_labels * 4, hipMemcpyDeviceToDevice, s));
-    if (onehot && loss) CHECK_HIP(hipMemcpyAsync(loss, a.loss, 4, hipMemcpyDeviceToDevice, s));
-    if (onehot) e.bd_out_cls = a.d_logits_out;
-    return 0;
 }
 int img_head_forward(mmhip_engine& e, const int64_t* onehot, const float* class_w, float* logits, float* loss, int* n_correct, hipStream_t s) {
     const int H = e.Hv(), B = e.B, P = e.P();
@@ -1366,7 +1352,7 @@ int img_head_forward(mmhip_engine& e, const int64_t* onehot, const float* class_
     CHECK_HIP(hipMemcpy2DAsync(e.ws + e.i_cls, rb, e.ws + e.i_xfin, (size_t)P * rb, rb, B, hipMemcpyDeviceToDevice, s));
     LNArgs n{e.ws + e.i_cls, e.ws + e.i_clsln, e.train + e.v_ln_w, e.train + e.v_ln_b, e.wsp<float>(e.i_mean), e.wsp<float>(e.i_rstd), B, H, H, H, e.cfg.ln_eps_img};
     CHECK_HIP(launch_layernorm_fwd(n, e.dt(), s));
-    return img_head_classify(e, onehot, class_w, logits, loss, n_correct, s);
+    return cls_head_forward(e, img_head_args(e), onehot, class_w, logits, loss, n_correct, s);
 }
 // stage 0: head, final LayerNorm on the B rows, and the gradient of the last stream: zero but for the CLS rows
 int img_head_backward(mmhip_engine& e, hipStream_t s) {
@@ -1404,17 +1390,13 @@ int image_layer_backward(mmhip_engine& e, int l, hipStream_t s) {
     const int np = e.bwd_np;
     const bool hi1 = px && np == 1;          // every reader takes one product: lo planes not written (d ctx excepted: the attention backward keeps three)
     const int set = l & 1;
-    const bool side = use_side(e);
     const int di = (l + 1) % 3, dn = l % 3;
     char *dx = e.ws + e.i_dxs[di], *dxg = px ? e.ws + e.i_dxs_p[di] : dx;                      // fp32 / 16-bit form, and as the GEMMs read it
     char *dxo = e.ws + e.i_dxs[dn], *dxo_p = e.ws + e.i_dxs_p[dn];
     char *du = e.ws + e.i_set[set][0], *dqkv = e.ws + e.i_set[set][1], *dxmid = e.ws + e.i_set[set][2];
     char *dxmid_g = px ? e.ws + e.i_set[set][3] : dxmid;
     char *dln = e.ws + e.i_dln, *dctx = e.ws + e.i_dctx;
-    if (side && e.tn_pending[set]) {           // the set was last read by layer l+2's side work
-        CHECK_HIP(hipStreamWaitEvent(s, e.ev_tn[set], 0));
-        e.tn_pending[set] = false;
-    }
+    CHECK_RC(join_set(e, set, s));           // the set was last read by layer l+2's side work
     const DropCfg nodrop = make_drop(0.f, 0, 0, false);
     // du = (dx . W2) * gelu'(u);  d ln2 = du . W1;  dx_mid = LNbwd(d ln2; x_mid) + dx
     CHECK_RC(run_gemm(e, G(dxg, H, e.ws + w.fc2T, H, du, I, Mv, I, H).mul_gelu_grad(e.ws + a.u, I).px_in(px, np).px_out(px, hi1), s));
@@ -1433,32 +1415,16 @@ int image_layer_backward(mmhip_engine& e, int l, hipStream_t s) {
                  e.wsp<float>(e.g_lnp[set][1]), 1.0f / e.gscale(), nullptr, nullptr, nodrop, 1, 1};
     ln_bwd_pair(b1, px, dxo_p, hi1);
     CHECK_HIP(launch_layernorm_bwd(b1, dt, s));
-    // ---- parameter gradients of the layer, off the dX chain -> side stream: the four weight gradients with their bias gradients in one grouped
-    // launch (no split-K, plain stores) and the second stage of the two LayerNorm reductions
-    hipStream_t ps = s;
-    if (side) {
-        CHECK_HIP(hipEventRecord(e.ev_ready[set], s));
-        CHECK_HIP(hipStreamWaitEvent(e.side, e.ev_ready[set], 0));
-        ps = e.side;
-    }
-    CHECK_HIP(launch_layernorm_bwd_reduce(b2, ps));
-    CHECK_HIP(launch_layernorm_bwd_reduce(b1, ps));
-    GemmTNProblem pr[4];
+    // ---- parameter gradients of the layer, off the dX chain -> side stream, forked once the whole chain is enqueued
+    hipStream_t ps;
+    CHECK_RC(fork_param_grads(e, set, s, ps));
     const int Mr = (int)mmhip_engine::pad64((size_t)Mv);          // reduction length with the zero pad rows (i_pad_B)
-    pr[0] = GemmTNProblem{dxg, e.ws + a.h, Gd + o.fc2_w, Mr, H, I, H, I, I, 0, Gd + o.fc2_b};               // dW2[H,I]    = dx^T h
-    pr[1] = GemmTNProblem{du, e.ws + a.ln2, Gd + o.fc1_w, Mr, I, H, I, H, H, 0, Gd + o.fc1_b};              // dW1[I,H]    = du^T ln2
-    pr[2] = GemmTNProblem{dqkv, e.ws + a.ln1, Gd + o.qkv_w, Mr, 3 * H, H, 3 * H, H, H, 0, Gd + o.qkv_b};    // dWqkv[3H,H] = dqkv^T ln1
-    pr[3] = GemmTNProblem{dxmid_g, e.ws + a.ctx, Gd + o.ao_w, Mr, H, H, H, H, H, 0, Gd + o.ao_b};           // dWo[H,H]    = dx_mid^T ctx
-    if (px) for (auto& q : pr) tn_pair(q, np);
-    {
-        const int i = e.side && ps == e.side ? 1 : 0;
-        CHECK_HIP(launch_gemm_tn(pr, 4, 0, dt, 0, ps, 1.0f / e.gscale(), e.x3_bytes[i] ? e.ws + e.x3_ws[i] : nullptr, e.x3_bytes[i]));
-    }
-    if (side) {
-        CHECK_HIP(hipEventRecord(e.ev_tn[set], e.side));
-        e.tn_pending[set] = true;
-    }
-    return 0;
+    GemmTNProblem pr[4] = {
+        {dxg, e.ws + a.h, Gd + o.fc2_w, Mr, H, I, H, I, I, 0, Gd + o.fc2_b},                   // dW2[H,I]    = dx^T h
+        {du, e.ws + a.ln2, Gd + o.fc1_w, Mr, I, H, I, H, H, 0, Gd + o.fc1_b},                  // dW1[I,H]    = du^T ln2
+        {dqkv, e.ws + a.ln1, Gd + o.qkv_w, Mr, 3 * H, H, 3 * H, H, H, 0, Gd + o.qkv_b},        // dWqkv[3H,H] = dqkv^T ln1
+        {dxmid_g, e.ws + a.ctx, Gd + o.ao_w, Mr, H, H, H, H, H, 0, Gd + o.ao_b}};              // dWo[H,H]    = dx_mid^T ctx
+    return layer_param_grads(e, set, ps, b2, b1, pr);
 }
 
 // stage L + 1: d position_embeddings, d cls_token and the compact patch-row gradient in one launch; the patch weight's gradient with its bias
@@ -1475,14 +1441,14 @@ int img_embed_backward(mmhip_engine& e, hipStream_t s) {
     GemmTNProblem pr{e.ws + e.i_dpe, e.ws + e.v_patches, e.grad + e.v_patch_w, (int)mmhip_engine::pad64((size_t)B * (P - 1)), H, Kpp, H, Kpp, Kpp, 0,
                      e.grad + e.v_patch_b};          // (zero pad rows: i_pad_B)
     if (px) tn_pair(pr, e.bwd_np);
-    CHECK_HIP(launch_gemm_tn(&pr, 1, 0, dt, 0, s, 1.0f / e.gscale(), e.x3_bytes[0] ? e.ws + e.x3_ws[0] : nullptr, e.x3_bytes[0]));
+    const X3Scratch x = x3_scratch(e, s);
+    CHECK_HIP(launch_gemm_tn(&pr, 1, 0, dt, 0, s, 1.0f / e.gscale(), x.ws, x.bytes));
     return 0;
 }
 
 int img_refresh(mmhip_engine& e, hipStream_t s) {
     for (int l = 0; l < e.cfg.layers_img; ++l) CHECK_RC(refresh_layer(e, e.train, e.vit[l], e.vit_w16[l], true, s, e.Hv(), e.Iv()));
-    CHECK_HIP(launch_cast_pad(e.train + e.v_patch_w, e.ws + e.patch_w16, e.Hv(), e.Kp(), e.Kpp(), e.px ? DT_PAIR : e.dt(), s));
-    return 0;
+    return refresh_patch(e, e.train, s);
 }
 
 }  // namespace
@@ -1543,7 +1509,7 @@ uint64_t mmhip_buffer_numel(mmhip_handle h, int buffer) { return !h ? 0 : (buffe
 uint64_t mmhip_workspace_bytes(mmhip_handle h) { return h ? h->ws_need : 0; }
 int mmhip_reserve_itc_global(mmhip_handle h, int max_world) {
     if (!h || max_world < 0) return MMHIP_E_INVALID;
-    if (h->ws || h->txt_only || h->img_only) return MMHIP_E_STATE;          // the workspace is sized before it is bound
+    if (h->ws || !h->is_late()) return MMHIP_E_STATE;          // the workspace is sized before it is bound
     mmhip_engine& e = *h;
     const size_t Bm = e.cfg.max_posts, E = e.cfg.proj_dim, Gm = (size_t)max_world * Bm;
     if (max_world > 1 && Gm > (size_t)ITC_GLOBAL_MAX_G) return MMHIP_E_INVALID;
@@ -1560,13 +1526,13 @@ int mmhip_reserve_itc_global(mmhip_handle h, int max_world) {
 }
 int mmhip_set_itc_global(mmhip_handle h, int world, int rank) {
     if (!h || world < 1 || rank < 0 || rank >= world) return MMHIP_E_INVALID;
-    if (h->txt_only || h->img_only) return MMHIP_E_STATE;
+    if (!h->is_late()) return MMHIP_E_STATE;
     if (world > 1 && world > h->itc_max_world) return MMHIP_E_CAPACITY;
     h->itc_world = world; h->itc_rank = rank;
     return 0;
 }
 int mmhip_itc_gather_buffers(mmhip_handle h, void** txt_local, void** img_local, void** txt_all, void** img_all) {
-    if (!h || !h->ws || !h->itc_max_world || h->txt_only || h->img_only) return MMHIP_E_STATE;
+    if (!h || !h->ws || !h->itc_max_world || !h->is_late()) return MMHIP_E_STATE;
     const mmhip_engine& e = *h;
     if (txt_local) *txt_local = e.ws + e.h_txt_n;
     if (img_local) *img_local = e.ws + e.h_img_n;
@@ -1575,7 +1541,7 @@ int mmhip_itc_gather_buffers(mmhip_handle h, void** txt_local, void** img_local,
     return 0;
 }
 int mmhip_bind(mmhip_handle h, float* frozen, float* train, float* train_grad, void* workspace, uint64_t workspace_bytes) {
-    if (!h || !frozen || !train || !workspace || h->txt_only || h->img_only) return MMHIP_E_INVALID;
+    if (!h || !frozen || !train || !workspace || !h->is_late()) return MMHIP_E_INVALID;
     if (workspace_bytes < h->ws_need) return MMHIP_E_CAPACITY;
     if (((uintptr_t)frozen | (uintptr_t)train | (uintptr_t)train_grad | (uintptr_t)workspace) & 255) return MMHIP_E_INVALID;
     h->frozen = frozen; h->train = train; h->grad = train_grad; h->ws = (char*)workspace; h->ws_bytes = workspace_bytes;
@@ -1586,13 +1552,12 @@ int mmhip_refresh_weights(mmhip_handle h, int which, void* stream) {
     if (!h || !h->ws) return MMHIP_E_STATE;
     hipStream_t s = (hipStream_t)stream;
     mmhip_engine& e = *h;
-    if ((which & 1) && e.txt_only) return MMHIP_E_STATE;          // no image tower, no frozen buffer (mmhip_txt_refresh_weights refreshes the text tower)
-    if (e.img_only) return MMHIP_E_STATE;                         // (mmhip_img_refresh_weights)
+    if ((which & 1) && e.is_text()) return MMHIP_E_STATE;          // no image tower, no frozen buffer (mmhip_txt_refresh_weights refreshes the text tower)
+    if (e.is_image()) return MMHIP_E_STATE;                         // (mmhip_img_refresh_weights)
     if (which & 1) {
         for (int l = 0; l < e.cfg.layers_img; ++l)
             CHECK_RC(refresh_layer(e, e.frozen, e.vit[l], e.vit_w16[l], false, s, e.Hv(), e.Iv()));
-        // patch-embedding weight [Hv, 3*p*p], rows zero-padded to the GEMM's k-step (14 x 14 patches: 588 -> 640)
-        CHECK_HIP(launch_cast_pad(e.frozen + e.v_patch_w, e.ws + e.patch_w16, e.Hv(), e.Kp(), e.Kpp(), e.px ? DT_PAIR : e.dt(), s));
+        CHECK_RC(refresh_patch(e, e.frozen, s));
     }
     if (which & 2)
         for (int l = 0; l < e.cfg.layers_txt; ++l)
@@ -1603,7 +1568,7 @@ int mmhip_refresh_weights(mmhip_handle h, int which, void* stream) {
 int mmhip_forward(mmhip_handle h, const int64_t* ids, const int64_t* mask, const float* pixels, const int64_t* tim_ids,
                   const int64_t* tim_mask, int B, int T, int train, uint64_t seed, float* out_cls, float* logits_per_text,
                   float* out_tim, float* mm_features, void* stream) {
-    if (!h || !h->ws || h->txt_only || h->img_only) return MMHIP_E_STATE;          // (a text-only handle has mmhip_txt_forward, an image-only one mmhip_img_forward)
+    if (!h || !h->ws || !h->is_late()) return MMHIP_E_STATE;          // (a text-only handle has mmhip_txt_forward, an image-only one mmhip_img_forward)
     if (!ids || !mask || B < 1 || T < 1) return MMHIP_E_INVALID;
     if ((tim_ids == nullptr) != (tim_mask == nullptr)) return MMHIP_E_INVALID;
     mmhip_engine& e = *h;
@@ -1705,12 +1670,12 @@ uint64_t mmhip_vision_record_bytes(mmhip_handle h) {
     return (P * h->Hv() * h->esz() + (uint64_t)h->Hv() * 4 + 255) & ~255ull;
 }
 int mmhip_vision_export(mmhip_handle h, const int64_t* slots, void* cache, uint64_t cache_records, void* stream) {
-    if (!h || !h->ws || !h->fwd_done || h->txt_only || h->img_only) return MMHIP_E_STATE;
+    if (!h || !h->ws || !h->fwd_done || !h->is_late()) return MMHIP_E_STATE;
     if (!slots || !cache || ((uintptr_t)cache & 15)) return MMHIP_E_INVALID;
     return vision_copy(*h, 1, slots, cache, cache_records, h->B, (hipStream_t)stream);
 }
 int mmhip_vision_import(mmhip_handle h, const int64_t* slots, const void* cache, uint64_t cache_records, int B, void* stream) {
-    if (!h || !h->ws || h->txt_only || h->img_only) return MMHIP_E_STATE;
+    if (!h || !h->ws || !h->is_late()) return MMHIP_E_STATE;
     if (!slots || !cache || ((uintptr_t)cache & 15) || B < 1) return MMHIP_E_INVALID;
     if (B > h->cfg.max_posts) return MMHIP_E_CAPACITY;
     CHECK_RC(vision_copy(*h, 0, slots, const_cast<void*>(cache), cache_records, B, (hipStream_t)stream));
@@ -1720,7 +1685,7 @@ int mmhip_vision_import(mmhip_handle h, const int64_t* slots, const void* cache,
 
 int mmhip_loss(mmhip_handle h, const int64_t* onehot, const float* class_w, const int64_t* lbl_tim, float w_cls, float w_itc,
                float w_itm, float* loss, int* n_correct, void* stream) {
-    if (!h || !h->fwd_done || h->txt_only || h->img_only) return MMHIP_E_STATE;
+    if (!h || !h->fwd_done || !h->is_late()) return MMHIP_E_STATE;
     if (!onehot) return MMHIP_E_INVALID;
     mmhip_engine& e = *h;
     if (w_itm != 0.f && (!e.itm || !lbl_tim)) return MMHIP_E_INVALID;
@@ -1784,13 +1749,13 @@ int mmhip_backward_stage(mmhip_handle h, int stage, void* stream) {
     mmhip_engine& e = *h;
     hipStream_t s = (hipStream_t)stream;
     const int L = e.nl();
-    if (e.img_only) {
+    if (e.is_image()) {
         if (stage == 0) return img_head_backward(e, s);
         if (stage >= 1 && stage <= L) return image_layer_backward(e, L - stage, s);
         if (stage == L + 1) return img_embed_backward(e, s);
         return MMHIP_E_INVALID;
     }
-    if (stage == 0) return e.txt_only ? txt_head_backward(e, s) : heads_backward(e, s);
+    if (stage == 0) return e.is_text() ? txt_head_backward(e, s) : heads_backward(e, s);
     if (stage >= 1 && stage <= L) return text_layer_backward(e, L - stage, s);
     if (stage == L + 1) return embed_backward(e, s);
     return MMHIP_E_INVALID;
@@ -1800,12 +1765,7 @@ int mmhip_backward_join_stage(mmhip_handle h, int stage, void* stream) {
     mmhip_engine& e = *h;
     const int L = e.nl();
     if (stage < 1 || stage > L) return 0;
-    const int set = (L - stage) & 1;
-    if (e.tn_pending[set]) {
-        CHECK_HIP(hipStreamWaitEvent((hipStream_t)stream, e.ev_tn[set], 0));
-        e.tn_pending[set] = false;
-    }
-    return 0;
+    return join_set(e, (L - stage) & 1, (hipStream_t)stream);
 }
 int mmhip_backward_finish(mmhip_handle h, void* stream) {
     if (!h || !h->bwd_begun) return MMHIP_E_STATE;
@@ -1862,11 +1822,8 @@ static int adamw_impl(float* p, float* g, float* m, float* v, uint64_t n, float 
                       float weight_decay, int step, float grad_scale, int zero_grad, void* stream, unsigned* g_nonfinite, const unsigned* g_skip) {
     if (!p || !g || !m || !v || step < 1) return MMHIP_E_INVALID;
     if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return MMHIP_E_INVALID;
-    AdamWArgs a;
-    a.p = p; a.g = g; a.m = m; a.v = v; a.n = n; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = weight_decay;
-    a.bc1 = (float)(1.0 - pow((double)beta1, step));
-    a.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, step));
-    a.zero_grad = zero_grad; a.grad_scale = grad_scale; a.nonfinite = g_nonfinite; a.skip = g_skip;
+    AdamWArgs a = adamw_args(lr, beta1, beta2, eps, weight_decay, step, grad_scale, zero_grad, g_nonfinite, g_skip);
+    a.p = p; a.g = g; a.m = m; a.v = v; a.n = n;
     CHECK_HIP(launch_adamw(a, (hipStream_t)stream));
     return 0;
 }
@@ -1891,11 +1848,8 @@ static int adamw_rows_impl(float* p, float* g, float* m, float* v, int rows, int
                            float eps, float weight_decay, int step, float grad_scale, int zero_grad, void* stream, unsigned* g_nonfinite, const unsigned* g_skip) {
     if (!p || !g || !m || !v || !row_state || step < 1 || rows < 0 || width <= 0 || width % 4) return MMHIP_E_INVALID;
     if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return MMHIP_E_INVALID;
-    AdamWArgs a;
-    a.p = p; a.g = g; a.m = m; a.v = v; a.n = (size_t)rows * width; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = weight_decay;
-    a.bc1 = (float)(1.0 - pow((double)beta1, step));
-    a.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, step));
-    a.zero_grad = zero_grad; a.grad_scale = grad_scale; a.nonfinite = g_nonfinite; a.skip = g_skip;
+    AdamWArgs a = adamw_args(lr, beta1, beta2, eps, weight_decay, step, grad_scale, zero_grad, g_nonfinite, g_skip);
+    a.p = p; a.g = g; a.m = m; a.v = v; a.n = (size_t)rows * width;
     CHECK_HIP(launch_adamw_rows(a, rows, width, row_state, (hipStream_t)stream));
     return 0;
 }
@@ -1963,7 +1917,7 @@ static int step_backward_update(mmhip_handle h, int use_itc, int use_itm, float*
     const int L = e.nl();          // text layers; an image-only handle: its image layers
     const std::vector<LayerOff>& lay = e.lay();
     const std::vector<LayerW16>& lay16 = e.lay_w16();
-    const int lH = e.img_only ? e.Hv() : e.cfg.hidden, lI = e.img_only ? e.Iv() : e.cfg.inter;
+    const int lH = e.is_image() ? e.Hv() : e.cfg.hidden, lI = e.is_image() ? e.Iv() : e.cfg.inter;
     // data-parallel form (cb): the callback is told about stage st-1 once stage st is enqueued and st-1's weight gradients are ordered in the
     // caller's stream -- its collective travels while the stages below compute.  The layer optimizers wait for the gradient exchange: PER BUCKET
     // (round 5).  When the callback answers MMHIP_CB_BUCKET -- "the collective that carries every stage since the last such answer has been
@@ -2031,7 +1985,7 @@ static int step_backward_update(mmhip_handle h, int use_itc, int use_itm, float*
     CHECK_RC(e.span(4, s));
     // merged [begin, end) ranges of the active gradient groups, in address order (text layers already stepped: skipped)
     bool act[6] = {false, use_itc != 0, use_itm != 0, e.cfg.fusion == MMHIP_FUSION_ATTENTION, true, false};
-    const uint64_t w0 = e.img_only ? e.n_train : e.t_word, V = (uint64_t)e.cfg.vocab, H = (uint64_t)e.cfg.hidden;      // (no word table in an image-only handle)
+    const uint64_t w0 = e.is_image() ? e.n_train : e.t_word, V = (uint64_t)e.cfg.vocab, H = (uint64_t)e.cfg.hidden;      // (no word table in an image-only handle)
     uint64_t rb = 0, re = 0;
     bool open = false;
     bool rows_due = false;
@@ -2058,8 +2012,8 @@ static int step_backward_update(mmhip_handle h, int use_itc, int use_itm, float*
     CHECK_RC(flush());
     for (int l = 0; l < L; ++l)          // 16-bit GEMM operand copies of the layers stepped just now: no word-table dependence
         if (!layer_done[l]) CHECK_RC(refresh_layer(e, e.train, lay[l], lay16[l], true, s, lH, lI));
-    if (e.img_only)          // the patch weight was stepped with the embeddings' range just now
-        CHECK_HIP(launch_cast_pad(e.train + e.v_patch_w, e.ws + e.patch_w16, e.Hv(), e.Kp(), e.Kpp(), e.px ? DT_PAIR : e.dt(), s));
+    if (e.is_image())          // the patch weight was stepped with the embeddings' range just now
+        CHECK_RC(refresh_patch(e, e.train, s));
     if (rows_due) {
         if (cb) CHECK_RC(cb(user, MMHIP_CB_FINISH_ROWS));                 // the exchanged word rows are summed into the gradient
         if (!e.word_row_state) return MMHIP_E_STATE;
@@ -2161,20 +2115,52 @@ int mmhip_gemm_timing_by_shape(mmhip_handle h, char* out, uint64_t capacity) {
     return 0;
 }
 
+// ================================================================================================ one-tower handles: what mmhip_txt_* and mmhip_img_* share
+// Every entry point of a kind refuses a handle of another kind before it touches it; the accessors forward to the late-fusion ones.
+using Kind = mmhip_engine::Kind;
+static bool is_kind(mmhip_handle h, Kind k) { return h && h->kind == k; }
+// the configuration fields both kinds have
+static bool tower_config_ok(int hidden, int heads, int inter, int layers, int dtype, int max_posts, int num_labels, float loss_scale) {
+    if (hidden <= 0 || hidden % 128 || hidden > 1024 || heads * 64 != hidden || inter <= 0 || inter % 128 || layers < 0) return false;
+    if (max_posts < 1 || max_posts > 1024) return false;
+    if (dtype != MMHIP_BF16 && dtype != MMHIP_F16 && dtype != MMHIP_BF16X3) return false;
+    return num_labels >= 1 && num_labels <= CLS_HEAD_MAX_C && loss_scale >= 0.f;
+}
+// one trainable buffer, no frozen one; the image tower's pad rows (i_pad_B) are cleared again for a new workspace
+static int one_tower_bind(mmhip_handle h, Kind k, float* params, float* grad, void* workspace, uint64_t workspace_bytes) {
+    if (!is_kind(h, k) || !params || !workspace) return MMHIP_E_INVALID;
+    if (workspace_bytes < h->ws_need) return MMHIP_E_CAPACITY;
+    if (((uintptr_t)params | (uintptr_t)grad | (uintptr_t)workspace) & 255) return MMHIP_E_INVALID;
+    h->frozen = nullptr; h->train = params; h->grad = grad; h->ws = (char*)workspace; h->ws_bytes = workspace_bytes;
+    h->fwd_done = false;
+    h->i_pad_B = 0;
+    return 0;
+}
+// opens a forward of B posts (no ITM rows): nothing of an earlier forward, loss or backward survives; no CU partition (one tower)
+static int one_tower_begin(mmhip_engine& e, int B, int T, int train, uint64_t seed) {
+    e.B = e.Bt = B; e.T = T; e.itm = false; e.train_mode = train != 0; e.seed = seed;
+    e.fwd_done = false; e.bwd_begun = false; e.bd_out_cls = nullptr; e.bd_logits = e.bd_out_tim = e.bd_feats = nullptr; e.bd_itc_global = false;
+    e.cur_part[0] = e.cur_part[1] = 0;
+    return side_init(e);
+}
+static int one_tower_step_guard(mmhip_handle h, Kind k, const float* adam_m, const float* adam_v, const int64_t* onehot, int step) {
+    if (!is_kind(h, k) || !h->ws || !h->grad) return MMHIP_E_STATE;
+    if (!adam_m || !adam_v || !onehot || step < 1) return MMHIP_E_INVALID;
+    return 0;
+}
+
 // ================================================================================================ text-only handle (mmhip_txt_*)
 // The reference's text-only trainer (models/text_only.py: BERT / BERNICE + TextModel.train): the text tower of this engine -- the same layer launch
 // sequences, forward and backward -- under the fused CLS classifier head, without the image tower and the dual-encoder heads.
 int mmhip_txt_create(const mmhip_txt_config* cfg, mmhip_txt_handle* out) {
     if (!cfg || !out) return MMHIP_E_INVALID;
     const mmhip_txt_config& t = *cfg;
-    if (t.hidden <= 0 || t.hidden % 128 || t.hidden > 1024 || t.heads * 64 != t.hidden || t.inter <= 0 || t.inter % 128 || t.layers < 0) return MMHIP_E_INVALID;
-    if (t.max_text_len > 128 || t.max_text_len < 1 || t.max_posts < 1 || t.max_posts > 1024) return MMHIP_E_INVALID;
-    if (t.dtype != MMHIP_BF16 && t.dtype != MMHIP_F16 && t.dtype != MMHIP_BF16X3) return MMHIP_E_INVALID;
-    if (t.num_labels < 1 || t.num_labels > CLS_HEAD_MAX_C || t.vocab < 1 || t.type_vocab < 1 || t.type_vocab > 2) return MMHIP_E_INVALID;
+    if (!tower_config_ok(t.hidden, t.heads, t.inter, t.layers, t.dtype, t.max_posts, t.num_labels, t.loss_scale)) return MMHIP_E_INVALID;
+    if (t.max_text_len > 128 || t.max_text_len < 1 || t.vocab < 1 || t.type_vocab < 1 || t.type_vocab > 2) return MMHIP_E_INVALID;
     if (t.txt_kind != MMHIP_TXT_XLMR && t.txt_kind != MMHIP_TXT_BERT) return MMHIP_E_INVALID;
     if (t.txt_kind == MMHIP_TXT_XLMR && t.max_pos < t.max_text_len + t.pad_id + 1) return MMHIP_E_INVALID;
     if (t.txt_kind == MMHIP_TXT_BERT && t.max_pos < t.max_text_len) return MMHIP_E_INVALID;
-    if (t.pad_id < 0 || t.pad_id >= t.vocab || !(t.p_hidden >= 0.f) || !(t.p_attn >= 0.f) || !(t.p_head >= 0.f) || !(t.loss_scale >= 0.f)) return MMHIP_E_INVALID;
+    if (t.pad_id < 0 || t.pad_id >= t.vocab || !(t.p_hidden >= 0.f) || !(t.p_attn >= 0.f) || !(t.p_head >= 0.f)) return MMHIP_E_INVALID;
     mmhip_engine* e = new (std::nothrow) mmhip_engine();
     if (!e) return MMHIP_E_INVALID;
     mmhip_config& c = e->cfg;
@@ -2186,7 +2172,7 @@ int mmhip_txt_create(const mmhip_txt_config* cfg, mmhip_txt_handle* out) {
     c.ln_eps_txt = c.ln_eps_img = t.ln_eps; c.image = c.patch = 16; c.proj_dim = 1; c.num_labels = t.num_labels; c.fusion = MMHIP_FUSION_CONCAT;
     c.p_hidden = t.p_hidden; c.p_attn = t.p_attn; c.p_head = t.p_head; c.dtype = t.dtype; c.max_posts = t.max_posts; c.max_text_len = t.max_text_len;
     c.loss_scale = t.loss_scale; c.img_kind = MMHIP_IMG_VIT;
-    e->txt_only = true;
+    e->kind = mmhip_engine::TEXT;
     e->tm_prefix = "bert_model.";
     read_x3_env(*e);
     build_layout_txt(*e);
@@ -2194,44 +2180,36 @@ int mmhip_txt_create(const mmhip_txt_config* cfg, mmhip_txt_handle* out) {
     *out = e;
     return 0;
 }
-void mmhip_txt_destroy(mmhip_txt_handle h) { if (h && h->txt_only) mmhip_destroy(h); }
-int mmhip_txt_param_count(mmhip_txt_handle h) { return h && h->txt_only ? (int)h->params.size() : MMHIP_E_INVALID; }
-int mmhip_txt_param_info_at(mmhip_txt_handle h, int i, mmhip_param_info* out) { return h && h->txt_only ? mmhip_param_info_at(h, i, out) : MMHIP_E_INVALID; }
-uint64_t mmhip_txt_numel(mmhip_txt_handle h) { return h && h->txt_only ? h->n_train : 0; }
-uint64_t mmhip_txt_workspace_bytes(mmhip_txt_handle h) { return h && h->txt_only ? h->ws_need : 0; }
+void mmhip_txt_destroy(mmhip_txt_handle h) { if (is_kind(h, Kind::TEXT)) mmhip_destroy(h); }
+int mmhip_txt_param_count(mmhip_txt_handle h) { return is_kind(h, Kind::TEXT) ? mmhip_param_count(h) : MMHIP_E_INVALID; }
+int mmhip_txt_param_info_at(mmhip_txt_handle h, int i, mmhip_param_info* out) { return is_kind(h, Kind::TEXT) ? mmhip_param_info_at(h, i, out) : MMHIP_E_INVALID; }
+uint64_t mmhip_txt_numel(mmhip_txt_handle h) { return is_kind(h, Kind::TEXT) ? mmhip_buffer_numel(h, 1) : 0; }
+uint64_t mmhip_txt_workspace_bytes(mmhip_txt_handle h) { return is_kind(h, Kind::TEXT) ? mmhip_workspace_bytes(h) : 0; }
 int mmhip_txt_bind(mmhip_txt_handle h, float* params, float* grad, void* workspace, uint64_t workspace_bytes) {
-    if (!h || !h->txt_only || !params || !workspace) return MMHIP_E_INVALID;
-    if (workspace_bytes < h->ws_need) return MMHIP_E_CAPACITY;
-    if (((uintptr_t)params | (uintptr_t)grad | (uintptr_t)workspace) & 255) return MMHIP_E_INVALID;
-    h->frozen = nullptr; h->train = params; h->grad = grad; h->ws = (char*)workspace; h->ws_bytes = workspace_bytes;
-    h->fwd_done = false;
-    return 0;
+    return one_tower_bind(h, Kind::TEXT, params, grad, workspace, workspace_bytes);
 }
 int mmhip_txt_refresh_weights(mmhip_txt_handle h, void* stream) {
-    if (!h || !h->txt_only) return MMHIP_E_INVALID;
+    if (!is_kind(h, Kind::TEXT)) return MMHIP_E_INVALID;
     return mmhip_refresh_weights(h, 2, stream);
 }
 // forward of the tower and the head; onehot != NULL: the head also leaves loss / correct count / d logits (fused step and mmhip_txt_loss)
 static int txt_forward_impl(mmhip_txt_handle h, const int64_t* ids, const int64_t* mask, const int64_t* type_ids, int B, int T, int train, uint64_t seed,
                             const int64_t* onehot, const float* class_w, float* logits, float* loss, int* n_correct, void* stream) {
-    if (!h || !h->txt_only || !h->ws) return MMHIP_E_STATE;
+    if (!is_kind(h, Kind::TEXT) || !h->ws) return MMHIP_E_STATE;
     if (!ids || !mask || B < 1 || T < 1) return MMHIP_E_INVALID;
     mmhip_engine& e = *h;
     if (B > e.cfg.max_posts || T > e.cfg.max_text_len) return MMHIP_E_CAPACITY;
     hipStream_t s = (hipStream_t)stream;
-    e.B = e.Bt = B; e.T = T; e.itm = false; e.train_mode = train != 0; e.seed = seed;
-    e.fwd_done = false; e.bwd_begun = false; e.bd_out_cls = nullptr; e.bd_logits = e.bd_out_tim = e.bd_feats = nullptr; e.bd_itc_global = false;
+    CHECK_RC(one_tower_begin(e, B, T, train, seed));
     CHECK_HIP(launch_copy_ids_clamped(ids, e.wsp<int64_t>(e.ids_all), (size_t)B * T, e.cfg.vocab, e.bad_index, s));
     CHECK_HIP(hipMemcpyAsync(e.ws + e.mask_all, mask, (size_t)B * T * 8, hipMemcpyDeviceToDevice, s));
     // a one-row type table has nothing to select: every token takes row 0 whatever the caller passes (RoBERTa-shaped checkpoints)
     e.has_tt = type_ids != nullptr && e.cfg.type_vocab > 1;
     if (e.has_tt) CHECK_HIP(launch_copy_ids_clamped(type_ids, e.wsp<int64_t>(e.tt_all), (size_t)B * T, e.cfg.type_vocab, e.bad_index, s));
-    CHECK_RC(side_init(e));
-    e.cur_part[0] = e.cur_part[1] = 0;
     CHECK_RC(e.span(0, s));
     CHECK_RC(text_forward(e, s));
     CHECK_RC(e.span(2, s));
-    CHECK_RC(txt_head_forward(e, onehot, class_w, logits, loss, n_correct, s));
+    CHECK_RC(cls_head_forward(e, txt_head_args(e), onehot, class_w, logits, loss, n_correct, s));
     CHECK_RC(e.span(3, s));
     e.fwd_done = true;
     return 0;
@@ -2241,19 +2219,18 @@ int mmhip_txt_forward(mmhip_txt_handle h, const int64_t* ids, const int64_t* mas
     return txt_forward_impl(h, ids, mask, type_ids, B, T, train, seed, nullptr, nullptr, logits, nullptr, nullptr, stream);
 }
 int mmhip_txt_loss(mmhip_txt_handle h, const int64_t* onehot, const float* class_w, float* loss, int* n_correct, void* stream) {
-    if (!h || !h->txt_only || !h->fwd_done) return MMHIP_E_STATE;
+    if (!is_kind(h, Kind::TEXT) || !h->fwd_done) return MMHIP_E_STATE;
     if (!onehot) return MMHIP_E_INVALID;
-    return txt_head_forward(*h, onehot, class_w, nullptr, loss, n_correct, (hipStream_t)stream);
+    return cls_head_forward(*h, txt_head_args(*h), onehot, class_w, nullptr, loss, n_correct, (hipStream_t)stream);
 }
 int mmhip_txt_backward(mmhip_txt_handle h, const float* d_logits, void* stream) {
-    if (!h || !h->txt_only) return MMHIP_E_STATE;
+    if (!is_kind(h, Kind::TEXT)) return MMHIP_E_STATE;
     return mmhip_backward(h, d_logits, nullptr, nullptr, nullptr, stream);
 }
 int mmhip_txt_train_step(mmhip_txt_handle h, const int64_t* ids, const int64_t* mask, const int64_t* type_ids, const int64_t* onehot, const float* class_w,
                          int B, int T, uint64_t seed, float* adam_m, float* adam_v, float lr, float beta1, float beta2, float eps, float weight_decay,
                          int step, float* loss, int* n_correct, void* stream) {
-    if (!h || !h->txt_only || !h->ws || !h->grad) return MMHIP_E_STATE;
-    if (!adam_m || !adam_v || !onehot || step < 1) return MMHIP_E_INVALID;
+    CHECK_RC(one_tower_step_guard(h, Kind::TEXT, adam_m, adam_v, onehot, step));
     CHECK_RC(txt_forward_impl(h, ids, mask, type_ids, B, T, 1, seed, onehot, class_w, nullptr, loss, n_correct, stream));
     return step_backward_update(h, 0, 0, adam_m, adam_v, lr, beta1, beta2, eps, weight_decay, step, 1.0f, stream, nullptr, nullptr);
 }
@@ -2263,13 +2240,11 @@ int mmhip_txt_train_step(mmhip_txt_handle h, const int64_t* ids, const int64_t* 
 int mmhip_img_create(const mmhip_img_config* cfg, mmhip_img_handle* out) {
     if (!cfg || !out) return MMHIP_E_INVALID;
     const mmhip_img_config& t = *cfg;
-    if (t.hidden <= 0 || t.hidden % 128 || t.hidden > 1024 || t.heads * 64 != t.hidden || t.inter <= 0 || t.inter % 128 || t.layers < 0) return MMHIP_E_INVALID;
+    if (!tower_config_ok(t.hidden, t.heads, t.inter, t.layers, t.dtype, t.max_posts, t.num_labels, t.loss_scale)) return MMHIP_E_INVALID;
     if (t.patch < 2 || t.image < t.patch || t.image % t.patch || (3 * t.patch * t.patch) % 64) return MMHIP_E_INVALID;
     const int P = (t.image / t.patch) * (t.image / t.patch) + 1;
     if (P < 129 || P > 288) return MMHIP_E_INVALID;          // what launch_attn_bwd_long takes (160 px and 384 px are out of scope)
-    if (t.max_posts < 1 || t.max_posts > 1024) return MMHIP_E_INVALID;
-    if (t.dtype != MMHIP_BF16 && t.dtype != MMHIP_F16 && t.dtype != MMHIP_BF16X3) return MMHIP_E_INVALID;
-    if (t.num_labels < 1 || t.num_labels > CLS_HEAD_MAX_C || !(t.loss_scale >= 0.f) || !(t.ln_eps > 0.f)) return MMHIP_E_INVALID;
+    if (!(t.ln_eps > 0.f)) return MMHIP_E_INVALID;
     if (t.p_hidden != 0.f || t.p_attn != 0.f) return MMHIP_E_INVALID;          // the checkpoints' tower dropouts are 0: no dropout is built into this path
     mmhip_engine* e = new (std::nothrow) mmhip_engine();
     if (!e) return MMHIP_E_INVALID;
@@ -2280,46 +2255,37 @@ int mmhip_img_create(const mmhip_img_config* cfg, mmhip_img_handle* out) {
     c.vocab = 1; c.max_pos = 1; c.type_vocab = 1; c.txt_kind = MMHIP_TXT_BERT; c.pad_id = 0; c.max_text_len = 1; c.proj_dim = 1; c.fusion = MMHIP_FUSION_CONCAT;
     c.ln_eps_txt = c.ln_eps_img = t.ln_eps; c.image = t.image; c.patch = t.patch; c.num_labels = t.num_labels; c.dtype = t.dtype; c.max_posts = t.max_posts;
     c.loss_scale = t.loss_scale; c.img_kind = MMHIP_IMG_VIT;
-    e->img_only = true;
+    e->kind = mmhip_engine::IMAGE;
     read_x3_env(*e);
     build_layout_img(*e);
     build_workspace_img(*e);
     *out = e;
     return 0;
 }
-void mmhip_img_destroy(mmhip_img_handle h) { if (h && h->img_only) mmhip_destroy(h); }
-int mmhip_img_param_count(mmhip_img_handle h) { return h && h->img_only ? (int)h->params.size() : MMHIP_E_INVALID; }
-int mmhip_img_param_info_at(mmhip_img_handle h, int i, mmhip_param_info* out) { return h && h->img_only ? mmhip_param_info_at(h, i, out) : MMHIP_E_INVALID; }
-uint64_t mmhip_img_numel(mmhip_img_handle h) { return h && h->img_only ? h->n_train : 0; }
-uint64_t mmhip_img_workspace_bytes(mmhip_img_handle h) { return h && h->img_only ? h->ws_need : 0; }
+void mmhip_img_destroy(mmhip_img_handle h) { if (is_kind(h, Kind::IMAGE)) mmhip_destroy(h); }
+int mmhip_img_param_count(mmhip_img_handle h) { return is_kind(h, Kind::IMAGE) ? mmhip_param_count(h) : MMHIP_E_INVALID; }
+int mmhip_img_param_info_at(mmhip_img_handle h, int i, mmhip_param_info* out) { return is_kind(h, Kind::IMAGE) ? mmhip_param_info_at(h, i, out) : MMHIP_E_INVALID; }
+uint64_t mmhip_img_numel(mmhip_img_handle h) { return is_kind(h, Kind::IMAGE) ? mmhip_buffer_numel(h, 1) : 0; }
+uint64_t mmhip_img_workspace_bytes(mmhip_img_handle h) { return is_kind(h, Kind::IMAGE) ? mmhip_workspace_bytes(h) : 0; }
 int mmhip_img_bind(mmhip_img_handle h, float* params, float* grad, void* workspace, uint64_t workspace_bytes) {
-    if (!h || !h->img_only || !params || !workspace) return MMHIP_E_INVALID;
-    if (workspace_bytes < h->ws_need) return MMHIP_E_CAPACITY;
-    if (((uintptr_t)params | (uintptr_t)grad | (uintptr_t)workspace) & 255) return MMHIP_E_INVALID;
-    h->frozen = nullptr; h->train = params; h->grad = grad; h->ws = (char*)workspace; h->ws_bytes = workspace_bytes;
-    h->fwd_done = false;
-    h->i_pad_B = 0;
-    return 0;
+    return one_tower_bind(h, Kind::IMAGE, params, grad, workspace, workspace_bytes);
 }
 int mmhip_img_refresh_weights(mmhip_img_handle h, void* stream) {
-    if (!h || !h->img_only) return MMHIP_E_INVALID;
+    if (!is_kind(h, Kind::IMAGE)) return MMHIP_E_INVALID;
     if (!h->ws) return MMHIP_E_STATE;
     return img_refresh(*h, (hipStream_t)stream);
 }
 static int img_forward_impl(mmhip_img_handle h, const float* pixels, int B, int train, const int64_t* onehot, const float* class_w, float* logits, float* loss,
                             int* n_correct, void* stream) {
-    if (!h || !h->img_only || !h->ws) return MMHIP_E_STATE;
+    if (!is_kind(h, Kind::IMAGE) || !h->ws) return MMHIP_E_STATE;
     if (!pixels || B < 1) return MMHIP_E_INVALID;
     mmhip_engine& e = *h;
     if (B > e.cfg.max_posts) return MMHIP_E_CAPACITY;
     hipStream_t s = (hipStream_t)stream;
-    e.B = e.Bt = B; e.T = 1; e.itm = false; e.train_mode = train != 0; e.seed = 0;
-    e.fwd_done = false; e.bwd_begun = false; e.bd_out_cls = nullptr; e.bd_logits = e.bd_out_tim = e.bd_feats = nullptr; e.bd_itc_global = false;
-    CHECK_RC(side_init(e));
-    e.cur_part[0] = e.cur_part[1] = 0;
+    CHECK_RC(one_tower_begin(e, B, 1, train, 0));
     CHECK_RC(e.span(0, s));
     if (e.i_pad_B != B) CHECK_RC(img_zero_pads(e, B, s));
-    CHECK_RC(img_tower_forward(e, pixels, s));
+    CHECK_RC(image_layers_forward(e, pixels, true, s));
     CHECK_RC(e.span(1, s));
     CHECK_RC(img_head_forward(e, onehot, class_w, logits, loss, n_correct, s));
     CHECK_RC(e.span(3, s));
@@ -2330,18 +2296,17 @@ int mmhip_img_forward(mmhip_img_handle h, const float* pixels, int B, int train,
     return img_forward_impl(h, pixels, B, train, nullptr, nullptr, logits, nullptr, nullptr, stream);
 }
 int mmhip_img_loss(mmhip_img_handle h, const int64_t* onehot, const float* class_w, float* loss, int* n_correct, void* stream) {
-    if (!h || !h->img_only || !h->fwd_done) return MMHIP_E_STATE;
+    if (!is_kind(h, Kind::IMAGE) || !h->fwd_done) return MMHIP_E_STATE;
     if (!onehot) return MMHIP_E_INVALID;
-    return img_head_classify(*h, onehot, class_w, nullptr, loss, n_correct, (hipStream_t)stream);
+    return cls_head_forward(*h, img_head_args(*h), onehot, class_w, nullptr, loss, n_correct, (hipStream_t)stream);
 }
 int mmhip_img_backward(mmhip_img_handle h, const float* d_logits, void* stream) {
-    if (!h || !h->img_only) return MMHIP_E_STATE;
+    if (!is_kind(h, Kind::IMAGE)) return MMHIP_E_STATE;
     return mmhip_backward(h, d_logits, nullptr, nullptr, nullptr, stream);
 }
 int mmhip_img_train_step(mmhip_img_handle h, const float* pixels, const int64_t* onehot, const float* class_w, int B, float* adam_m, float* adam_v,
                          float lr, float beta1, float beta2, float eps, float weight_decay, int step, float* loss, int* n_correct, void* stream) {
-    if (!h || !h->img_only || !h->ws || !h->grad) return MMHIP_E_STATE;
-    if (!adam_m || !adam_v || !onehot || step < 1) return MMHIP_E_INVALID;
+    CHECK_RC(one_tower_step_guard(h, Kind::IMAGE, adam_m, adam_v, onehot, step));
     CHECK_RC(img_forward_impl(h, pixels, B, 1, onehot, class_w, nullptr, loss, n_correct, stream));
     return step_backward_update(h, 0, 0, adam_m, adam_v, lr, beta1, beta2, eps, weight_decay, step, 1.0f, stream, nullptr, nullptr);
 }

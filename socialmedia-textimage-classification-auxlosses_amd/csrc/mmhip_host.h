@@ -163,6 +163,19 @@ inline int launch_tn_groups(const std::vector<GemmTNProblem>& probs, int accumul
                           [&](const GemmTNProblem* p, int n) { return launch_gemm_tn(p, n, accumulate, dtype, 0, s, 1.0f); });
 }
 
+// ------------------------------------------------------------------------------------------------ optimizer
+// everything of an AdamW launch but the range (p, g, m, v, n), which the caller fills per launch: the hyper-parameters, the bias corrections of
+// `step` (computed in double), and the overflow guard's words (either may be null)
+inline AdamWArgs adamw_args(float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, int zero_grad,
+                            unsigned* nonfinite = nullptr, const unsigned* skip = nullptr) {
+    AdamWArgs a{};
+    a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = weight_decay;
+    a.bc1 = (float)(1.0 - pow((double)beta1, step));
+    a.bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, step));
+    a.zero_grad = zero_grad; a.grad_scale = grad_scale; a.nonfinite = nonfinite; a.skip = skip;
+    return a;
+}
+
 // ------------------------------------------------------------------------------------------------ layout
 // workspace carve-up: byte offsets, every piece 256-byte aligned
 struct Carver {
