@@ -422,6 +422,43 @@ int mmhip_op_itc_global_fwd(const float* txt_n, const float* img_n, const float*
 int mmhip_op_itc_global_bwd(const float* txt_n, const float* img_n, const float* logit_scale, const float* rowlse, const float* collse, int G, int B_local,
                             int rank_offset, int E, float seed, float* d_txt_n, float* d_img_n, float* d_logit_scale, const float* txt_inv,
                             const float* img_inv, float* d_txt_e, float* d_img_e, void* ws, uint64_t ws_bytes, void* stream);
+/* ---- the rest of the late-fusion head, alone (operator tests): fusion attention, the fused loss, the heads' fp32 GEMM and bias gradient.
+ * Fusion attention for the CLS query (csrc/heads.hip fusion_attn_fwd_kernel / _bwd_kernel).  qk fp32 [Bt, H]; xv [B * P, H] image tokens of type
+ * dtype = MMHIP_BF16 | MMHIP_F16 | MMHIP_F32 (parity mode: the float kernel); row bt attends to the P tokens of post bt % B (Bt = 2 B: the ITM
+ * rows reuse the images of the first B).
+ *   fwd: s_j = scale * qk[bt] . xv[bt % B, j],  prob [Bt, P] = softmax_j(s),  xbar [Bt, H] = sum_j prob_j xv[bt % B, j]   (both overwritten)
+ *   bwd: dp_j = dxbar[bt] . xv[bt % B, j],  dqk [Bt, H] = scale * sum_j prob_j (dp_j - sum_i prob_i dp_i) xv[bt % B, j]    (overwritten)
+ * MMHIP_E_INVALID before any launch, nothing written: a NULL tensor, B < 1, Bt < 1, P < 1 or > 512, H < 4 or > 1024 or H % 4 != 0, another dtype,
+ * xv / qk / dxbar off 16-byte alignment (the kernels load rows 8 and 16 bytes at a time). */
+int mmhip_op_fusion_attn_fwd(int dtype, const float* qk, const void* xv, int Bt, int B, int P, int H, float scale, float* prob, float* xbar, void* stream);
+int mmhip_op_fusion_attn_bwd(int dtype, const float* dxbar, const float* prob, const void* xv, int Bt, int B, int P, int H, float scale, float* dqk,
+                             void* stream);
+/* The fused loss mix and its gradients, one launch (csrc/heads.hip loss_kernel; what mmhip_loss runs on the engine's buffers).  out_cls fp32 [B, C],
+ * onehot int64 [B, C] read as a soft target (float)onehot, class_w [C] or NULL (all 1):
+ *   loss[1] = -(1 / B) sum_bc class_w_c y_bc log_softmax(out_cls)_bc;   loss[2] = the ITC term: from logits_per_text [B, B],
+ *   (CE(S, arange) + CE(S^T, arange)) / 2, or the scalar itc_global_loss[0] computed elsewhere (at most one of the two; neither: 0);
+ *   loss[3] = mean CE(out_tim [B, 2], lbl_tim int64 [B]) (out_tim NULL: 0);   loss[0] = w_cls loss[1] + w_itc loss[2] + w_itm loss[3].
+ * d_out_cls [B, C], d_logits [B, B] (only with logits_per_text), d_out_tim [B, 2]: gradients of loss[0], overwritten; n_correct[0] = the number
+ * of rows whose first arg-max of out_cls is the first arg-max of onehot.  Each of the four may be NULL: loss[] is the same bits and nothing
+ * else is written.  MMHIP_E_INVALID before the launch: out_cls, onehot or loss NULL, B < 1 or > 1024, C < 1, out_tim without lbl_tim, both
+ * logits_per_text and itc_global_loss. */
+int mmhip_op_loss(const float* out_cls, const int64_t* onehot, const float* class_w, const float* logits_per_text, const float* itc_global_loss,
+                  const float* out_tim, const int64_t* lbl_tim, float w_cls, float w_itc, float w_itm, int B, int C, float* loss, float* d_out_cls,
+                  float* d_logits, float* d_out_tim, int32_t* n_correct, void* stream);
+/* The heads' exact-fp32 GEMM on the matrix cores (csrc/gemm.hip small_gemm_kernel behind launch_small_nt / _nn / _tn):
+ *   out[M, N] (+)= act(P + bias),  bias fp32 [N] or NULL, act = 0 none | 1 tanh | 2 relu, accumulate != 0 adds to what out holds (else overwrites);
+ *   mode 0 (NT): P = A[M, K] W[N, K]^T, lda >= K, ldw >= K, A of type a_dtype = MMHIP_BF16 | MMHIP_F16 | MMHIP_F32;
+ *   mode 1 (NN): P = A[M, K] W[K, N],   lda >= K, ldw >= N, fp32 A;
+ *   mode 2 (TN): P = A[K, M]^T W[K, N], lda >= M, ldw >= N, fp32 A: the reduction runs over the K ROWS of both operands (launch_small_tn takes that
+ *                length as its M and the output's row count as n_rows; here M, N are always the output's shape and K the reduction length).
+ * W and out are fp32, ldo >= N; leading dimensions in elements.  No alignment is required (16-byte loads are taken per lane where the address allows).
+ * MMHIP_E_INVALID before the launch: A, W or out NULL, M / N / K < 1, a leading dimension shorter than the row it strides, another mode, act or
+ * a_dtype, a 16-bit A outside mode 0.
+ * mmhip_op_bias_grad_f32: out[c] (+)= sum_r d[r * ld + c], fp32 [rows, cols] (csrc/heads.hip bias_grad_f32_kernel); MMHIP_E_INVALID for a NULL
+ * tensor, rows < 1, cols < 1, ld < cols. */
+int mmhip_op_small_gemm(int mode, int a_dtype, const void* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldo, int M, int N,
+                        int K, int act, int accumulate, void* stream);
+int mmhip_op_bias_grad_f32(const float* d, int rows, int cols, int ld, float* out, int accumulate, void* stream);
 int mmhip_op_colsum(int dtype, const void* x, int rows, int cols, int ld, float* out, void* stream);
 int mmhip_op_cast(int dtype, const float* src, void* dst, uint64_t n, int transpose_rows, int transpose_cols, void* stream);
 /* Which kernel ran: what the GEMM launchers actually launched for the CALLING THREAD's most recent NT (which = 0: mmhip_op_gemm_nt and every NT product

@@ -140,6 +140,11 @@ _SIGS = {
     "mmhip_op_itc_bwd": (I, [P, P, P, P, P, P, P, I, I, P, P, P, P]),
     "mmhip_op_itc_global_fwd": (I, [P, P, P, I, I, P, P, P, P, P, U64, P]),
     "mmhip_op_itc_global_bwd": (I, [P, P, P, P, P, I, I, I, I, F, P, P, P, P, P, P, P, P, U64, P]),
+    "mmhip_op_fusion_attn_fwd": (I, [I, P, P, I, I, I, I, F, P, P, P]),
+    "mmhip_op_fusion_attn_bwd": (I, [I, P, P, P, I, I, I, I, F, P, P]),
+    "mmhip_op_loss": (I, [P, P, P, P, P, P, P, F, F, F, I, I, P, P, P, P, P, P]),
+    "mmhip_op_small_gemm": (I, [I, I, P, I, P, I, P, P, I, I, I, I, I, I, P]),
+    "mmhip_op_bias_grad_f32": (I, [P, I, I, I, P, I, P]),
     "mmhip_op_colsum": (I, [I, P, I, I, I, P, P]),
     "mmhip_op_cast": (I, [I, P, P, U64, I, I, P]),
     "mmhip_op_probe_layouts": (I, [P, P]),

@@ -362,6 +362,58 @@ int mmhip_op_itc_bwd(const float* d_logits, const float* logits, const float* tx
     CHECK_HIP(launch_itc_bwd(a, (hipStream_t)stream));
     return 0;
 }
+// ------------------------------------------------------------------------------------------------ the late-fusion head's other kernels, alone
+static bool fusion_attn_args_ok(int dtype, const void* rows32, const void* xv, const void* o1, const void* o2, int Bt, int B, int P, int H) {
+    if (!rows32 || !xv || !o1 || !o2 || B < 1 || Bt < 1 || P < 1 || P > 512 || H < 4 || H > 1024 || H % 4) return false;
+    if (dtype != MMHIP_BF16 && dtype != MMHIP_F16 && dtype != MMHIP_F32) return false;
+    return !(((uintptr_t)rows32 | (uintptr_t)xv) & 15);
+}
+int mmhip_op_fusion_attn_fwd(int dtype, const float* qk, const void* xv, int Bt, int B, int P, int H, float scale, float* prob, float* xbar, void* stream) {
+    if (!fusion_attn_args_ok(dtype, qk, xv, prob, xbar, Bt, B, P, H)) return MMHIP_E_INVALID;
+    FusionAttnArgs a{qk, xv, prob, xbar, Bt, B, P, H, scale};
+    CHECK_HIP(launch_fusion_attn_fwd(a, dtype, (hipStream_t)stream));
+    return 0;
+}
+int mmhip_op_fusion_attn_bwd(int dtype, const float* dxbar, const float* prob, const void* xv, int Bt, int B, int P, int H, float scale, float* dqk,
+                             void* stream) {
+    if (!fusion_attn_args_ok(dtype, dxbar, xv, prob, dqk, Bt, B, P, H)) return MMHIP_E_INVALID;
+    FusionAttnBwdArgs a{dxbar, prob, xv, dqk, Bt, B, P, H, scale};
+    CHECK_HIP(launch_fusion_attn_bwd(a, dtype, (hipStream_t)stream));
+    return 0;
+}
+int mmhip_op_loss(const float* out_cls, const int64_t* onehot, const float* class_w, const float* logits_per_text, const float* itc_global_loss,
+                  const float* out_tim, const int64_t* lbl_tim, float w_cls, float w_itc, float w_itm, int B, int C, float* loss, float* d_out_cls,
+                  float* d_logits, float* d_out_tim, int32_t* n_correct, void* stream) {
+    if (!out_cls || !onehot || !loss || B < 1 || B > 1024 || C < 1) return MMHIP_E_INVALID;
+    if ((out_tim && !lbl_tim) || (logits_per_text && itc_global_loss)) return MMHIP_E_INVALID;
+    LossArgs a{};
+    a.out_cls = out_cls; a.onehot = onehot; a.class_w = class_w; a.logits_per_text = logits_per_text; a.itc_global_loss = itc_global_loss;
+    a.out_tim = out_tim; a.lbl_tim = lbl_tim; a.w_cls = w_cls; a.w_itc = w_itc; a.w_itm = w_itm; a.loss = loss;
+    a.d_out_cls = d_out_cls; a.d_logits = d_logits; a.d_out_tim = d_out_tim; a.n_correct = n_correct; a.B = B; a.C = C;
+    CHECK_HIP(launch_loss(a, (hipStream_t)stream));
+    return 0;
+}
+int mmhip_op_small_gemm(int mode, int a_dtype, const void* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldo, int M, int N,
+                        int K, int act, int accumulate, void* stream) {
+    if (!A || !W || !out || M < 1 || N < 1 || K < 1 || mode < 0 || mode > 2 || ldo < N) return MMHIP_E_INVALID;
+    if (act != ACT_NONE && act != ACT_TANH && act != ACT_RELU) return MMHIP_E_INVALID;
+    if (a_dtype != MMHIP_F32 && (mode != 0 || (a_dtype != MMHIP_BF16 && a_dtype != MMHIP_F16))) return MMHIP_E_INVALID;
+    if (lda < (mode == 2 ? M : K) || ldw < (mode == 0 ? K : N)) return MMHIP_E_INVALID;
+    SmallGemmArgs g{};
+    g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.out = out; g.ldo = ldo; g.M = M; g.N = N; g.K = K; g.act = act; g.accumulate = accumulate ? 1 : 0;
+    if (mode == 0) CHECK_HIP(launch_small_nt(g, a_dtype, (hipStream_t)stream));
+    else if (mode == 1) CHECK_HIP(launch_small_nn(g, (hipStream_t)stream));
+    else {
+        g.M = K;          // launch_small_tn: the reduction length goes in as M, the output's rows as n_rows
+        CHECK_HIP(launch_small_tn(g, DT_F32, M, (hipStream_t)stream));
+    }
+    return 0;
+}
+int mmhip_op_bias_grad_f32(const float* d, int rows, int cols, int ld, float* out, int accumulate, void* stream) {
+    if (!d || !out || rows < 1 || cols < 1 || ld < cols) return MMHIP_E_INVALID;
+    CHECK_HIP(launch_bias_grad_f32(d, rows, cols, ld, out, accumulate, (hipStream_t)stream));
+    return 0;
+}
 // ------------------------------------------------------------------------------------------------ global-batch ITC
 uint64_t mmhip_op_itc_global_ws_bytes(int G, int B_local) {
     if (G < 1 || G > ITC_GLOBAL_MAX_G || B_local < 1 || B_local > G) return 0;

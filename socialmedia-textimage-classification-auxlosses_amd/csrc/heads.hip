@@ -523,11 +523,9 @@ __global__ __launch_bounds__(256) void adamw_kernel(AdamWArgs a) {
         reinterpret_cast<f32x4*>(a.v)[i] = v;
         if (a.zero_grad) reinterpret_cast<f32x4*>(a.g)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    if (bad && a.nonfinite) atomicAdd(a.nonfinite, 1u);
-    if (blockIdx.x == 0 && threadIdx.x < (a.n & 3)) {
+    if (blockIdx.x == 0 && threadIdx.x < (a.n & 3)) {          // the n & 3 tail: its non-finite elements count with the thread's others
         const size_t i = n4 * 4 + threadIdx.x;
-        bool bad1 = false;
-        const float ge = guard_finite(a.g[i] * a.grad_scale, bad1);
+        const float ge = guard_finite(a.g[i] * a.grad_scale, bad);
         float p = a.p[i] * decay;
         const float m = a.m[i] + one_m_b1 * (ge - a.m[i]);
         const float v = a.v[i] * a.beta2 + one_m_b2 * ge * ge;
@@ -535,6 +533,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(AdamWArgs a) {
         a.p[i] = p; a.m[i] = m; a.v[i] = v;
         if (a.zero_grad) a.g[i] = 0.f;
     }
+    if (bad && a.nonfinite) atomicAdd(a.nonfinite, 1u);
 }
 
 // ------------------------------------------------------------------------------------------------ launchers
