@@ -32,7 +32,17 @@ enum { MMHIP_BF16 = 0, MMHIP_F16 = 1, MMHIP_F32 = 2, MMHIP_BF16X3 = 2,
        MMHIP_PAIR = 3 };   /* op-level entry points that say so only: the parity mode's tensors as the engine stores them -- bf16 PLANE PAIRS, a row of W values =
                               [hi = bf16(x) (W) | lo = bf16(x - hi) (W)], the same bytes as the fp32 row (csrc/mmhip_kernels.h) */
 enum { MMHIP_TXT_BERT = 0, MMHIP_TXT_XLMR = 1 };
-enum { MMHIP_IMG_VIT = 0, MMHIP_IMG_CLIP = 1 };   /* HF ViTModel | HF CLIPVisionModel (pre-LN, quick-GELU, bias-free patch conv, pre_layrnorm) */
+enum { MMHIP_IMG_VIT = 0, MMHIP_IMG_CLIP = 1,     /* HF ViTModel | HF CLIPVisionModel (pre-LN, quick-GELU, bias-free patch conv, pre_layrnorm) */
+       MMHIP_IMG_BEIT = 2 };
+/* MMHIP_IMG_BEIT: HF BeitModel as microsoft/beit-base-patch16-224-pt22k-ft22k configures it (--img_model_name beit): no absolute position embeddings, a
+ * relative position bias per layer and head added to the scaled scores, a key projection without bias, layer scale (lambda_1 / lambda_2) on both
+ * residual branches, last_hidden_state = the encoder output (no final LayerNorm), pooler_output = LayerNorm(mean of the patch tokens).  Parameters
+ * under dual_encoder.vision_model.* in 4.25.1 naming, all MMHIP_G_FROZEN; the key bias HF does not have is an unnamed zero slot of the frozen buffer
+ * (never in mmhip_param_info_at; cleared by mmhip_refresh_weights).  mmhip_refresh_weights(which & 1) folds the layer scales into the 16-bit operand
+ * copies and expands every layer's bias table into an fp32 image [heads][P][P rounded up to 4].  At most 224 image tokens; in MMHIP_BF16X3 the
+ * attention with the bias exists on the matrix cores only, so mmhip_create answers MMHIP_E_INVALID under MMHIP_X3_FAST=0; the existing rules on
+ * tower widths hold (attention / aspect-att: equal widths).  Stochastic depth: mmhip_set_drop_path.  Handles of the other two kinds keep every name,
+ * offset, group and workspace size. */
 /* MMHIP_FUSION_ASPECT = 2: --fusion_name aspect-att (models/mm_late.py:115-131): V = reshape(stack(t_pool, v_pool), [B, 2, H]) -- slot j of post n is
  * row 2 n + j of [t_pool; v_pool], a reshape and not a transpose, so only B = 1 pairs a post's own text and image; reproduced as it is -- then
  * relu(softmax_j(tanh(V a + b)) . V).  Such a handle needs equally wide towers (mmhip_create: MMHIP_E_INVALID otherwise) and has its own parameter
@@ -224,6 +234,13 @@ int mmhip_set_index_counter(mmhip_handle h, uint32_t* device_word);
  * three.  Measured gradient bounds per setting: DESIGN.md section 4c.  Env MMHIP_X3_BWD=n sets the default at mmhip_create.
  * Returns MMHIP_E_STATE for products != 3 on a handle of another dtype. */
 int mmhip_set_backward_products(mmhip_handle h, int products);
+/* MMHIP_IMG_BEIT handles only (any other: MMHIP_E_INVALID; so is a rate outside [0, 1)): stochastic depth of the frozen image tower, HF
+ * drop_path_rate.  The reference puts the whole module in train mode, so its frozen BEiT tower drops residual branches while training; reproduced.
+ * Layer l takes p_l = linspace(0, rate, layers_img)[l]; in a training forward (train != 0) with p_l > 0 each of the layer's two residual branches
+ * is dropped for a whole post with probability p_l (threshold round(p_l * 65536) on 16 bits of the engine's hash: stream 0x1000 + 2 l + branch,
+ * element index = the post's row in the batch, the forward's seed) and a kept branch is scaled by the matching 1 / (1 - p_l).  Default 0: off.
+ * The ITM pass reuses the first pass's image tokens -- one set of draws per step, where the reference's second encoder call draws again. */
+int mmhip_set_drop_path(mmhip_handle h, float rate);
 
 /* ---- one whole training step of MMLate_Model.train (models/mm_late.py:452-491: zero_grad, forward, loss mix, backward,
  * optimizer.step) in ONE call: mmhip_forward(train) + mmhip_loss + mmhip_backward + AdamW over exactly the parameter ranges
@@ -389,6 +406,21 @@ int mmhip_op_attn_fwd(int dtype, const void* qkv, const float* maskbias, void* c
                       float p_drop, uint64_t seed, uint32_t stream_id, void* stream);
 int mmhip_op_attn_bwd(int dtype, const void* qkv, const float* maskbias, const void* ctx, const void* dctx, const float* lse,
                       void* dqkv, int posts, int S, int heads, float p_drop, uint64_t seed, uint32_t stream_id, void* stream);
+/* Self-attention forward with a per-head additive score bias (BEiT's relative position bias): softmax(q k^T / 8 + bias2d[head]) v.  bias2d fp32
+ * [heads][S][ld_bias] in natural units, the same for every post; qkv / ctx / lse as mmhip_op_attn_fwd takes them, dtype MMHIP_BF16 | MMHIP_F16 |
+ * MMHIP_F32 (parity mode, fp32 tensors) | MMHIP_PAIR; no key mask, no dropout.  Columns S .. ld_bias-1 of a bias row are read and must be finite.
+ * MMHIP_E_INVALID / hipErrorInvalidValue before any launch, nothing written: a NULL tensor, S < 1 or > 224, ld_bias % 4 != 0, ld_bias < S, bias2d off
+ * 16-byte alignment, another dtype. */
+int mmhip_op_attn_fwd_bias(int dtype, const void* qkv, const float* bias2d, int ld_bias, void* ctx, float* lse, int posts, int S, int heads, void* stream);
+/* out fp32 [heads][P][ld_bias], P = window_h * window_w + 1: out[h][i][j] = table[index(i, j)][h] with HF BeitRelativePositionBias's index (computed on
+ * the device from the window geometry); table fp32 [(2 window_h - 1)(2 window_w - 1) + 3, heads]; columns P .. ld_bias-1 are written as zeros.
+ * MMHIP_E_INVALID: a NULL pointer, heads / window_h / window_w < 1, ld_bias < P. */
+int mmhip_op_beit_bias_image(const float* table, int heads, int window_h, int window_w, float* out, int ld_bias, void* stream);
+/* BEiT's pooler: out fp32 [posts, width] = LayerNorm(mean over rows 1 .. rows_per_post-1 of each post's [rows_per_post, width] block of x) -- row 0,
+ * the CLS token, is not part of the mean.  x in `dtype` (MMHIP_BF16 | MMHIP_F16 | MMHIP_F32), fp32 sums in token order: the same bits on every call.
+ * MMHIP_E_INVALID: a NULL pointer, posts < 1, rows_per_post < 2, width % 4 != 0 or > 1024, another dtype. */
+int mmhip_op_patch_mean_ln(int dtype, const void* x, int rows_per_post, int posts, int width, const float* gamma, const float* beta, float eps, float* out,
+                           void* stream);
 /* Self-attention backward at image length: 129 <= S <= 288 keys (ViT-B/16: 197, CLIP-ViT-L/14 @224: 257), head dimension 64, every matrix product on
  * the matrix cores in all four forms -- MMHIP_BF16, MMHIP_F16, MMHIP_F32 (parity mode on fp32 tensors, three bf16 products per matrix product) and
  * MMHIP_PAIR (the same on plane pairs).  Arguments, shapes and layouts are mmhip_op_attn_bwd's: qkv and dqkv [posts*S, 3*heads*64] packed q|k|v (pairs:

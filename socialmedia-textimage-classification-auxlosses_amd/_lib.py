@@ -11,7 +11,7 @@ BF16X3 = 2          # as an engine dtype: the strict-parity mode (fp32 activatio
 PAIR = 3            # op-level entry points that say so only: the parity mode's tensors as bf16 plane pairs (MMHIP_PAIR)
 TXT_BERT, TXT_XLMR = 0, 1
 FUSION_CONCAT, FUSION_ATTENTION, FUSION_ASPECT = 0, 1, 2      # include/mmhip.h MMHIP_FUSION_*: concat | attention | aspect-att
-IMG_VIT, IMG_CLIP = 0, 1
+IMG_VIT, IMG_CLIP, IMG_BEIT = 0, 1, 2
 G_NEVER, G_ITC, G_ITM, G_FUSION_ATT, G_ALWAYS, G_FROZEN = range(6)
 
 
@@ -105,6 +105,7 @@ _SIGS = {
     "mmhip_adamw_rows_guarded": (I, [P, P, P, P, I, I, P, F, F, F, F, F, I, F, I, P, P]),
     "mmhip_set_loss_scale": (I, [P, F]),
     "mmhip_set_backward_products": (I, [P, I]),
+    "mmhip_set_drop_path": (I, [P, F]),
     "mmhip_side_stream": (P, [P]),
     "mmhip_set_index_counter": (I, [P, P]),
     "mmhip_early_set_index_counter": (I, [P, P]),
@@ -134,6 +135,9 @@ _SIGS = {
     "mmhip_op_layernorm_bwd": (I, [I, P, P, P, P, P, P, P, P, P, I, I, P]),
     "mmhip_op_attn_fwd": (I, [I, P, P, P, P, I, I, I, F, U64, U32, P]),
     "mmhip_op_attn_bwd": (I, [I, P, P, P, P, P, P, I, I, I, F, U64, U32, P]),
+    "mmhip_op_attn_fwd_bias": (I, [I, P, P, I, P, P, I, I, I, P]),
+    "mmhip_op_beit_bias_image": (I, [P, I, I, I, P, I, P]),
+    "mmhip_op_patch_mean_ln": (I, [I, P, I, I, I, P, P, F, P, P]),
     "mmhip_op_attn_bwd_long": (I, [I, P, P, P, P, P, P, I, I, I, F, U64, U32, P]),
     "mmhip_op_itc_global_ws_bytes": (U64, [I, I]),
     "mmhip_op_itc_fwd": (I, [P, P, P, I, I, P, P, P, P, P, P]),

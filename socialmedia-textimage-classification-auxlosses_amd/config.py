@@ -43,7 +43,10 @@ TEXT_ARCH = {
 }
 # "clip" / "clip336" (additive; BASELINE config 4): CLIP-ViT-L/14 vision tower, HF CLIPVisionModel -- 1024 wide, 16 heads, 4096 MLP,
 # 24 pre-LN layers, quick-GELU, 14 x 14 patches (257 tokens at 224, 577 at 336: openai/clip-vit-large-patch14[-336])
+# "beit": HF BeitModel as microsoft/beit-base-patch16-224-pt22k-ft22k configures it (reference models/config.py:145) -- relative position bias per
+# layer, no absolute positions, mean pooling, layer scale 0.1, stochastic depth 0.1 (on in the reference's training: the whole module is in train mode)
 IMAGE_ARCH = {"vit": dict(image=224, patch=16, ln_eps_img=1e-12, img_kind="vit"),
+              "beit": dict(image=224, patch=16, ln_eps_img=1e-12, img_kind="beit", drop_path_rate=0.1, layer_scale_init_value=0.1),
               "clip": dict(image=224, patch=14, ln_eps_img=1e-5, img_kind="clip", hidden_img=1024, heads_img=16, inter_img=4096, layers_img=24),
               "clip336": dict(image=336, patch=14, ln_eps_img=1e-5, img_kind="clip", hidden_img=1024, heads_img=16, inter_img=4096, layers_img=24)}
 

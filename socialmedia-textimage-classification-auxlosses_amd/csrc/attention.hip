@@ -59,8 +59,15 @@ __device__ __forceinline__ void stage_image(char* img, const T* src, int ld, int
 // score tile live at a time (~100 VGPRs -> 4 waves per SIMD) instead of all of them (490 VGPRs, 1 wave per SIMD).
 // DROP (compile time, so that neither instance branches per element): 0 = no dropout, 1 = one hash per element, 2 = one hash per PAIR of
 // consecutive keys (S even: the element index of an even key is even, mm_keep2)
-template <typename T, int NKT, int NW, int DROP>
-__global__ __launch_bounds__(NW * 64, 4) void attn_fwd_kernel(AttnArgs a) {
+// A = AttnBiasArgs (compile time): a per-head additive score bias bias2d[head][query][key] (BEiT's relative position bias), added after the
+// scaling.  The lane of query q reads its row's four consecutive keys of every 8-key group as one 16-byte load; the four loads of a score tile
+// are issued before the tile's MFMAs.  Addresses are clamped into the row (never a branch around a load): keys past ld_bias lie past Sk, where mb
+// is -inf.  A = AttnArgs compiles to the kernel without the bias, on its own argument block.
+template <typename A> struct HasBias { static constexpr bool value = false; };
+template <> struct HasBias<AttnBiasArgs> { static constexpr bool value = true; };
+template <typename T, int NKT, int NW, int DROP, typename A = AttnArgs>
+__global__ __launch_bounds__(NW * 64, 4) void attn_fwd_kernel(A a) {
+    constexpr bool BIAS = HasBias<A>::value;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     typedef typename Vec<T>::v8 v8;
     typedef typename Vec<T>::v4 v4;
@@ -94,10 +101,20 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_kernel(AttnArgs a) {
 #pragma unroll
         for (int s = 0; s < 4; ++s) qf[s] = *reinterpret_cast<const v8*>(qp + 16 * s);
         const uint32_t ebase = (uint32_t)(((size_t)post * a.heads + head) * S + (uint32_t)qrow) * (uint32_t)S;
+        // the head's bias at a uniform base, this lane's query row as a 32-bit element offset (one scalar base + one offset register per load)
+        const float* bhead = nullptr;
+        uint32_t brow = 0;
+        if constexpr (BIAS) { bhead = a.bias2d + (size_t)head * S * a.ld_bias; brow = (uint32_t)qrow * (uint32_t)a.ld_bias; }
         float m_run = -INFINITY, l_run = 0.f;
         f32x16 oacc[2] = {f32x16{}, f32x16{}};
 #pragma unroll 1
         for (int kt = 0; kt < nkt; ++kt) {
+            f32x4 b2[4];
+            if constexpr (BIAS) {
+#pragma unroll
+                for (int g = 0; g < 4; ++g) b2[g] = *reinterpret_cast<const f32x4*>(bhead + (brow + (uint32_t)min(kt * 32 + 8 * g + 4 * h2, a.ld_bias - 4)));
+                __builtin_amdgcn_sched_barrier(0);      // the loads stay in front of the MFMAs that hide them (the scheduler sinks them to their use otherwise)
+            }
             // S^T tile: acc[reg] = score(key = kt*32 + (reg&3) + 8*(reg>>2) + 4*h2, query q)
             f32x16 acc = f32x16{};
 #pragma unroll
@@ -111,7 +128,8 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_fwd_kernel(AttnArgs a) {
                 f32x4 b = *reinterpret_cast<const f32x4*>(mb + kt * 32 + 8 * g + 4 * h2);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float v = acc[4 * g + e] * sc + b[e];
+                    float v = acc[4 * g + e] * sc + b[e];
+                    if constexpr (BIAS) v = fmaf(b2[g][e], LOG2E, v);
                     acc[4 * g + e] = v;
                     tmax = fmaxf(tmax, v);
                 }
@@ -426,8 +444,9 @@ __device__ __forceinline__ Frag3 global_pair(const float* p) {
     return split8(v);
 }
 
-template <int NKT, int NW, bool PAIR>
-__global__ __launch_bounds__(NW * 64) void attn_fwd_x3_kernel(AttnArgs a) {
+template <int NKT, int NW, bool PAIR, typename A = AttnArgs>          // A = AttnBiasArgs: as in attn_fwd_kernel
+__global__ __launch_bounds__(NW * 64) void attn_fwd_x3_kernel(A a) {
+    constexpr bool BIAS = HasBias<A>::value;
     typedef X3IO<PAIR> IO;
     typedef typename IO::elem E;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -464,10 +483,20 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_x3_kernel(AttnArgs a) {
 #pragma unroll
         for (int s = 0; s < 4; ++s) qf[s] = IO::frag(qp + 16 * s, a.lo_qkv);
         const uint32_t ebase = (uint32_t)(((size_t)post * a.heads + head) * S + (uint32_t)qrow) * (uint32_t)S;
+        // the head's bias at a uniform base, this lane's query row as a 32-bit element offset (one scalar base + one offset register per load)
+        const float* bhead = nullptr;
+        uint32_t brow = 0;
+        if constexpr (BIAS) { bhead = a.bias2d + (size_t)head * S * a.ld_bias; brow = (uint32_t)qrow * (uint32_t)a.ld_bias; }
         float m_run = -INFINITY, l_run = 0.f;
         f32x16 oacc[2] = {f32x16{}, f32x16{}};
 #pragma unroll 1
         for (int kt = 0; kt < nkt; ++kt) {
+            f32x4 b2[4];
+            if constexpr (BIAS) {
+#pragma unroll
+                for (int g = 0; g < 4; ++g) b2[g] = *reinterpret_cast<const f32x4*>(bhead + (brow + (uint32_t)min(kt * 32 + 8 * g + 4 * h2, a.ld_bias - 4)));
+                __builtin_amdgcn_sched_barrier(0);      // the loads stay in front of the MFMAs that hide them (the scheduler sinks them to their use otherwise)
+            }
             f32x16 acc = f32x16{};
 #pragma unroll
             for (int s = 0; s < 4; ++s) acc = mma3_32(lds_pair(Kh, Kl, rowimg_off(kt * 32 + r, 2 * s + h2)), qf[s], acc);
@@ -477,7 +506,8 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_x3_kernel(AttnArgs a) {
                 f32x4 b = *reinterpret_cast<const f32x4*>(mb + kt * 32 + 8 * g + 4 * h2);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float v = acc[4 * g + e] * sc + b[e];
+                    float v = acc[4 * g + e] * sc + b[e];
+                    if constexpr (BIAS) v = fmaf(b2[g][e], LOG2E, v);
                     acc[4 * g + e] = v;
                     tmax = fmaxf(tmax, v);
                 }
@@ -898,6 +928,53 @@ static bool x3_mfma_attention() {
     static int on = -1;
     if (on < 0) { const char* e = getenv("MMHIP_X3_FAST"); on = e ? atoi(e) : 1; }
     return on != 0;
+}
+// ---- forward with a per-head 2-D score bias (AttnBiasArgs): its own instantiations, S <= 224, no dropout
+template <typename T, int NKT, int NW>
+static void launch_fwd_bias_t(const AttnBiasArgs& a, hipStream_t s) {
+    const int lds = 2 * NKT * 32 * 128 + NKT * 32 * 4;
+    static bool done = false;
+    if (!done) { (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<T, NKT, NW, 0, AttnBiasArgs>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); done = true; }
+    hipLaunchKernelGGL((attn_fwd_kernel<T, NKT, NW, 0, AttnBiasArgs>), dim3(a.heads, a.posts), dim3(NW * 64), lds, s, a);
+}
+template <int NKT, int NW>
+static void launch_fwd_x3_bias_t(const AttnBiasArgs& a, hipStream_t s) {
+    const int lds = 4 * NKT * 32 * 128 + NKT * 32 * 4;
+    static bool done[2] = {false, false};
+    if (a.pair) {
+        if (!done[1]) { (void)hipFuncSetAttribute((const void*)attn_fwd_x3_kernel<NKT, NW, true, AttnBiasArgs>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); done[1] = true; }
+        hipLaunchKernelGGL((attn_fwd_x3_kernel<NKT, NW, true, AttnBiasArgs>), dim3(a.heads, a.posts), dim3(NW * 64), lds, s, a);
+    } else {
+        if (!done[0]) { (void)hipFuncSetAttribute((const void*)attn_fwd_x3_kernel<NKT, NW, false, AttnBiasArgs>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); done[0] = true; }
+        hipLaunchKernelGGL((attn_fwd_x3_kernel<NKT, NW, false, AttnBiasArgs>), dim3(a.heads, a.posts), dim3(NW * 64), lds, s, a);
+    }
+}
+template <typename T>
+static void launch_fwd_bias_d(const AttnBiasArgs& a, hipStream_t s) {
+    if (a.S <= 32) launch_fwd_bias_t<T, 1, 1>(a, s);
+    else if (a.S <= 64) launch_fwd_bias_t<T, 2, 2>(a, s);
+    else if (a.S <= 128) launch_fwd_bias_t<T, 4, 4>(a, s);
+    else launch_fwd_bias_t<T, 7, 8>(a, s);
+}
+static constexpr int BIAS_MAX_S = 224;
+hipError_t launch_attn_fwd_bias(const AttnBiasArgs& a, int dtype, hipStream_t s) {
+    if (a.hidden != a.heads * HD || a.ld_qkv % 8 || a.ld_ctx % 8 || a.S < 1 || a.S > BIAS_MAX_S) return hipErrorInvalidValue;
+    const bool cross = a.Sq_live > 0 || a.Sk_live > 0 || a.q_rps > 0 || a.kv_rps > 0 || a.ctx_rps > 0;
+    // a row stride that is no multiple of 4 floats or shorter than the row, a bias off 16-byte alignment (the lane's four keys are one 16-byte
+    // load), cross attention, dropout: no instantiation stands behind any of them
+    if (!a.bias2d || a.ld_bias % 4 || a.ld_bias < a.S || ((uintptr_t)a.bias2d & 15) || cross || a.drop.thresh16) return hipErrorInvalidValue;
+    if (dtype == DT_F32) {
+        if (!x3_mfma_attention() || ((uintptr_t)a.qkv & 15) || ((uintptr_t)a.ctx & 15)) return hipErrorInvalidValue;
+        if (a.S <= 32) launch_fwd_x3_bias_t<1, 1>(a, s);
+        else if (a.S <= 64) launch_fwd_x3_bias_t<2, 2>(a, s);
+        else if (a.S <= 128) launch_fwd_x3_bias_t<4, 4>(a, s);
+        else launch_fwd_x3_bias_t<7, 8>(a, s);
+        return hipGetLastError();
+    }
+    if (dtype == DT_BF16) launch_fwd_bias_d<bf16_t>(a, s);
+    else if (dtype == DT_F16) launch_fwd_bias_d<f16_t>(a, s);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
 }
 hipError_t launch_attn_fwd(const AttnArgs& a, int dtype, hipStream_t s) {
     if (a.hidden != a.heads * HD || a.ld_qkv % 8 || a.ld_ctx % 8 || a.S < 1 || a.Sq_live > a.S || a.Sk_live > a.S) return hipErrorInvalidValue;

@@ -316,6 +316,26 @@ int mmhip_op_attn_fwd(int dtype, const void* qkv, const float* maskbias, void* c
     CHECK_HIP(launch_attn_fwd(a, dtype, (hipStream_t)stream));
     return 0;
 }
+int mmhip_op_attn_fwd_bias(int dtype, const void* qkv, const float* bias2d, int ld_bias, void* ctx, float* lse, int posts, int S, int heads, void* stream) {
+    if (!qkv || !bias2d || !ctx || posts < 1 || S < 1 || heads < 1) return MMHIP_E_INVALID;
+    if (dtype != MMHIP_BF16 && dtype != MMHIP_F16 && dtype != MMHIP_F32 && dtype != MMHIP_PAIR) return MMHIP_E_INVALID;
+    AttnArgs a = attn_args(qkv, nullptr, ctx, lse, posts, S, heads, heads * 64);
+    if (dtype == MMHIP_PAIR) { attn_pair(a, true); dtype = MMHIP_F32; }
+    CHECK_HIP(launch_attn_fwd_bias(attn_bias(a, bias2d, ld_bias), dtype, (hipStream_t)stream));
+    return 0;
+}
+int mmhip_op_beit_bias_image(const float* table, int heads, int window_h, int window_w, float* out, int ld_bias, void* stream) {
+    if (!table || !out || heads < 1 || window_h < 1 || window_w < 1 || ld_bias < window_h * window_w + 1) return MMHIP_E_INVALID;
+    CHECK_HIP(launch_beit_bias_image(table, heads, window_h, window_w, out, ld_bias, (hipStream_t)stream));
+    return 0;
+}
+int mmhip_op_patch_mean_ln(int dtype, const void* x, int rows_per_post, int posts, int width, const float* gamma, const float* beta, float eps, float* out,
+                           void* stream) {
+    if (!x || !gamma || !beta || !out || posts < 1 || rows_per_post < 2 || width < 4 || width % 4 || width > 1024) return MMHIP_E_INVALID;
+    if (dtype != MMHIP_BF16 && dtype != MMHIP_F16 && dtype != MMHIP_F32) return MMHIP_E_INVALID;
+    CHECK_HIP(launch_patch_mean_ln(x, rows_per_post, posts, width, gamma, beta, eps, out, dtype, (hipStream_t)stream));
+    return 0;
+}
 int mmhip_op_attn_bwd(int dtype, const void* qkv, const float* maskbias, const void* ctx, const void* dctx, const float* lse,
                       void* dqkv, int posts, int S, int heads, float p_drop, uint64_t seed, uint32_t stream_id, void* stream) {
     if (!qkv || !ctx || !dctx || !lse || !dqkv || posts < 1 || S < 1 || heads < 1) return MMHIP_E_INVALID;

@@ -14,6 +14,11 @@ namespace {
 
 struct LayerOff {   // element offsets into a flat fp32 buffer
     size_t qkv_w, qkv_b, ao_w, ao_b, ln1_w, ln1_b, fc1_w, fc1_b, fc2_w, fc2_b, ln2_w, ln2_b, begin, end;
+    size_t rel_table, lambda1, lambda2;      // BEiT layers only: relative position bias table, the two layer scales
+};
+struct BeitWs {     // BEiT layer: what mmhip_refresh_weights derives beside the operand copies (byte offsets into the workspace)
+    size_t ao_b, fc2_b;      // fp32 [Hv]: lambda_1 * attention.output.dense.bias, lambda_2 * output.dense.bias
+    size_t bias;             // fp32 [heads][P][ldb]: the layer's relative position bias, expanded
 };
 struct LayerW16 {   // 16-bit GEMM operand copies (byte offsets into the workspace)
     size_t qkv, ao, fc1, fc2, qkvT, aoT, fc1T, fc2T;
@@ -152,6 +157,19 @@ struct mmhip_engine {
     int dt() const { return cfg.dtype; }
     // image tower geometry: its own width for CLIP-ViT-L/14 (BASELINE config 4), the text tower's otherwise
     bool clip() const { return cfg.img_kind == MMHIP_IMG_CLIP; }
+    // BEiT tower (HF BeitModel, MMHIP_IMG_BEIT): no position embeddings, a relative position bias per layer and head inside the attention, layer
+    // scale (folded into the 16-bit operand copies at refresh), a mean-pool pooler, and stochastic depth that the reference leaves on in train mode
+    bool beit() const { return cfg.img_kind == MMHIP_IMG_BEIT; }
+    std::vector<BeitWs> beit_ws;
+    size_t beit_fold = 0;        // refresh scratch, fp32 [Hv, Iv]: a weight with its layer scale folded in, before the cast
+    size_t beit_branch = 0;      // drop path: a residual branch [Mv, Hv] before its per-post scale is added to the stream
+    float drop_path = 0.f;       // mmhip_set_drop_path: the last layer's drop probability; layer l takes linspace(0, rate, L)[l]
+    int window() const { return cfg.image / cfg.patch; }
+    int ldb() const { return (P() + 3) & ~3; }          // row stride of the bias image: a lane's four consecutive keys are one aligned 16-byte load
+    float drop_path_p(int l) const {
+        const int L = cfg.layers_img;
+        return (train_mode && drop_path > 0.f && L > 1) ? drop_path * (float)l / (float)(L - 1) : 0.f;
+    }
     bool aspect() const { return cfg.fusion == MMHIP_FUSION_ASPECT; }
     int Hv() const { return cfg.hidden_img > 0 ? cfg.hidden_img : cfg.hidden; }
     int Iv() const { return cfg.inter_img > 0 ? cfg.inter_img : cfg.inter; }
@@ -171,9 +189,11 @@ namespace {
 // ------------------------------------------------------------------------------------------------ layout
 // One transformer layer's 16 parameters, per family: {key suffix, the LayerOff slot the row sets (none: key / value follow query, the fused QKV
 // operand reads the three as one [3H, H] block), shape}.  add_layer walks a table in its own order, so the table IS the layout of the layer.
-enum class Shape { HH, H, IH, I, HI };
+enum class Shape { HH, H, IH, I, HI,
+                   REL,      // BEiT: [(2W-1)^2 + 3, heads] relative position bias table
+                   PAD };    // H unnamed elements: no parameter, never in mmhip_param_info_at (BEiT: the key bias HF does not have, zero-filled at refresh)
 struct LayerKey { const char* suffix; size_t LayerOff::*slot; Shape shape; };
-struct LayerKeys { const char* stem; LayerKey rows[16]; };
+struct LayerKeys { const char* stem; LayerKey rows[20]; };      // rows past the last one have no suffix
 // BERT / XLM-R text layer (post-LN)
 const LayerKeys BERT_LAYER = {"encoder.layer.", {
     {"attention.self.query.weight", &LayerOff::qkv_w, Shape::HH}, {"attention.self.key.weight", nullptr, Shape::HH},
@@ -205,13 +225,29 @@ const LayerKeys VIT_LAYER = {"encoder.layer.", {
     {"output.dense.weight", &LayerOff::fc2_w, Shape::HI}, {"output.dense.bias", &LayerOff::fc2_b, Shape::H},
     {"layernorm_before.weight", &LayerOff::ln1_w, Shape::H}, {"layernorm_before.bias", &LayerOff::ln1_b, Shape::H},
     {"layernorm_after.weight", &LayerOff::ln2_w, Shape::H}, {"layernorm_after.bias", &LayerOff::ln2_b, Shape::H}}};
-// layer l of a tower under `prefix`, in buffer `buf` and group `g`
-void add_layer(ParamTable& b, const LayerKeys& keys, const std::string& prefix, int l, int buf, int g, int H, int I, LayerOff& o) {
+// HF BeitLayer, transformers 4.25.1 keys: the key projection has no bias -- the packed QKV GEMM reads one [3H] bias block, so an unnamed zero slot
+// stands where it would be -- a relative position bias table per layer (use_shared_relative_position_bias = False), two layer scales
+const LayerKeys BEIT_LAYER = {"encoder.layer.", {
+    {"attention.attention.query.weight", &LayerOff::qkv_w, Shape::HH}, {"attention.attention.key.weight", nullptr, Shape::HH},
+    {"attention.attention.value.weight", nullptr, Shape::HH}, {"attention.attention.query.bias", &LayerOff::qkv_b, Shape::H},
+    {"", nullptr, Shape::PAD}, {"attention.attention.value.bias", nullptr, Shape::H},
+    {"attention.attention.relative_position_bias.relative_position_bias_table", &LayerOff::rel_table, Shape::REL},
+    {"attention.output.dense.weight", &LayerOff::ao_w, Shape::HH}, {"attention.output.dense.bias", &LayerOff::ao_b, Shape::H},
+    {"intermediate.dense.weight", &LayerOff::fc1_w, Shape::IH}, {"intermediate.dense.bias", &LayerOff::fc1_b, Shape::I},
+    {"output.dense.weight", &LayerOff::fc2_w, Shape::HI}, {"output.dense.bias", &LayerOff::fc2_b, Shape::H},
+    {"lambda_1", &LayerOff::lambda1, Shape::H}, {"lambda_2", &LayerOff::lambda2, Shape::H},
+    {"layernorm_before.weight", &LayerOff::ln1_w, Shape::H}, {"layernorm_before.bias", &LayerOff::ln1_b, Shape::H},
+    {"layernorm_after.weight", &LayerOff::ln2_w, Shape::H}, {"layernorm_after.bias", &LayerOff::ln2_b, Shape::H}}};
+// layer l of a tower under `prefix`, in buffer `buf` and group `g`; rel_rows / heads: the shape of a Shape::REL row
+void add_layer(ParamTable& b, const LayerKeys& keys, const std::string& prefix, int l, int buf, int g, int H, int I, LayerOff& o, int rel_rows = 0, int heads = 0) {
     const std::string p = prefix + keys.stem + std::to_string(l) + ".";
     o.begin = b.off[buf];
     for (const LayerKey& k : keys.rows) {
+        if (!k.suffix) break;
         size_t at = 0;
         switch (k.shape) {
+            case Shape::REL: at = b.add(p + k.suffix, buf, g, {rel_rows, heads}); break;
+            case Shape::PAD: at = b.off[buf]; b.off[buf] += (size_t)H; break;          // (H % 4 == 0: the next tensor stays 16-byte aligned)
             case Shape::HH: at = b.add(p + k.suffix, buf, g, {H, H}); break;
             case Shape::H: at = b.add(p + k.suffix, buf, g, {H}); break;
             case Shape::IH: at = b.add(p + k.suffix, buf, g, {I, H}); break;
@@ -245,7 +281,20 @@ void build_layout(mmhip_engine& e) {
     ParamTable b{e.params};
     // ---- frozen: vision tower (every dual_encoder parameter with 'vision' in its name, mm_late.py:67-69)
     e.vit.resize(c.layers_img);
-    if (e.clip()) {
+    if (e.beit()) {
+        // HF BeitModel (models/beit/modeling_beit.py) as microsoft/beit-base-patch16-224-pt22k-ft22k configures it: no position embeddings, no final
+        // layernorm (Identity under mean pooling), the pooler is a LayerNorm over the mean of the patch tokens
+        const std::string vm = "dual_encoder.vision_model.";
+        const int W = e.window(), rel = (2 * W - 1) * (2 * W - 1) + 3;
+        e.v_cls = b.add(vm + "embeddings.cls_token", 0, MMHIP_G_FROZEN, {1, 1, Hv});
+        e.v_pos = 0;
+        e.v_patch_w = b.add(vm + "embeddings.patch_embeddings.projection.weight", 0, MMHIP_G_FROZEN, {Hv, 3, c.patch, c.patch});
+        e.v_patch_b = b.add(vm + "embeddings.patch_embeddings.projection.bias", 0, MMHIP_G_FROZEN, {Hv});
+        for (int l = 0; l < c.layers_img; ++l) add_layer(b, BEIT_LAYER, vm, l, 0, MMHIP_G_FROZEN, Hv, e.Iv(), e.vit[l], rel, e.heads_v());
+        e.v_ln_w = b.add(vm + "pooler.layernorm.weight", 0, MMHIP_G_FROZEN, {Hv});
+        e.v_ln_b = b.add(vm + "pooler.layernorm.bias", 0, MMHIP_G_FROZEN, {Hv});
+        e.v_pool_w = e.v_pool_b = 0;
+    } else if (e.clip()) {
         // HF CLIPVisionTransformer (models/clip/modeling_clip.py): class_embedding [Hv], bias-free patch conv, learned positions,
         // pre_layrnorm, pre-LN layers, post_layernorm on the pooled CLS row only
         const std::string vm = "dual_encoder.vision_model.vision_model.";
@@ -509,6 +558,12 @@ void build_workspace(mmhip_engine& e) {
     e.h_dz = f(Bt * (H + Hv)); e.h_dxcls = f(Bt * H); e.h_dxbar = f(Bt * H); e.h_dqk = f(Bt * H); e.h_dq = f(Bt * H);
     e.h_dtxt_e = f(Bm * E); e.h_dimg_e = f(Bm * E); e.h_dtpool = f(Bm * H); e.h_dprepool = f(Bm * H); e.h_loss = f(8);
     if (e.aspect()) { e.h_asp_w = f(Bm * 2); e.h_asp_e = f(Bm * 2); e.h_asp_partial = f(aspect_fusion_partial_floats((int)Bm, (int)H)); }
+    if (e.beit()) {      // a BEiT handle alone: every other handle keeps its workspace size
+        e.beit_ws.resize(c.layers_img);
+        for (auto& L : e.beit_ws) { L.ao_b = f(Hv); L.fc2_b = f(Hv); L.bias = f((size_t)e.heads_v() * P * e.ldb()); }
+        e.beit_fold = f(Hv * (Iv > Hv ? Iv : Hv));
+        e.beit_branch = w.take(Mv * Hv * Z);
+    }
     e.ws_need = e.ws_base = w.off;
 }
 
@@ -617,6 +672,28 @@ int refresh_layer(mmhip_engine& e, const float* base, const LayerOff& o, const L
     CHECK_HIP(launch_cast_group(m, 4, e.px ? DT_PAIR : e.dt(), s));
     return 0;
 }
+// BEiT layer l of the frozen tower.  The layer scales are folded into the operand copies in fp32, before the cast or the plane split:
+// Wo' = diag(lambda_1) Wo, bo' = lambda_1 * bo, likewise lambda_2 into FC2 -- the residual epilogues then add lambda * branch as they are and the fp32
+// masters stay as loaded.  The key bias slot is cleared, and the layer's bias table is expanded into its [heads][P][ldb] image.
+int refresh_layer_beit(mmhip_engine& e, int l, hipStream_t s) {
+    const float* F = e.frozen;
+    const LayerOff& o = e.vit[l]; const LayerW16& w = e.vit_w16[l]; const BeitWs& bw = e.beit_ws[l];
+    const int H = e.Hv(), I = e.Iv(), dt = e.px ? DT_PAIR : e.dt();
+    float* fold = e.wsp<float>(e.beit_fold);
+    CHECK_HIP(hipMemsetAsync(e.frozen + o.qkv_b + H, 0, (size_t)H * 4, s));
+    CastMat m[2] = {{F + o.qkv_w, e.ws + w.qkv, nullptr, 3 * H, H, 0}, {F + o.fc1_w, e.ws + w.fc1, nullptr, I, H, 0}};
+    CHECK_HIP(launch_cast_group(m, 2, dt, s));
+    CHECK_HIP(launch_scale_rows_f32(F + o.ao_w, F + o.lambda1, fold, H, H, s));
+    CastMat ao{fold, e.ws + w.ao, nullptr, H, H, 0};
+    CHECK_HIP(launch_cast_group(&ao, 1, dt, s));
+    CHECK_HIP(launch_scale_rows_f32(F + o.fc2_w, F + o.lambda2, fold, H, I, s));
+    CastMat fc2{fold, e.ws + w.fc2, nullptr, H, I, 0};
+    CHECK_HIP(launch_cast_group(&fc2, 1, dt, s));
+    CHECK_HIP(launch_scale_rows_f32(F + o.ao_b, F + o.lambda1, e.wsp<float>(bw.ao_b), H, 1, s));
+    CHECK_HIP(launch_scale_rows_f32(F + o.fc2_b, F + o.lambda2, e.wsp<float>(bw.fc2_b), H, 1, s));
+    CHECK_HIP(launch_beit_bias_image(F + o.rel_table, e.heads_v(), e.window(), e.window(), e.wsp<float>(bw.bias), e.ldb(), s));
+    return 0;
+}
 // patch-embedding weight [Hv, 3*p*p] of the tower whose parameters live in `base`, rows zero-padded to the GEMM's k-step (14 x 14 patches: 588 -> 640)
 int refresh_patch(mmhip_engine& e, const float* base, hipStream_t s) {
     CHECK_HIP(launch_cast_pad(base + e.v_patch_w, e.ws + e.patch_w16, e.Hv(), e.Kp(), e.Kpp(), e.px ? DT_PAIR : e.dt(), s));
@@ -712,7 +789,7 @@ int vit_embed(mmhip_engine& e, const float* pixels, hipStream_t s) {
     g.px_in(e.px);
     part_gemm(e, g, 1);
     CHECK_RC(run_gemm(e, g, s));
-    CHECK_HIP(launch_vit_assemble(e.ws + e.v_pe, F + e.v_cls, F + e.v_pos, x0, B, P, H, dt, s));
+    CHECK_HIP(launch_vit_assemble(e.ws + e.v_pe, F + e.v_cls, e.beit() ? nullptr : F + e.v_pos, x0, B, P, H, dt, s));      // BEiT: no absolute positions
     if (e.clip()) {
         LNArgs ln{x0, x0, F + e.v_pre_ln_w, F + e.v_pre_ln_b, nullptr, nullptr, B * P, H, H, H, c.ln_eps_img};
         CHECK_HIP(launch_layernorm_fwd(ln, dt, s));
@@ -745,11 +822,14 @@ struct ImageLayer {
     const LayerOff& o; const LayerW16& w;
     const ImageBufs b;
     const float* F;
-    const int H, I, Mv;
+    const int l, H, I, Mv;
     const bool px;
     ImageLayer(const mmhip_engine& e, int l) : ImageLayer(e, l, image_bufs_shared(e)) {}
     ImageLayer(const mmhip_engine& e, int l, const ImageBufs& b)
-        : e(e), o(e.vit[l]), w(e.vit_w16[l]), b(b), F(b.W), H(e.Hv()), I(e.Iv()), Mv(e.B * e.P()), px(e.px) {}
+        : e(e), o(e.vit[l]), w(e.vit_w16[l]), b(b), F(b.W), l(l), H(e.Hv()), I(e.Iv()), Mv(e.B * e.P()), px(e.px) {}
+    // BEiT: the residual GEMMs read the biases with the layer scale folded in (refresh_layer_beit)
+    const float* ao_bias() const { return e.beit() ? e.wsp<float>(e.beit_ws[l].ao_b) : F + o.ao_b; }
+    const float* fc2_bias() const { return e.beit() ? e.wsp<float>(e.beit_ws[l].fc2_b) : F + o.fc2_b; }
     G part(G& g) const { part_gemm(e, g, 1); return g; }
     int ln(const char* x, char* y, size_t gamma, size_t beta, float* mean, float* rstd, hipStream_t s) const {
         LNArgs n{x, y, F + gamma, F + beta, mean, rstd, Mv, H, H, H, e.cfg.ln_eps_img};
@@ -763,10 +843,14 @@ struct ImageLayer {
     int attention(hipStream_t s) const {
         AttnArgs at = attn_args(b.qkv, nullptr, b.ctx, b.lse, e.B, e.P(), e.heads_v(), H);
         attn_pair(at, px);
+        if (e.beit()) {          // the layer's relative position bias, expanded at refresh
+            CHECK_HIP(launch_attn_fwd_bias(attn_bias(at, e.wsp<float>(e.beit_ws[l].bias), e.ldb()), e.dt(), s));
+            return 0;
+        }
         CHECK_HIP(launch_attn_fwd(at, e.dt(), s));
         return 0;
     }
-    G attn_out() const { return part(G(b.ctx, H, e.ws + w.ao, H, b.x_mid, H, Mv, H, H).bias(F + o.ao_b).residual(b.x_in, H).px_in(px)); }
+    G attn_out() const { return part(G(b.ctx, H, e.ws + w.ao, H, b.x_mid, H, Mv, H, H).bias(ao_bias()).residual(b.x_in, H).px_in(px)); }
     G fc1() const {
         G g(b.ln2, H, e.ws + w.fc1, H, b.h, I, Mv, I, H);
         g.bias(F + o.fc1_b);
@@ -774,7 +858,20 @@ struct ImageLayer {
         if (e.clip()) g.qgelu(); else g.gelu();
         return part(g.px_in(px).px_out(px));
     }
-    G fc2() const { return part(G(b.h, I, e.ws + w.fc2, I, b.x_out, H, Mv, H, I).bias(F + o.fc2_b).residual(b.x_mid, H).px_in(px)); }
+    G fc2() const { return part(G(b.h, I, e.ws + w.fc2, I, b.x_out, H, Mv, H, I).bias(fc2_bias()).residual(b.x_mid, H).px_in(px)); }
+    // Stochastic depth (BEiT, train mode, p_l > 0; the shared buffer set: the stream is updated in place).  The residual GEMM writes the branch -- bias
+    // and layer scale included -- to a scratch tensor instead of adding it, and one more launch adds keep_scale * branch to the posts the hash keeps.
+    // One draw per (layer, branch, post): the element index is the post's row in the batch.
+    static uint32_t stream_droppath(int l, int which) { return 0x1000u + 2u * (uint32_t)l + (uint32_t)which; }
+    G branch(int which) const {          // 0: the attention block's, 1: the MLP's
+        char* scratch = e.ws + e.beit_branch;
+        G g = which == 0 ? G(b.ctx, H, e.ws + w.ao, H, scratch, H, Mv, H, H).bias(ao_bias()) : G(b.h, I, e.ws + w.fc2, I, scratch, H, Mv, H, I).bias(fc2_bias());
+        return part(g.px_in(px));
+    }
+    int droppath_add(int which, float p, hipStream_t s) const {
+        CHECK_HIP(launch_droppath_add(which == 0 ? b.x_mid : b.x_out, e.ws + e.beit_branch, e.B, e.P(), H, make_drop(p, e.seed, stream_droppath(l, which)), e.dt(), s));
+        return 0;
+    }
 };
 
 // closes the image tower: last hidden state in v_out, pooled feature in h_vpool
@@ -782,6 +879,13 @@ int vit_close(mmhip_engine& e, hipStream_t s) {
     const int H = e.Hv(), B = e.B, P = e.P(), Mv = B * P, dt = e.dt();
     const float* F = e.frozen;
     char* x = e.ws + e.v_x;
+    if (e.beit()) {
+        // last_hidden_state = the encoder output as it is (BeitModel.layernorm is Identity under mean pooling); pooler_output = LayerNorm(mean of the
+        // patch tokens), no dense, no tanh   (BeitPooler.forward)
+        CHECK_HIP(hipMemcpyAsync(e.ws + e.v_out, x, (size_t)Mv * H * e.esz(), hipMemcpyDeviceToDevice, s));
+        CHECK_HIP(launch_patch_mean_ln(x, P, B, H, F + e.v_ln_w, F + e.v_ln_b, e.cfg.ln_eps_img, e.wsp<float>(e.h_vpool), dt, s));
+        return 0;
+    }
     if (e.clip()) {
         // last_hidden_state = the encoder output as it is; pooler_output = post_layernorm(CLS row)   (CLIPVisionTransformer.forward)
         CHECK_HIP(hipMemcpyAsync(e.ws + e.v_out, x, (size_t)Mv * H * e.esz(), hipMemcpyDeviceToDevice, s));
@@ -807,10 +911,21 @@ int image_layers_forward(mmhip_engine& e, const float* pixels, bool saved, hipSt
         CHECK_RC(v.ln1(s));
         CHECK_RC(run_gemm(e, v.qkv(), s));
         CHECK_RC(v.attention(s));
-        CHECK_RC(run_gemm(e, v.attn_out(), s));
+        const float p_drop = !saved && e.beit() ? e.drop_path_p(l) : 0.f;      // > 0: BEiT's stochastic depth is on for this layer
+        if (p_drop > 0.f) {
+            CHECK_RC(run_gemm(e, v.branch(0), s));
+            CHECK_RC(v.droppath_add(0, p_drop, s));
+        } else {
+            CHECK_RC(run_gemm(e, v.attn_out(), s));
+        }
         CHECK_RC(v.ln2(s));
         CHECK_RC(run_gemm(e, v.fc1(), s));
-        CHECK_RC(run_gemm(e, v.fc2(), s));
+        if (p_drop > 0.f) {
+            CHECK_RC(run_gemm(e, v.branch(1), s));
+            CHECK_RC(v.droppath_add(1, p_drop, s));
+        } else {
+            CHECK_RC(run_gemm(e, v.fc2(), s));
+        }
     }
     return 0;
 }
@@ -850,7 +965,7 @@ bool lockstep_ok(const mmhip_engine& e) {
     // GEMMs for free, in lockstep they are serial work between launches that wait for each other.  Off by default in every mode.
     static int on = -2;
     if (on == -2) on = env_int("MMHIP_LOCKSTEP", 0);
-    return on > 0 && (e.dt() == DT_BF16 || e.dt() == DT_F16 || (e.dt() == DT_F32 && e.px)) && !e.clip() && e.Hv() == e.cfg.hidden && e.Iv() == e.cfg.inter &&
+    return on > 0 && (e.dt() == DT_BF16 || e.dt() == DT_F16 || (e.dt() == DT_F32 && e.px)) && !e.clip() && !e.beit() && e.Hv() == e.cfg.hidden && e.Iv() == e.cfg.inter &&
            e.cfg.layers_txt > 0 && e.cfg.layers_img > 0;
 }
 int towers_forward_lockstep(mmhip_engine& e, const float* pixels, hipStream_t s) {
@@ -1464,7 +1579,7 @@ int mmhip_create(const mmhip_config* cfg, mmhip_handle* out) {
     if (c.hidden <= 0 || c.hidden % 64 || c.hidden > 1024 || c.heads * 64 != c.hidden || c.inter % 128 || c.hidden % 128) return MMHIP_E_INVALID;
     {   // image tower: ViT (HF ViTModel) or CLIP vision (HF CLIPVisionModel), its own width allowed (CLIP-ViT-L/14: 1024 / 16 / 4096)
         const int hv = c.hidden_img > 0 ? c.hidden_img : c.hidden, iv = c.inter_img > 0 ? c.inter_img : c.inter, nh = c.heads_img > 0 ? c.heads_img : c.heads;
-        if (c.img_kind != MMHIP_IMG_VIT && c.img_kind != MMHIP_IMG_CLIP) return MMHIP_E_INVALID;
+        if (c.img_kind != MMHIP_IMG_VIT && c.img_kind != MMHIP_IMG_CLIP && c.img_kind != MMHIP_IMG_BEIT) return MMHIP_E_INVALID;
         if (hv % 128 || hv > 1024 || nh * 64 != hv || iv % 128 || c.patch < 2 || c.image % c.patch) return MMHIP_E_INVALID;
         if (c.fusion == MMHIP_FUSION_ATTENTION && hv != c.hidden) return MMHIP_E_INVALID;       // fc_K / fc_V are hidden x hidden (mm_late.py:74-75)
         if (c.fusion == MMHIP_FUSION_ASPECT && hv != c.hidden) return MMHIP_E_INVALID;          // the two pooler outputs are stacked into one matrix (mm_late.py:120)
@@ -1472,6 +1587,10 @@ int mmhip_create(const mmhip_config* cfg, mmhip_handle* out) {
         // the fp32 parity-mode attention holds 4-byte K / V: 288 keys
         const int P = (c.image / c.patch) * (c.image / c.patch) + 1;
         if (P > 608) return MMHIP_E_INVALID;
+        if (c.img_kind == MMHIP_IMG_BEIT && P > 224) return MMHIP_E_INVALID;          // the attention forward with a 2-D bias is instantiated up to 224 keys
+        // ... and on the matrix cores only: the parity mode's vector-ALU attention (MMHIP_X3_FAST=0) has no bias form, so such a handle is refused here
+        // instead of failing in every forward
+        if (c.img_kind == MMHIP_IMG_BEIT && c.dtype == MMHIP_BF16X3 && env_int("MMHIP_X3_FAST", 1) == 0) return MMHIP_E_INVALID;
     }
     if (c.max_text_len > 128 || c.max_text_len < 1 || c.max_posts < 1 || c.max_posts > 1024) return MMHIP_E_INVALID;
     if (c.dtype != MMHIP_BF16 && c.dtype != MMHIP_F16 && c.dtype != MMHIP_BF16X3) return MMHIP_E_INVALID;
@@ -1555,8 +1674,10 @@ int mmhip_refresh_weights(mmhip_handle h, int which, void* stream) {
     if ((which & 1) && e.is_text()) return MMHIP_E_STATE;          // no image tower, no frozen buffer (mmhip_txt_refresh_weights refreshes the text tower)
     if (e.is_image()) return MMHIP_E_STATE;                         // (mmhip_img_refresh_weights)
     if (which & 1) {
-        for (int l = 0; l < e.cfg.layers_img; ++l)
-            CHECK_RC(refresh_layer(e, e.frozen, e.vit[l], e.vit_w16[l], false, s, e.Hv(), e.Iv()));
+        for (int l = 0; l < e.cfg.layers_img; ++l) {
+            if (e.beit()) CHECK_RC(refresh_layer_beit(e, l, s));
+            else CHECK_RC(refresh_layer(e, e.frozen, e.vit[l], e.vit_w16[l], false, s, e.Hv(), e.Iv()));
+        }
         CHECK_RC(refresh_patch(e, e.frozen, s));
     }
     if (which & 2)
@@ -1810,6 +1931,11 @@ int mmhip_set_backward_products(mmhip_handle h, int products) {
     if (!h || products < 1 || products > 3) return MMHIP_E_INVALID;
     if (h->cfg.dtype != MMHIP_BF16X3 || !h->px) return products == 3 ? 0 : MMHIP_E_STATE;      // the 16-bit modes have one product; round 3's copy form has three
     h->bwd_np = products;
+    return 0;
+}
+int mmhip_set_drop_path(mmhip_handle h, float rate) {
+    if (!h || !h->is_late() || !h->beit() || !(rate >= 0.f) || rate >= 1.f) return MMHIP_E_INVALID;
+    h->drop_path = rate;
     return 0;
 }
 int mmhip_set_loss_scale(mmhip_handle h, float loss_scale) {

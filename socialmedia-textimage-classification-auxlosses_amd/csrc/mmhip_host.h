@@ -127,6 +127,13 @@ inline void attn_pair(A& a, bool px) {
     if (px) { a.pair = 1; a.ld_qkv = 6 * a.hidden; a.lo_qkv = 3 * a.hidden; a.ld_ctx = 2 * a.hidden; a.lo_ctx = a.hidden; }
 }
 inline void attn_pair(AttnBwdArgs& a, bool px, int nprod) { attn_pair(a, px); if (px) a.nprod = nprod; }      // nprod: AttnBwdArgs::nprod, the backward's product policy
+// the forward with a per-head 2-D score bias: `a` as filled above (pair strides included) plus the bias image [heads][S][ld_bias]
+inline AttnBiasArgs attn_bias(const AttnArgs& a, const float* bias2d, int ld_bias) {
+    AttnBiasArgs b{};
+    static_cast<AttnArgs&>(b) = a;
+    b.bias2d = bias2d; b.ld_bias = ld_bias;
+    return b;
+}
 // cross attention on compact tensors: Sq queries per post against Sk keys; the Q columns of qkv and ctx hold Sq rows per post, the K | V columns Sk
 template <typename A>
 inline void attn_cross(A& a, int Sq, int Sk) { a.Sq_live = Sq; a.Sk_live = Sk; a.q_rps = Sq; a.kv_rps = Sk; a.ctx_rps = Sq; }

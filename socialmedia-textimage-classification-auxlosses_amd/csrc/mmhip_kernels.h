@@ -133,6 +133,13 @@ struct AttnArgs {
                           // query row q of post p is row p * q_rps + q, key row k is row p * kv_rps + k; the two projections write Mq and Mc rows and nothing is
                           // remapped, cleared or copied
 };
+// AttnArgs plus a per-head additive score bias (BEiT's relative position bias).  A type of its own, so that the kernels that take AttnArgs keep their
+// kernel-argument block -- and with it their code -- exactly (growing AttnArgs itself by these 16 bytes re-schedules every dropout instantiation of
+// the forward kernel: profiles/beit_attn_resources.txt).
+struct AttnBiasArgs : AttnArgs {
+    const float* bias2d;  // [heads][S][ld_bias] fp32 in natural units, the same for every post, added to the scores after the scaling
+    int ld_bias;          // ld_bias % 4 == 0, ld_bias >= S, bias2d 16-byte aligned; columns S .. ld_bias-1 must be finite (they are read, then masked)
+};
 struct AttnBwdArgs {
     const void* qkv; const float* maskbias; const void* ctx; const void* dctx; const float* lse;
     void* dqkv;           // [rows, ld_qkv]
@@ -149,6 +156,10 @@ struct AttnBwdArgs {
                           // products take one, d ctx is read from its hi plane only; 0 / 3: three products throughout (GemmNTArgs::nprod: the engine's policy)
 };
 hipError_t launch_attn_fwd(const AttnArgs& a, int dtype, hipStream_t s);
+// forward with the 2-D bias: self-attention on the matrix cores, S <= 224, no dropout, dtype DT_BF16 | DT_F16 | DT_F32 (parity mode: fp32 tensors, or
+// plane pairs with a.pair).  hipErrorInvalidValue before any launch for: ld_bias % 4 != 0, ld_bias < S, a null or misaligned bias2d, cross-attention
+// arguments (Sq_live, Sk_live, q_rps, kv_rps, ctx_rps), dropout, S > 224, another dtype, fp32 tensors off 16-byte alignment or MMHIP_X3_FAST=0
+hipError_t launch_attn_fwd_bias(const AttnBiasArgs& a, int dtype, hipStream_t s);
 hipError_t launch_attn_fwd_f32(const AttnArgs& a, hipStream_t s);
 hipError_t launch_attn_bwd_f32(const AttnBwdArgs& a, hipStream_t s);
 hipError_t launch_attn_bwd(const AttnBwdArgs& a, int dtype, hipStream_t s);
@@ -223,7 +234,18 @@ hipError_t launch_embed_bwd(const EmbedBwdArgs& a, int dtype, hipStream_t s);
 
 hipError_t launch_patchify(const float* pixels, void* out, int B, int img, int patch, int ld, int dtype, hipStream_t s);   // rows of ld >= 3*patch^2 columns, zero-padded
 hipError_t launch_cast_pad(const float* src, void* dst, int rows, int cols, int ld, int dtype, hipStream_t s);   // dst[r][0..ld) = cast(src[r][0..cols)), 0 beyond
-hipError_t launch_vit_assemble(const void* patches, const float* cls, const float* pos, void* x, int B, int P, int H, int dtype, hipStream_t s);
+hipError_t launch_vit_assemble(const void* patches, const float* cls, const float* pos, void* x, int B, int P, int H, int dtype, hipStream_t s);   // pos == nullptr: nothing added
+// ---- BEiT tower pieces (HF BeitModel: relative position bias, layer scale, mean-pool pooler, stochastic depth)
+// out[post][0..width) (fp32) = LayerNorm(mean over rows 1 .. rows_per_post-1 of the post's block of x): the CLS row 0 is not part of the mean.  One
+// workgroup per post, fp32 sums in token order (the same bits on every call).  rows_per_post >= 2, width % 4 == 0, width <= 1024.
+hipError_t launch_patch_mean_ln(const void* x, int rows_per_post, int posts, int width, const float* gamma, const float* beta, float eps, float* out, int dtype,
+                                hipStream_t s);
+// x[post] += keep_scale * branch[post] for the posts the hash keeps (element index = post, DropCfg as make_drop builds it); a dropped post's rows are
+// not touched.  x, branch [posts * rows_per_post, width] in `dtype` (DT_BF16 | DT_F16 | DT_F32), width % 4 == 0.
+hipError_t launch_droppath_add(void* x, const void* branch, int posts, int rows_per_post, int width, const DropCfg& d, int dtype, hipStream_t s);
+hipError_t launch_scale_rows_f32(const float* src, const float* scale, float* dst, int rows, int cols, hipStream_t s);      // dst[r][c] = scale[r] * src[r][c]
+// out [heads][Wh*Ww+1][ld] (fp32) = table[index(i, j)][head], table [(2Wh-1)(2Ww-1)+3, heads]; columns past the token count are zero; ld >= Wh*Ww+1
+hipError_t launch_beit_bias_image(const float* table, int heads, int Wh, int Ww, float* out, int ld, hipStream_t s);
 // Backward of launch_vit_assemble.  dx [B*P, H] is the gradient of the tower's first residual stream in the activation type (16-bit; parity mode fp32).
 //   dpos [P, H] += alpha * sum_b dx[b, p, :]      dcls [H] += alpha * sum_b dx[b, 0, :]   (the same sum as row 0 of dpos, computed once)
 //   dpe  [B*(P-1), H]: the patch rows, compact, as the weight-gradient GEMM reads them -- the same 16-bit words; parity mode: fp32 words, or with

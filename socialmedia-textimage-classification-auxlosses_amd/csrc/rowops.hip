@@ -629,7 +629,8 @@ __global__ __launch_bounds__(256) void cast_pad_kernel(const float* __restrict__
     }
 }
 // x[b*P] = cls + pos[0]; x[b*P + 1 + p] = patches[b*(P-1) + p] + pos[1 + p]      (HF vit :146-157)
-template <typename T>
+// POS = false: no position table, nothing is added (BEiT: use_absolute_position_embeddings = False)
+template <typename T, bool POS = true>
 __global__ __launch_bounds__(256) void vit_assemble_kernel(const T* __restrict__ patches, const float* __restrict__ cls, const float* __restrict__ pos, T* __restrict__ x, int B, int P, int H) {
     const int hc = H / 4;
     const size_t total = (size_t)B * P * hc;
@@ -640,9 +641,11 @@ __global__ __launch_bounds__(256) void vit_assemble_kernel(const T* __restrict__
         float v[4], q[4];
         if (p == 0) load4<float>(cls + c, v);
         else load4<T>(patches + ((size_t)b * (P - 1) + (p - 1)) * H + c, v);
-        load4<float>(pos + (size_t)p * H + c, q);
+        if (POS) {
+            load4<float>(pos + (size_t)p * H + c, q);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] += q[e];
+            for (int e = 0; e < 4; ++e) v[e] += q[e];
+        }
         store4<T>(x + row * H + c, v);
     }
 }
@@ -915,6 +918,106 @@ __global__ __launch_bounds__(256) void gather_rows_f32_kernel(const T* __restric
     }
 }
 
+// ------------------------------------------------------------------------------------------------ BEiT tower pieces
+// Pooler of HF BeitModel under use_mean_pooling: out[post] = LayerNorm(mean over the post's patch tokens of x) -- rows 1 .. rows_per_post-1, the CLS
+// row 0 is left out -- in one launch.  One workgroup per post; a thread owns four columns and adds the tokens in ascending order in fp32 (PM_UNROLL
+// loads requested before the first is added), so the result does not depend on the launch; the LayerNorm's two sums go through LDS.
+static constexpr int PM_UNROLL = 8;
+template <typename T>
+__global__ __launch_bounds__(256) void patch_mean_ln_kernel(const T* __restrict__ x, int rows_per_post, int width, const float* __restrict__ gamma,
+                                                            const float* __restrict__ beta, float eps, float* __restrict__ out) {
+    __shared__ float red[4];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, c = tid * 4;
+    const bool live = c < width;
+    const T* xp = x + (size_t)blockIdx.x * rows_per_post * width + c;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    if (live) {
+        int r = 1;
+        for (; r + PM_UNROLL <= rows_per_post; r += PM_UNROLL) {
+            float v[PM_UNROLL][4];
+#pragma unroll
+            for (int i = 0; i < PM_UNROLL; ++i) load4<T>(xp + (size_t)(r + i) * width, v[i]);
+#pragma unroll
+            for (int i = 0; i < PM_UNROLL; ++i)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[e] += v[i][e];
+        }
+        for (; r < rows_per_post; ++r) {
+            float v[4];
+            load4<T>(xp + (size_t)r * width, v);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[e] += v[e];
+        }
+        const float inv = 1.0f / (float)(rows_per_post - 1);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[e] *= inv;
+    }
+    auto block_sum = [&](float v) -> float {
+        v = wave_sum(v);
+        __syncthreads();
+        if (lane == 0) red[wv] = v;
+        __syncthreads();
+        return (red[0] + red[1]) + (red[2] + red[3]);
+    };
+    const float mean = block_sum(live ? (acc[0] + acc[1]) + (acc[2] + acc[3]) : 0.f) / (float)width;
+    float q = 0.f;
+    if (live)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { const float d = acc[e] - mean; q += d * d; }
+    const float rstd = rsqrtf(block_sum(q) / (float)width + eps);
+    if (live) {
+        float g[4], b[4];
+        load4<float>(gamma + c, g);
+        load4<float>(beta + c, b);
+        *reinterpret_cast<f32x4*>(out + (size_t)blockIdx.x * width + c) =
+            f32x4{(acc[0] - mean) * rstd * g[0] + b[0], (acc[1] - mean) * rstd * g[1] + b[1], (acc[2] - mean) * rstd * g[2] + b[2], (acc[3] - mean) * rstd * g[3] + b[3]};
+    }
+}
+// Stochastic depth (HF BeitDropPath), one decision per post: x[post] += s * branch[post], s = keep_scale when the post's 16 random bits (the engines'
+// hash on element index = the post's row in the batch) reach the threshold, else the post's rows are left as they are -- bit for bit.
+template <typename T>
+__global__ __launch_bounds__(256) void droppath_add_kernel(T* __restrict__ x, const T* __restrict__ branch, int posts, int rows_per_post, int width, DropCfg d) {
+    const int wc = width / 4;
+    const size_t per_post = (size_t)rows_per_post * wc, total = per_post * posts;
+    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+        const uint32_t post = (uint32_t)(idx / per_post);
+        if (!mm_keep(post, d)) continue;
+        float a[4], b[4];
+        load4<T>(x + idx * 4, a);
+        load4<T>(branch + idx * 4, b);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) a[e] = fmaf(d.keep_scale, b[e], a[e]);
+        store4<T>(x + idx * 4, a);
+    }
+}
+// out[r][c] = scale[r] * src[r][c] (fp32): the layer scale folded into a weight's rows before its 16-bit copy is cast; cols == 1: a bias vector
+__global__ __launch_bounds__(256) void scale_rows_kernel(const float* __restrict__ src, const float* __restrict__ scale, float* __restrict__ dst, int rows, int cols) {
+    const size_t total = (size_t)rows * cols;
+    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) dst[idx] = scale[idx / cols] * src[idx];
+}
+// BEiT relative position bias, expanded: out[h][i][j] = table[index(i, j)][h] for tokens i, j < P = Wh * Ww + 1 (HF BeitRelativePositionBias: patches
+// by their coordinate difference, then three extra rows: CLS to token, token to CLS, CLS to CLS); columns P .. ld-1 are zero.  The index is computed
+// here from the window geometry, never uploaded.
+__global__ __launch_bounds__(256) void beit_bias_image_kernel(const float* __restrict__ table, int heads, int Wh, int Ww, float* __restrict__ out, int ld) {
+    const int P = Wh * Ww + 1, n = (2 * Wh - 1) * (2 * Ww - 1) + 3;
+    const size_t total = (size_t)heads * P * ld;
+    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+        const int j = (int)(idx % ld), i = (int)((idx / ld) % P), h = (int)(idx / ((size_t)ld * P));
+        float v = 0.f;
+        if (j < P) {
+            int k;
+            if (i == 0) k = j == 0 ? n - 1 : n - 3;
+            else if (j == 0) k = n - 2;
+            else {
+                const int a = i - 1, b = j - 1;
+                k = (a / Ww - b / Ww + Wh - 1) * (2 * Ww - 1) + (a % Ww - b % Ww + Ww - 1);
+            }
+            v = table[(size_t)k * heads + h];
+        }
+        out[idx] = v;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ launchers
 #define DISPATCH_T(dtype, KERNEL, grid, block, stream, ...)                                        \
     do {                                                                                           \
@@ -1023,6 +1126,12 @@ hipError_t launch_patchify(const float* pixels, void* out, int B, int img, int p
 hipError_t launch_vit_assemble(const void* patches, const float* cls, const float* pos, void* x, int B, int P, int H, int dtype, hipStream_t s) {
     if (B <= 0) return hipSuccess;
     const size_t total = (size_t)B * P * (H / 4);
+    if (!pos) {
+        if (dtype == DT_BF16) hipLaunchKernelGGL((vit_assemble_kernel<bf16_t, false>), dim3(cap_grid(total)), dim3(256), 0, s, (const bf16_t*)patches, cls, pos, (bf16_t*)x, B, P, H);
+        else if (dtype == DT_F16) hipLaunchKernelGGL((vit_assemble_kernel<f16_t, false>), dim3(cap_grid(total)), dim3(256), 0, s, (const f16_t*)patches, cls, pos, (f16_t*)x, B, P, H);
+        else hipLaunchKernelGGL((vit_assemble_kernel<float, false>), dim3(cap_grid(total)), dim3(256), 0, s, (const float*)patches, cls, pos, (float*)x, B, P, H);
+        return hipGetLastError();
+    }
     if (dtype == DT_BF16) hipLaunchKernelGGL(vit_assemble_kernel<bf16_t>, dim3(cap_grid(total)), dim3(256), 0, s, (const bf16_t*)patches, cls, pos, (bf16_t*)x, B, P, H);
     else if (dtype == DT_F16) hipLaunchKernelGGL(vit_assemble_kernel<f16_t>, dim3(cap_grid(total)), dim3(256), 0, s, (const f16_t*)patches, cls, pos, (f16_t*)x, B, P, H);
     else hipLaunchKernelGGL(vit_assemble_kernel<float>, dim3(cap_grid(total)), dim3(256), 0, s, (const float*)patches, cls, pos, (float*)x, B, P, H);
@@ -1138,6 +1247,37 @@ hipError_t launch_scatter_cls_rows(const float* d, void* dx, int posts, int T, i
     if (dtype == DT_BF16) hipLaunchKernelGGL(scatter_cls_kernel<bf16_t>, dim3(cap_grid(total)), dim3(256), 0, s, d, (bf16_t*)dx, posts, T, H, scale);
     else if (dtype == DT_F16) hipLaunchKernelGGL(scatter_cls_kernel<f16_t>, dim3(cap_grid(total)), dim3(256), 0, s, d, (f16_t*)dx, posts, T, H, scale);
     else hipLaunchKernelGGL(scatter_cls_kernel<float>, dim3(cap_grid(total)), dim3(256), 0, s, d, (float*)dx, posts, T, H, scale);
+    return hipGetLastError();
+}
+
+hipError_t launch_patch_mean_ln(const void* x, int rows_per_post, int posts, int width, const float* gamma, const float* beta, float eps, float* out, int dtype,
+                                hipStream_t s) {
+    if (posts <= 0) return hipSuccess;
+    if (rows_per_post < 2 || width % 4 || width < 4 || width > 1024) return hipErrorInvalidValue;
+    if (dtype == DT_BF16) hipLaunchKernelGGL(patch_mean_ln_kernel<bf16_t>, dim3(posts), dim3(256), 0, s, (const bf16_t*)x, rows_per_post, width, gamma, beta, eps, out);
+    else if (dtype == DT_F16) hipLaunchKernelGGL(patch_mean_ln_kernel<f16_t>, dim3(posts), dim3(256), 0, s, (const f16_t*)x, rows_per_post, width, gamma, beta, eps, out);
+    else if (dtype == DT_F32) hipLaunchKernelGGL(patch_mean_ln_kernel<float>, dim3(posts), dim3(256), 0, s, (const float*)x, rows_per_post, width, gamma, beta, eps, out);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+hipError_t launch_droppath_add(void* x, const void* branch, int posts, int rows_per_post, int width, const DropCfg& d, int dtype, hipStream_t s) {
+    if (posts <= 0 || rows_per_post <= 0) return hipSuccess;
+    if (width % 4) return hipErrorInvalidValue;
+    const int grid = cap_grid((size_t)posts * rows_per_post * (width / 4));
+    if (dtype == DT_BF16) hipLaunchKernelGGL(droppath_add_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (bf16_t*)x, (const bf16_t*)branch, posts, rows_per_post, width, d);
+    else if (dtype == DT_F16) hipLaunchKernelGGL(droppath_add_kernel<f16_t>, dim3(grid), dim3(256), 0, s, (f16_t*)x, (const f16_t*)branch, posts, rows_per_post, width, d);
+    else if (dtype == DT_F32) hipLaunchKernelGGL(droppath_add_kernel<float>, dim3(grid), dim3(256), 0, s, (float*)x, (const float*)branch, posts, rows_per_post, width, d);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+hipError_t launch_scale_rows_f32(const float* src, const float* scale, float* dst, int rows, int cols, hipStream_t s) {
+    if (rows <= 0 || cols <= 0) return hipSuccess;
+    hipLaunchKernelGGL(scale_rows_kernel, dim3(cap_grid((size_t)rows * cols)), dim3(256), 0, s, src, scale, dst, rows, cols);
+    return hipGetLastError();
+}
+hipError_t launch_beit_bias_image(const float* table, int heads, int Wh, int Ww, float* out, int ld, hipStream_t s) {
+    if (heads < 1 || Wh < 1 || Ww < 1 || ld < Wh * Ww + 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(beit_bias_image_kernel, dim3(cap_grid((size_t)heads * (Wh * Ww + 1) * ld)), dim3(256), 0, s, table, heads, Wh, Ww, out, ld);
     return hipGetLastError();
 }
 

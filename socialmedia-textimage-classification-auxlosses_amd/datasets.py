@@ -264,6 +264,55 @@ class BatchTokenizeCollate:
         return batch
 
 
+def read_preprocessor_config(model_dir, default_size=224):
+    """what the reference's ViTFeatureExtractor.from_pretrained(img_model_dir) (models/mm_late.py:324) would take from the model directory's
+    preprocessor_config.json -> dict(size, image_mean, image_std); without the file the ViT defaults (224, bilinear, mean = std = 0.5).  Anything
+    the GPU / host preprocessing here does not implement is refused, never ignored: another resample filter than bilinear (PIL code 2), a
+    non-square size, resizing or normalisation switched off.  Keys that the 4.25.1 ViTFeatureExtractor does not know -- do_center_crop, crop_size --
+    have no effect there (it resizes and normalises, nothing else) and have none here."""
+    out = dict(size=int(default_size), image_mean=[0.5, 0.5, 0.5], image_std=[0.5, 0.5, 0.5])
+    path = os.path.join(model_dir or "", "preprocessor_config.json")
+    if not os.path.isfile(path):
+        return out
+    import json
+    with open(path) as f:
+        pc = json.load(f)
+    size = pc.get("size", out["size"])
+    if isinstance(size, dict):
+        if "height" in size or "width" in size:
+            if size.get("height") != size.get("width"):
+                raise NotImplementedError(f"{path}: size {size!r} is not square; the image preprocessing here resizes to a square")
+            size = size["height"]
+        else:
+            raise NotImplementedError(f"{path}: size {size!r} (shortest-edge resizing) is not implemented; a square {{height, width}} is")
+    elif isinstance(size, (list, tuple)):
+        if len(set(size)) != 1:
+            raise NotImplementedError(f"{path}: size {size!r} is not square; the image preprocessing here resizes to a square")
+        size = size[0]
+    if int(pc.get("resample", 2)) != 2:
+        raise NotImplementedError(f"{path}: resample = {pc['resample']} (PIL filter code); the image preprocessing here implements bilinear (2) only")
+    for flag in ("do_resize", "do_normalize", "do_rescale"):
+        if not pc.get(flag, True):
+            raise NotImplementedError(f"{path}: {flag} = false is not implemented")
+    if float(pc.get("rescale_factor", 1 / 255)) != 1 / 255:
+        raise NotImplementedError(f"{path}: rescale_factor = {pc['rescale_factor']}; 1 / 255 is implemented")
+    out.update(size=int(size), image_mean=[float(x) for x in pc.get("image_mean", out["image_mean"])],
+               image_std=[float(x) for x in pc.get("image_std", out["image_std"])])
+    return out
+
+
+def image_preprocessing(img_kind, model_dir, size):
+    """-> dict(size, image_mean, image_std) of the image processor of a run.  Only the BEiT tower reads its model directory's
+    preprocessor_config.json (and refuses what the file asks for beyond that); every other tower keeps the fixed ViT defaults at the tower's
+    image size, whatever its directory holds."""
+    if img_kind != "beit":
+        return dict(size=int(size), image_mean=[0.5, 0.5, 0.5], image_std=[0.5, 0.5, 0.5])
+    pre = read_preprocessor_config(model_dir, size)
+    if pre["size"] != size:
+        raise ValueError(f"preprocessor_config.json resizes to {pre['size']} but the image tower takes {size} x {size} images")
+    return pre
+
+
 def loaders_from_data_key(cfg, args, trainer):
     from transformers import AutoTokenizer
     tdir = MODEL_DIR_DICT[args.txt_model_name]
@@ -278,6 +327,9 @@ def loaders_from_data_key(cfg, args, trainer):
     # image resize + normalize run on the GPU per batch (image_processing.py) unless --cpu_preprocess asks for the host form
     gpu = not getattr(args, "cpu_preprocess", False) and trainer.device.type == "cuda"
     size = trainer.model.arch["image"]
+    pre = image_preprocessing(trainer.model.arch["img_kind"], MODEL_DIR_DICT.get(args.img_model_name, ""), size)
+    if not gpu and (pre["image_mean"] != [0.5] * 3 or pre["image_std"] != [0.5] * 3):
+        raise NotImplementedError("--cpu_preprocess normalises with mean = std = 0.5; this model directory's preprocessor_config.json says otherwise")
     # texts are encoded per batch in the collate (one encode_batch call) unless --item_tokenize keeps the reference's per-item calls
     batch_tok = not getattr(args, "item_tokenize", False) and getattr(tok, "is_fast", False)
     mk = lambda df, y: MM_Dataset(df.tweet_id.values, df.text.values, y, tok, cfg.max_length, cfg.img_fmt, size, raw_images=gpu, batch_tokenize=batch_tok)
@@ -295,7 +347,7 @@ def loaders_from_data_key(cfg, args, trainer):
     inner, ring_collates = None, None
     if gpu:
         from .image_processing import GpuImageProcessor, RawImageCollate, RingCollate, SharedImageRing
-        trainer.image_processor = GpuImageProcessor(size=size, device=trainer.device)
+        trainer.image_processor = GpuImageProcessor(size=size, image_mean=pre["image_mean"], image_std=pre["image_std"], device=trainer.device)
         inner = RawImageCollate(trainer.image_processor)
         if kw["num_workers"] > 0 and os.environ.get("MMHIP_IMAGE_RING", "1") != "0":
             # decoded images reach the training process through a pinned shared-memory ring instead of the DataLoader's result queue

@@ -43,13 +43,18 @@ ASPECT_ITM_MESSAGE = ("fusion 'aspect-att' has no image-text matching pass: the 
                       "without the pooler outputs and raises; run it without --use_tim_loss / tim_inputs")
 
 
+# a cached tower output would freeze one draw of the stochastic depth for every later epoch
+VISION_CACHE_DROP_PATH_MESSAGE = ("the image-tower output cache needs a deterministic tower: the BEiT tower trains under stochastic depth "
+                                  "(drop_path_rate > 0, as in the reference); run without --cache_vision, or set drop_path_rate to 0")
+
+
 def default_arch(txt_model_name, img_model_name):
     if txt_model_name not in TEXT_ARCH:
         raise ValueError(f"text model {txt_model_name!r}: late-fusion path supports {sorted(TEXT_ARCH)}")
     if img_model_name not in IMAGE_ARCH:
-        raise ValueError(f"image model {img_model_name!r}: late-fusion HIP path supports {sorted(IMAGE_ARCH)} (ViT-B/16, CLIP-ViT-L/14)")
+        raise ValueError(f"image model {img_model_name!r}: late-fusion HIP path supports {sorted(IMAGE_ARCH)} (ViT-B/16, BEiT-B/16, CLIP-ViT-L/14)")
     a = dict(hidden=768, heads=12, inter=3072, layers_txt=12, layers_img=12, proj_dim=512, p_hidden=0.1, p_attn=0.1,
-             img_kind="vit", hidden_img=0, heads_img=0, inter_img=0)
+             img_kind="vit", hidden_img=0, heads_img=0, inter_img=0, drop_path_rate=0.0, layer_scale_init_value=0.0)
     a.update(TEXT_ARCH[txt_model_name])
     a.update(IMAGE_ARCH[img_model_name])
     return a
@@ -69,6 +74,73 @@ def _vit_key_to_ref(k):
         k = k.replace("attention.v_proj", "attention.attention.value").replace("attention.o_proj", "attention.output.dense")
         k = k.replace("mlp.fc1", "intermediate.dense").replace("mlp.fc2", "output.dense")
     return k
+
+
+def _beit_key_to_ref(k):
+    """transformers >= 5 BEiT names -> 4.25.1 checkpoint names: the ViT renames, lambda_* stay on the layer, and the per-layer relative position
+    bias moves back under the attention (layers.N.relative_position_bias.* -> encoder.layer.N.attention.attention.relative_position_bias.*)"""
+    if k.startswith("layers."):
+        n, rest = k[len("layers."):].split(".", 1)
+        if rest.startswith("relative_position_bias."):
+            return f"encoder.layer.{n}.attention.attention.{rest}"
+        return _vit_key_to_ref(k)
+    return k
+
+
+def _beit_ref_to_key(k):
+    """the inverse of _beit_key_to_ref: 4.25.1 checkpoint names -> transformers >= 5 names"""
+    if k.startswith("encoder.layer."):
+        n, rest = k[len("encoder.layer."):].split(".", 1)
+        if rest.startswith("attention.attention.relative_position_bias."):
+            return f"layers.{n}.{rest[len('attention.attention.'):]}"
+        for old, new in (("attention.attention.query", "attention.q_proj"), ("attention.attention.key", "attention.k_proj"),
+                         ("attention.attention.value", "attention.v_proj"), ("attention.output.dense", "attention.o_proj"),
+                         ("intermediate.dense", "mlp.fc1"), ("output.dense", "mlp.fc2")):
+            if rest.startswith(old):
+                rest = new + rest[len(old):]
+                break
+        return f"layers.{n}.{rest}"
+    return k
+
+
+BEIT_SUPPORTED = dict(use_absolute_position_embeddings=False, use_relative_position_bias=True, use_shared_relative_position_bias=False,
+                      use_mean_pooling=True)
+
+
+def check_beit_config(img_cfg):
+    """the BEiT tower is built for the configuration of microsoft/beit-base-patch16-224-pt22k-ft22k; a model directory that says otherwise is
+    refused (HF defaults: the three position flags False, mean pooling True)"""
+    hf_default = dict(use_absolute_position_embeddings=False, use_relative_position_bias=False, use_shared_relative_position_bias=False,
+                      use_mean_pooling=True)
+    for flag, want in BEIT_SUPPORTED.items():
+        got = bool(img_cfg.get(flag, hf_default[flag]))
+        if got != want:
+            raise NotImplementedError(f"BEiT config.json has {flag} = {got}: the HIP tower implements {flag} = {want} only (per-layer relative "
+                                      "position bias, no absolute position embeddings, mean-pool pooler)")
+    if float(img_cfg.get("hidden_dropout_prob", 0.0)) != 0.0 or float(img_cfg.get("attention_probs_dropout_prob", 0.0)) != 0.0:
+        raise NotImplementedError("BEiT config.json has a non-zero hidden / attention dropout: the frozen HIP tower implements 0.0 only")
+    if float(img_cfg.get("layer_scale_init_value", 0.1)) <= 0.0:
+        raise NotImplementedError("BEiT config.json has layer_scale_init_value <= 0 (no lambda_1 / lambda_2): the HIP tower implements layer scale only")
+    if img_cfg.get("hidden_act", "gelu") != "gelu":
+        raise NotImplementedError(f"BEiT config.json has hidden_act = {img_cfg.get('hidden_act')!r}: the HIP tower implements 'gelu' only")
+
+
+def beit_relative_position_index(window_h, window_w):
+    """HF BeitRelativePositionBias.relative_position_index for a window_h x window_w window, int64 [P, P] with P = window_h * window_w + 1: patches
+    by their coordinate difference, then three extra table rows for CLS to token, token to CLS and CLS to CLS.  4.25.1 checkpoints carry it as
+    a buffer; the engine computes the same index on the device (csrc/rowops.hip beit_bias_image_kernel)."""
+    n = (2 * window_h - 1) * (2 * window_w - 1) + 3
+    ys, xs = np.divmod(np.arange(window_h * window_w), window_w)
+    rel = (ys[:, None] - ys[None, :] + window_h - 1) * (2 * window_w - 1) + (xs[:, None] - xs[None, :] + window_w - 1)
+    idx = np.empty((window_h * window_w + 1,) * 2, dtype=np.int64)
+    idx[1:, 1:] = rel
+    idx[0, :] = n - 3
+    idx[:, 0] = n - 2
+    idx[0, 0] = n - 1
+    return torch.from_numpy(idx)
+
+
+_IMG_KINDS = {"vit": _lib.IMG_VIT, "clip": _lib.IMG_CLIP, "beit": _lib.IMG_BEIT}
 
 
 class _MMFunction(torch.autograd.Function):
@@ -139,6 +211,9 @@ class MM_Model(WordTableEngineModule):
             if a["img_kind"] == "clip":
                 a.update(hidden_img=img_cfg.get("hidden_size", 1024), heads_img=img_cfg.get("num_attention_heads", 16),
                          inter_img=img_cfg.get("intermediate_size", 4096))
+            if a["img_kind"] == "beit":
+                check_beit_config(img_cfg)
+                a.update(drop_path_rate=float(img_cfg.get("drop_path_rate", 0.1)), layer_scale_init_value=float(img_cfg.get("layer_scale_init_value", 0.1)))
         a.update(arch or {})
         if fusion_name == "attention" and a["hidden_img"] not in (0, a["hidden"]):
             raise NotImplementedError("attention fusion needs image tokens as wide as the text tower (fc_K / fc_V are 768 x 768, reference "
@@ -146,7 +221,11 @@ class MM_Model(WordTableEngineModule):
         if fusion_name == "aspect-att" and a["hidden_img"] not in (0, a["hidden"]):
             raise NotImplementedError("aspect-att fusion stacks the two pooler outputs into one matrix (reference models/mm_late.py:120): the towers "
                                       "must be equally wide; use fusion_name='concat' with the CLIP-ViT-L/14 tower")
+        if a["img_kind"] == "beit" and not 0.0 <= float(a["drop_path_rate"]) < 1.0:
+            raise ValueError(f"drop_path_rate {a['drop_path_rate']!r}: a probability in [0, 1)")
         self.arch = a
+        # BEiT only: stochastic depth of the frozen tower in train mode (include/mmhip.h mmhip_set_drop_path); every handle is told (set_drop_path)
+        self.drop_path_rate = float(a["drop_path_rate"]) if a["img_kind"] == "beit" else 0.0
         self.dtype_name = dtype
         # parity mode only (include/mmhip.h mmhip_set_backward_products): MFMA products per reduction slice in the backward's matrix products;
         # None = the library's default (3, or MMHIP_X3_BWD).  The forward -- logits and loss -- always takes three.
@@ -160,7 +239,7 @@ class MM_Model(WordTableEngineModule):
                             proj_dim=a["proj_dim"], num_labels=num_labels,
                             fusion=_FUSIONS[fusion_name],
                             p_hidden=a["p_hidden"], p_attn=a["p_attn"], p_head=float(dropout),
-                            img_kind=_lib.IMG_CLIP if a["img_kind"] == "clip" else _lib.IMG_VIT, hidden_img=int(a["hidden_img"]),
+                            img_kind=_IMG_KINDS[a["img_kind"]], hidden_img=int(a["hidden_img"]),
                             heads_img=int(a["heads_img"]), inter_img=int(a["inter_img"]),
                             dtype={"bf16": _lib.BF16, "f16": _lib.F16, "bf16x3": _lib.BF16X3}[dtype])
         self._init_engine(int(seed) if seed is not None else int(torch.initial_seed()))
@@ -169,7 +248,14 @@ class MM_Model(WordTableEngineModule):
         if txt_sd is not None:
             self._load_tower(txt_sd, "dual_encoder.text_model.", lambda k: k)
         if img_sd is not None:
-            self._load_tower(img_sd, "dual_encoder.vision_model.", _clip_key_to_ref if a["img_kind"] == "clip" else _vit_key_to_ref)
+            loaded = self._load_tower(img_sd, "dual_encoder.vision_model.", {"clip": _clip_key_to_ref, "beit": _beit_key_to_ref}.get(a["img_kind"], _vit_key_to_ref))
+            if a["img_kind"] == "beit":
+                # a key map or a shape that does not fit the checkpoint (a 384 px bias table, another BEiT variant) must not leave a frozen tensor
+                # at its initial value without a word: every parameter of the tower has to come from the checkpoint
+                left = sorted(i["name"] for i in self._infos if i["buffer"] == 0 and i["name"] not in loaded)
+                if left:
+                    raise _lib.MMHipError(f"BEiT checkpoint in {MODEL_DIR_DICT.get(img_model_name)!r}: {len(left)} of the tower's parameters were not found in it "
+                                          f"under a matching name and shape, e.g. {left[:3]} (config.json and the weights disagree, or another BEiT variant)")
         self._refresh_weights(3)
 
     # ------------------------------------------------------------------ engine / buffers
@@ -187,6 +273,28 @@ class MM_Model(WordTableEngineModule):
     def _on_registered(self):
         super()._on_registered()
         self._train_params = [i for i in self._infos if i["buffer"] == 1]
+        if self.arch["img_kind"] == "beit":
+            # transformers 4.25.1 checkpoints carry this int64 buffer per layer (BeitRelativePositionBias registers it); the engine never reads it
+            w = self.arch["image"] // self.arch["patch"]
+            index = beit_relative_position_index(w, w).to(self.device_)
+            layers = self._modules["dual_encoder"]._modules["vision_model"]._modules["encoder"]._modules["layer"]
+            for l in range(self.arch["layers_img"]):
+                layers._modules[str(l)]._modules["attention"]._modules["attention"]._modules["relative_position_bias"].register_buffer(
+                    "relative_position_index", index.clone())
+
+    def _apply_setters(self, h):
+        super()._apply_setters(h)
+        if self.arch["img_kind"] == "beit":
+            _lib.check(_lib.lib().mmhip_set_drop_path(h, self.drop_path_rate), "set_drop_path")
+
+    def set_drop_path(self, rate):
+        """BEiT tower only: the stochastic depth rate of the training forward (HF drop_path_rate; 0 turns it off)"""
+        if self.arch["img_kind"] != "beit":
+            raise ValueError("set_drop_path: only the BEiT image tower has stochastic depth")
+        if getattr(self, "_vcache", None) is not None and float(rate) > 0.0:
+            raise NotImplementedError(VISION_CACHE_DROP_PATH_MESSAGE)
+        _lib.check(_lib.lib().mmhip_set_drop_path(self._handle, float(rate)), "set_drop_path")
+        self.drop_path_rate = float(rate)
 
     def _before_workspace(self, h):
         # global-batch ITC: the gathered [world * max_posts, proj_dim] rows live in the workspace (reserved before it is sized; nothing at world 1)
@@ -211,6 +319,10 @@ class MM_Model(WordTableEngineModule):
                 if n.startswith("dual_encoder."):
                     if n.endswith("logit_scale"):
                         p.fill_(2.6592)
+                    elif n.endswith(".lambda_1") or n.endswith(".lambda_2"):
+                        p.fill_(float(self.arch["layer_scale_init_value"]) or 0.1)          # HF BeitLayer: layer_scale_init_value * ones
+                    elif n.endswith("relative_position_bias_table"):
+                        p.zero_()                                                           # HF BeitRelativePositionBias: zeros
                     elif "LayerNorm.weight" in n or (("layernorm" in n or "layer_norm" in n or "layrnorm" in n) and n.endswith("weight")):
                         p.fill_(1.0)
                     elif n.endswith(".bias"):
@@ -225,15 +337,19 @@ class MM_Model(WordTableEngineModule):
             self._modules["dual_encoder"]._modules["text_model"]._modules["embeddings"]._modules["word_embeddings"].weight[pad].zero_()
 
     def _load_tower(self, sd, prefix, keymap):
+        """-> the names of the parameters that were assigned (a key whose mapped name or shape matches nothing is skipped)"""
         own = {inf["name"]: inf["param"] for inf in self._infos}
+        loaded = set()
         with torch.no_grad():
             for k, v in sd.items():
-                for strip in ("vit.", "bert.", "roberta.", ""):
+                for strip in ("vit.", "beit.", "bert.", "roberta.", ""):
                     if k.startswith(strip):
                         name = prefix + keymap(k[len(strip):])
                         if name in own and tuple(own[name].shape) == tuple(v.shape):
                             own[name].copy_(v.to(own[name].device, torch.float32))
+                            loaded.add(name)
                             break
+        return loaded
 
     def _refresh_weights(self, which):
         _lib.check(_lib.lib().mmhip_refresh_weights(self._handle, which, _lib.stream_ptr()), "refresh_weights")
@@ -254,6 +370,8 @@ class MM_Model(WordTableEngineModule):
         """keep the frozen, dropout-free image tower's outputs per post key (306 KB each, in HBM): a post seen again (every
         epoch after the first) skips the tower and the pixel transfer; results are bit-identical.  Keys are passed to
         `_engine_forward(..., vision_keys=...)` (MMLate_Model.train / eval pass the batch's data_id)."""
+        if self.drop_path_rate > 0.0:
+            raise NotImplementedError(VISION_CACHE_DROP_PATH_MESSAGE)
         rec = int(_lib.lib().mmhip_vision_record_bytes(self._handle))
         self._vcache = dict(rec=rec, cap=int(capacity_posts), slots={}, hits=0, misses=0,
                             buf=torch.empty(int(capacity_posts) * rec, dtype=torch.uint8, device=self.device_))

@@ -33,10 +33,13 @@ def build_parser():
     # reference flags, models/run_mm_late.py:21-43 (names, types, choices, defaults unchanged)
     p.add_argument("--txt_model_name", type=str, choices=["bert", "bernice", "bertweet", "roberta"], help="model name")
     p.add_argument("--img_model_name", type=str, choices=["vit", "beit", "deit", "resnet50", "resnet152", "clip", "clip336"],
-                   help="model name (clip / clip336: CLIP-ViT-L/14 vision tower at 224 / 336, additive: BASELINE config 4; use --fusion_name concat)")
+                   help="model name (vit, beit: BEiT-B/16 with its relative position bias and, in training, its stochastic depth; clip / clip336: "
+                        "CLIP-ViT-L/14 vision tower at 224 / 336, additive: BASELINE config 4, use --fusion_name concat; deit and the resnets are not built)")
     p.add_argument("--fusion_name", type=str, choices=["xatt", "concat", "attention", "concat_cnn", "aspect-att", "gmu"], help="fusion method")
     p.add_argument("--use_clip_loss", action="store_true", help="use contrastive Loss")
-    p.add_argument("--use_tim_loss", action="store_true", help="use TIM Loss")
+    p.add_argument("--use_tim_loss", action="store_true",
+                   help="use TIM Loss (with --img_model_name beit the ITM pass reuses the first pass's image tokens: one set of stochastic-depth draws "
+                        "per step, where the reference's second encoder call draws again -- DESIGN.md)")
     p.add_argument("--use_iadds_loss", action="store_true", help="use image-adds loss")
     p.add_argument("--beta_iadds", type=float, default=0.1, help="hyperparameter for iadds loss")
     p.add_argument("--beta_itc", type=float, default=0.1, help="hyperparameter for itc loss")
@@ -66,7 +69,8 @@ def build_parser():
     p.add_argument("--num_workers", type=int, default=0, help="DataLoader workers (reference: 0); 8 or more keep the image decode ahead of the GPU step (tools/loader_bench.py)")
     p.add_argument("--item_tokenize", action="store_true", help="tokenise per item like the reference instead of once per batch in the collate")
     p.add_argument("--cache_vision", type=int, default=0, metavar="POSTS",
-                   help="keep the frozen image tower's outputs of up to POSTS posts in HBM (306 KB each): epochs after the first skip the tower")
+                   help="keep the frozen image tower's outputs of up to POSTS posts in HBM (306 KB each): epochs after the first skip the tower "
+                        "(refused with --img_model_name beit while its drop_path_rate is above 0: the tower is stochastic in training)")
     p.add_argument("--itc_global", action="store_true",
                    help="data parallel: contrast every post against the gathered embeddings of ALL ranks' posts (the single-process objective on the "
                         "concatenated batch) instead of the rank's own batch; no effect in a single process")
