@@ -1,7 +1,8 @@
-"""Host-side machinery shared by the front ends over libmmhip.so (mm_late.py, mm_early.py, text_only.py): parameters as views into flat fp32
-buffers under the reference checkpoint's keys, the engine handle and its (re)creation when a batch outgrows the capacity, the dropout seed
-counter, and the trainer-side pieces every fused step shares.  Nothing here knows an architecture: a front end names its C entry points
-(`_ABI`), builds its config struct, allocates its flat buffers, re-applies its per-handle setters and binds (the hooks of EngineModule).
+"""Host-side machinery shared by the front ends over libmmhip.so (mm_late.py, mm_early.py, and one_tower.py under text_only.py and
+image_only.py): parameters as views into flat fp32 buffers under the reference checkpoint's keys, the engine handle and its (re)creation when a
+batch outgrows the capacity, the dropout seed counter, the guard words, and the trainer-side pieces every fused step shares.  Nothing here knows
+an architecture: a front end names its C entry points (`_ABI`), builds its config struct, allocates its flat buffers, re-applies its per-handle
+setters and binds (the hooks of EngineModule).
 """
 import ctypes as C
 import json
@@ -156,13 +157,33 @@ class EngineModule(nn.Module):
             self._grad_dirty = False
 
 
-class WordTableEngineModule(EngineModule):
+class GuardedEngineModule(EngineModule):
+    """engines of the mmhip_handle kind (late fusion, text only, image only; include/mmhip.h: the per-handle setters take any of them): the guard
+    words are device memory of the module that every handle is pointed at.  A subclass sets `backward_products` (None: the engine's default)."""
+
+    _loss_scale = 0.0         # of the f16 gradients (0: the engine's own); the late-fusion trainer moves it
+    _word_info = None         # no word table unless WordTableEngineModule finds one: FlatTrainer steps the whole buffer densely
+
+    def _on_registered(self):
+        # device words of every handle: [0:2] include/mmhip.h mmhip_set_guard {non-finite counter, void-step flag}; [2] the word table's
+        self._guard4 = torch.zeros(4, dtype=torch.int32, device=self.device_)
+        self._nonfinite = self._guard4[:2]
+
+    def _apply_setters(self, h):
+        lib = _lib.lib()
+        _lib.check(lib.mmhip_set_guard(h, _lib.ptr(self._nonfinite)), "set_guard")
+        if self.backward_products is not None:
+            _lib.check(lib.mmhip_set_backward_products(h, self.backward_products), "set_backward_products")
+
+
+class WordTableEngineModule(GuardedEngineModule):
     """engines whose trainable buffer is closed by a word table stepped row-lazily (late fusion, text only): the row flags shared by the
-    backward pass and mmhip_adamw_rows, and the guard words, are device memory of the module that every handle is pointed at"""
+    backward pass and mmhip_adamw_rows, like the guard words, are device memory of the module that every handle is pointed at"""
 
     _embeddings = ()          # module path of the text embeddings (they carry the position_ids buffer)
 
     def _on_registered(self):
+        super()._on_registered()
         emb = self
         for part in self._embeddings:
             emb = emb._modules[part]
@@ -170,22 +191,16 @@ class WordTableEngineModule(EngineModule):
         emb.register_buffer("position_ids", torch.arange(self.arch["max_pos"], device=self.device_).unsqueeze(0))
         self._word_info = next(i for i in self._infos if i["name"].endswith("word_embeddings.weight"))
         self._word_row_state = torch.zeros((self._word_info["shape"][0] + 3) // 4 * 4, dtype=torch.uint8, device=self.device_)
-        # device words of every handle: [0:2] include/mmhip.h mmhip_set_guard {non-finite counter, void-step flag}; [2] mmhip_set_index_counter
-        # (token ids that had to be clamped into the word table: the reference raises IndexError for them)
-        self._guard4 = torch.zeros(4, dtype=torch.int32, device=self.device_)
-        self._nonfinite, self._bad_index = self._guard4[:2], self._guard4[2:3]
-        self._loss_scale = 0.0
+        # mmhip_set_index_counter: token ids that had to be clamped into the word table (the reference raises IndexError for them)
+        self._bad_index = self._guard4[2:3]
 
     def _apply_setters(self, h):
-        # (a text-only handle is an mmhip_handle: the per-handle setters of the late-fusion family take it, include/mmhip.h)
+        super()._apply_setters(h)
         lib = _lib.lib()
         _lib.check(lib.mmhip_set_row_state(h, _lib.ptr(self._word_row_state)), "set_row_state")
-        _lib.check(lib.mmhip_set_guard(h, _lib.ptr(self._nonfinite)), "set_guard")
         _lib.check(lib.mmhip_set_index_counter(h, _lib.ptr(self._bad_index)), "set_index_counter")
         if self._loss_scale > 0:
             _lib.check(lib.mmhip_set_loss_scale(h, self._loss_scale), "set_loss_scale")
-        if self.backward_products is not None:
-            _lib.check(lib.mmhip_set_backward_products(h, self.backward_products), "set_backward_products")
 
     def _zero_grad_state(self):
         """... and no "row has a gradient" flags"""
@@ -194,7 +209,8 @@ class WordTableEngineModule(EngineModule):
 
 
 class FlatTrainer(object):
-    """what the trainers over `self.model` (an EngineModule) share.  `_moments` / `_adamw_ranges` serve WordTableEngineModule models."""
+    """what the trainers over `self.model` (an EngineModule) share.  `_moments` / `_adamw_ranges` serve GuardedEngineModule models, with a word
+    table (stepped row-lazily) or without one."""
 
     # ---- checkpoints: plain state_dict with the reference's keys
     def load_saved_model(self, model_path):
@@ -214,16 +230,17 @@ class FlatTrainer(object):
         m = self.model
         if self._opt is None:
             self._opt = (torch.zeros_like(m._flat_train), torch.zeros_like(m._flat_train))
-            m._word_row_state.bitwise_and_(1)                      # fresh moments: no row has any yet
+            if m._word_info is not None:
+                m._word_row_state.bitwise_and_(1)                  # fresh moments: no row has any yet
         return self._opt
 
     def _adamw_ranges(self, ranges, lr, weight_decay, step, grad_scale, dense=True, rows=True):
-        """staged AdamW: the dense part of each range up to the word table, then the row-lazy word table"""
+        """staged AdamW: the dense part of each range up to the word table, then the row-lazy word table (no word table: all of it is dense)"""
         m, lib = self.model, _lib.lib()
         em, ev = self._moments()
         at = lambda t, el: C.c_void_p(t.data_ptr() + el * 4)
-        V, H = m._word_info["shape"]
-        w0 = m._word_info["offset"]                                 # the word table closes the trainable buffer
+        word = m._word_info
+        w0 = word["offset"] if word is not None else float("inf")    # the word table closes the trainable buffer
         for b, e in ranges:
             dense_end = min(e, w0)
             if dense and dense_end > b:
@@ -231,7 +248,7 @@ class FlatTrainer(object):
                                                    1e-8, weight_decay, step, grad_scale, 1, _lib.stream_ptr(), _lib.ptr(m._nonfinite)), "adamw")
             if rows and e > w0:
                 # rows without gradient and without moments only decay: same values as the dense update, 1/4 of its traffic
-                _lib.check(lib.mmhip_adamw_rows_guarded(at(m._flat_train, w0), at(m._flat_grad, w0), at(em, w0), at(ev, w0), V, H,
+                _lib.check(lib.mmhip_adamw_rows_guarded(at(m._flat_train, w0), at(m._flat_grad, w0), at(em, w0), at(ev, w0), *word["shape"],
                                                         _lib.ptr(m._word_row_state), lr, 0.9, 0.999, 1e-8, weight_decay, step,
                                                         grad_scale, 1, _lib.stream_ptr(), _lib.ptr(m._nonfinite)), "adamw_rows")
 

@@ -7,22 +7,18 @@
 
 The reference classifies last_hidden[:, 0, :]; the encoder's pooler is computed there and never consumed.  Its parameters are kept (checkpoint
 keys), never computed here, receive no gradient and no optimizer step -- what torch does with `grad is None`.
-There is no CPU / eager fallback: without the built library (or without a GPU) construction raises.
+What this family shares with the image-only one -- the engine plumbing, the autograd edge, the trainer's steps, epoch loop and evaluation --
+is one_tower.py.  There is no CPU / eager fallback: without the built library (or without a GPU) construction raises.
 """
-import logging
 import math
-import os
 
-import numpy as np
 import torch
 
 from . import _lib
 from . import dist as mmdist
-from .config import MODEL_DIR_DICT, TEXT_ARCH, metric_names
-from .engine_module import FlatTrainer, WordTableEngineModule, _read_hf_dir, merge_ranges
-from .utils import agg_metrics_val
-
-logger = logging.getLogger(__name__)
+from .config import MODEL_DIR_DICT, TEXT_ARCH
+from .engine_module import WordTableEngineModule
+from .one_tower import OneTowerModule, OneTowerTrainer, tower_abi
 
 
 def default_txt_arch(arch_name):
@@ -31,76 +27,33 @@ def default_txt_arch(arch_name):
     return a
 
 
-class _TxtFunction(torch.autograd.Function):
-    """autograd edge around the engine so that the reference's loss.backward() (text_only.py:163) works on the returned logits"""
-
-    @staticmethod
-    def forward(ctx, model, ids, mask, type_ids, *params):
-        out = model._engine_forward(ids, mask, type_ids)
-        ctx.model, ctx.token = model, model._fwd_token
-        return out
-
-    @staticmethod
-    def backward(ctx, d_logits):
-        model = ctx.model
-        if ctx.token != model._fwd_token:
-            raise RuntimeError("text-only model: backward() after another forward(); the engine keeps one set of activations")
-        return (None,) * 4 + tuple(model._engine_backward_autograd(d_logits))
-
-
-class _TextOnly(WordTableEngineModule):
+class _TextOnly(OneTowerModule, WordTableEngineModule):
     """shared body of BERT and BERNICE.  Keyword-only extras are additive, as in MM_Model: `arch` overrides (layer count, vocab ... for tests),
     `arch_name` (the TEXT_ARCH preset when model_dir holds no checkpoint), `dtype` ('bf16' | 'f16' | 'bf16x3'), `max_posts` / `max_text_len`
     (capacity), `device`, `seed`, `backward_products` (bf16x3 only)."""
 
     _default_arch_name = "bernice"
-    # a text-only handle is an mmhip_handle: the stage ranges of the late-fusion family are read through its entry points (include/mmhip.h)
-    _ABI = dict(create="mmhip_txt_create", destroy="mmhip_txt_destroy", param_count="mmhip_txt_param_count", param_info_at="mmhip_txt_param_info_at",
-                workspace_bytes="mmhip_txt_workspace_bytes", num_stages="mmhip_num_backward_stages", stage_grad_range="mmhip_stage_grad_range")
+    _family, _what, _ABI = "txt", "text-only", tower_abi("txt")
+    _Config, _capacity_names = _lib.TxtConfig, ("max_posts", "max_text_len")
     _embeddings = ("bert_model", "embeddings")
 
     def __init__(self, model_dir, num_labels, dropout=0.1, *, arch=None, arch_name=None, dtype="bf16", max_posts=64, max_text_len=128,
                  device=None, seed=0, backward_products=None):
         super().__init__()
-        if not torch.cuda.is_available():
-            raise _lib.MMHipError("the text-only model needs an MI355X (gfx950) GPU: the HIP path has no CPU fallback")
-        self.num_labels = int(num_labels)
-        self.device_ = torch.device(device if device is not None else f"cuda:{int(os.environ.get('LOCAL_RANK', 0))}")
-        a = default_txt_arch(arch_name or self._default_arch_name)
-        cfg, sd = _read_hf_dir(model_dir or "")
-        if cfg:
-            a.update(vocab=cfg["vocab_size"], max_pos=cfg["max_position_embeddings"], type_vocab=cfg.get("type_vocab_size", 1),
-                     layers=cfg["num_hidden_layers"], ln_eps_txt=cfg.get("layer_norm_eps", 1e-12), pad_id=cfg.get("pad_token_id", a["pad_id"]),
-                     p_hidden=cfg.get("hidden_dropout_prob", 0.1), p_attn=cfg.get("attention_probs_dropout_prob", 0.1),
-                     txt_kind="bert" if cfg.get("model_type", "") == "bert" else "xlmr")
-        a.update(arch or {})
-        self.arch, self.dtype_name = a, dtype
-        if backward_products is not None and (dtype != "bf16x3" or int(backward_products) not in (1, 2, 3)):
-            raise ValueError("backward_products is 1, 2 or 3 and belongs to dtype='bf16x3'")
-        self.backward_products = None if backward_products is None else int(backward_products)
-        self._cfg_kw = dict(hidden=a["hidden"], heads=a["heads"], inter=a["inter"], layers=a["layers"], vocab=a["vocab"], max_pos=a["max_pos"],
-                            type_vocab=a["type_vocab"], txt_kind=_lib.TXT_XLMR if a["txt_kind"] == "xlmr" else _lib.TXT_BERT, pad_id=a["pad_id"],
-                            ln_eps=a["ln_eps_txt"], num_labels=self.num_labels, p_hidden=a["p_hidden"], p_attn=a["p_attn"], p_head=float(dropout),
-                            dtype={"bf16": _lib.BF16, "f16": _lib.F16, "bf16x3": _lib.BF16X3}[dtype])
-        self._init_engine(int(seed) if seed is not None else int(torch.initial_seed()))
-        self._create_engine(max_posts, max_text_len)
-        self._init_weights()
-        if sd is not None:
-            self._load_tower(sd)
-        self._refresh_weights()
+        self._build(model_dir, num_labels, default_txt_arch(arch_name or self._default_arch_name), arch, dtype, (max_posts, max_text_len), device,
+                    seed, backward_products, p_head=float(dropout))
 
-    # ------------------------------------------------------------------ engine / buffers
-    def _config(self, max_posts, max_text_len):
-        return _lib.TxtConfig(max_posts=int(max_posts), max_text_len=int(max_text_len), loss_scale=float(getattr(self, "_loss_scale", 0.0)), **self._cfg_kw)
+    @staticmethod
+    def _arch_from_hf(cfg, a):
+        return dict(vocab=cfg["vocab_size"], max_pos=cfg["max_position_embeddings"], type_vocab=cfg.get("type_vocab_size", 1),
+                    layers=cfg["num_hidden_layers"], ln_eps_txt=cfg.get("layer_norm_eps", 1e-12), pad_id=cfg.get("pad_token_id", a["pad_id"]),
+                    p_hidden=cfg.get("hidden_dropout_prob", 0.1), p_attn=cfg.get("attention_probs_dropout_prob", 0.1),
+                    txt_kind="bert" if cfg.get("model_type", "") == "bert" else "xlmr")
 
-    def _allocate_flats(self, h):
-        n = _lib.lib().mmhip_txt_numel(h)
-        self._flat_train = torch.zeros(n, dtype=torch.float32, device=self.device_)
-        self._flat_grad = torch.zeros(n, dtype=torch.float32, device=self.device_)
-        return {1: self._flat_train}
-
-    def _bind(self, h):
-        _lib.check(_lib.lib().mmhip_txt_bind(h, _lib.ptr(self._flat_train), _lib.ptr(self._flat_grad), _lib.ptr(self._ws), self._ws.numel()), "txt_bind")
+    @staticmethod
+    def _cfg_keywords(a):
+        return dict(vocab=a["vocab"], max_pos=a["max_pos"], type_vocab=a["type_vocab"], pad_id=a["pad_id"], ln_eps=a["ln_eps_txt"],
+                    txt_kind=_lib.TXT_XLMR if a["txt_kind"] == "xlmr" else _lib.TXT_BERT)
 
     def _init_weights(self):
         """HF initializer_range 0.02 for the encoder, nn.Linear defaults for the classifier (reference: from_pretrained + nn.Linear)"""
@@ -120,7 +73,7 @@ class _TextOnly(WordTableEngineModule):
                     p.uniform_(-bound, bound, generator=g)
             self._modules["bert_model"]._modules["embeddings"]._modules["word_embeddings"].weight[self.arch["pad_id"]].zero_()
 
-    def _load_tower(self, sd):
+    def _load_checkpoint(self, sd):
         own = {inf["name"]: inf["param"] for inf in self._infos}
         with torch.no_grad():
             for k, v in sd.items():
@@ -130,19 +83,7 @@ class _TextOnly(WordTableEngineModule):
                         own[name].copy_(v.to(own[name].device, torch.float32))
                         break
 
-    def _refresh_weights(self):
-        _lib.check(_lib.lib().mmhip_txt_refresh_weights(self._handle, _lib.stream_ptr()), "txt_refresh_weights")
-        self._weights_version = self._flat_train._version
-
-    def _ensure(self, B, T):
-        cap_b, cap_t = self._capacity
-        if B > cap_b or T > cap_t:
-            self._create_engine(max(B, cap_b), max(T, cap_t))
-            self._refresh_weights()
-        elif self._weights_version != self._flat_train._version:
-            self._refresh_weights()        # parameters were modified in place (optimizer.step / load_state_dict)
-
-    def _inputs(self, ids, mask, type_ids):
+    def _inputs(self, ids, mask, type_ids=None):
         dev = self.device_
         ids = ids.to(dev, torch.int64).contiguous()
         mask = mask.to(dev, torch.int64).contiguous()
@@ -154,43 +95,20 @@ class _TextOnly(WordTableEngineModule):
                 raise ValueError(f"token_type_ids {tuple(type_ids.shape)} for ids {tuple(ids.shape)}")
         return ids, mask, type_ids
 
-    def _engine_forward(self, ids, mask, type_ids=None, seed=None):
-        ids, mask, type_ids = self._inputs(ids, mask, type_ids)
+    def _seeded(self, seed, ids, mask, type_ids):
+        """one dropout seed per engine call unless the caller brings one; -> the arguments both native calls begin with, B, T, seed"""
         B, T = ids.shape
-        self._ensure(B, T)
         seed = self._next_seed() if seed is None else seed
-        logits = torch.empty(B, self.num_labels, device=self.device_)
-        _lib.check(_lib.lib().mmhip_txt_forward(self._handle, _lib.ptr(ids), _lib.ptr(mask), _lib.ptr(type_ids), B, T, int(self.training), seed,
-                                                _lib.ptr(logits), _lib.stream_ptr()), "txt_forward")
-        self._fwd_token += 1
         self._last = dict(B=B, T=T, seed=seed, ids=ids)
-        return logits
+        return [_lib.ptr(ids), _lib.ptr(mask), _lib.ptr(type_ids)], B, T, seed
 
-    def trainable_infos(self):
-        """parameters that receive a gradient: everything but the never-consumed pooler (MMHIP_G_NEVER)"""
-        return [i for i in self._infos if i["group"] != _lib.G_NEVER]
+    def _forward_args(self, seed, *inputs):
+        ptrs, B, T, seed = self._seeded(seed, *inputs)
+        return ptrs + [B, T, int(self.training), seed]
 
-    def active_ranges(self):
-        """merged [begin, end) element ranges of the flat buffer that AdamW steps"""
-        return merge_ranges((i["offset"], i["numel"]) for i in self.trainable_infos())
-
-    def _engine_backward(self, d_logits=None):
-        """gradient of the last forward into the flat gradient buffer (cleared first); d_logits None: the one mmhip_txt_loss left in the handle"""
-        self._zero_grad_state()
-        if d_logits is not None:
-            d_logits = d_logits.to(self.device_, torch.float32).contiguous()
-        _lib.check(_lib.lib().mmhip_txt_backward(self._handle, _lib.ptr(d_logits), _lib.stream_ptr()), "txt_backward")
-        self._grad_dirty = True
-
-    def _engine_backward_autograd(self, d_logits):
-        self._engine_backward(d_logits)
-        return [None if inf["group"] == _lib.G_NEVER else self._flat_grad[inf["offset"]: inf["offset"] + inf["numel"]].view(inf["shape"]).clone()
-                for inf in self._infos]
-
-    def _forward(self, ids, mask, type_ids):
-        if torch.is_grad_enabled() and any(i["param"].requires_grad for i in self._infos):
-            return _TxtFunction.apply(self, ids, mask, type_ids, *[i["param"] for i in self._infos])
-        return self._engine_forward(ids, mask, type_ids)
+    def _step_args(self, seed, onehot, cw, *inputs):
+        ptrs, B, T, seed = self._seeded(seed, *inputs)
+        return ptrs + [_lib.ptr(onehot), _lib.ptr(cw), B, T, seed]
 
 
 class BERNICE(_TextOnly):
@@ -198,7 +116,7 @@ class BERNICE(_TextOnly):
     _default_arch_name = "bernice"
 
     def forward(self, ids, mask):
-        return self._forward(ids, mask, None)
+        return self._logits(ids, mask, None)
 
 
 class BERT(_TextOnly):
@@ -207,12 +125,15 @@ class BERT(_TextOnly):
     _default_arch_name = "bert"
 
     def forward(self, ids, mask, token_type_ids):
-        return self._forward(ids, mask, token_type_ids)
+        return self._logits(ids, mask, token_type_ids)
 
 
 # =====================================================================================================================
-class TextModel(FlatTrainer):
-    """reference models/text_only.py:68-268.  `train()` / `eval()` keep the reference's semantics and return dictionaries; the step is fused."""
+class TextModel(OneTowerTrainer):
+    """reference models/text_only.py:68-268.  A step takes `ids, mask, token_type_ids, onehot, class_weight, lr, weight_decay, step`."""
+
+    _overflow_note = "step(s) were skipped"
+    _eval_line = "loss: {:.4f} acc: {:.4f}\n"
 
     def __init__(self, config, model_name, freeze=False, **model_kw):
         if freeze:
@@ -239,7 +160,6 @@ class TextModel(FlatTrainer):
         self.model = cls(self.model_dir, self.num_labels, dropout=self.dropout, **model_kw)
         self.with_types = model_name not in {"roberta", "bernice"}
         self.device = self.model.device_
-        self._opt = None
 
     # ---- data
     def load_data(self, data, testing=False, eval_txt_test=False, task_name=None):
@@ -266,115 +186,11 @@ class TextModel(FlatTrainer):
         to = lambda t: t.to(self.device, non_blocking=True)
         return to(b["input_ids"]), to(b["attention_mask"]), (to(b["token_type_ids"]) if "token_type_ids" in b else None)
 
-    # ---- one fused training step on device tensors -> (loss[1] device tensor, n_correct[1] device tensor)
-    def train_step(self, ids, mask, token_type_ids, onehot, class_weight, lr, weight_decay, step, seed=None):
-        m = self.model
-        if not m.training:
-            m.train()
-        m._clean_grad()
-        ids, mask, token_type_ids = m._inputs(ids, mask, token_type_ids if self.with_types else None)
-        B, T = ids.shape
-        m._ensure(B, T)
-        em, ev = self._moments()
-        onehot = onehot.to(self.device, torch.int64).contiguous()
-        cw = None if class_weight is None else class_weight.to(self.device, torch.float32).contiguous()
-        loss = torch.empty(1, device=self.device)
-        ncorr = torch.empty(1, dtype=torch.int32, device=self.device)
-        seed = m._next_seed() if seed is None else seed
-        m._last = dict(B=B, T=T, seed=seed, ids=ids)
-        _lib.check(_lib.lib().mmhip_txt_train_step(m._handle, _lib.ptr(ids), _lib.ptr(mask), _lib.ptr(token_type_ids), _lib.ptr(onehot), _lib.ptr(cw),
-                                                   B, T, seed, _lib.ptr(em), _lib.ptr(ev), lr, 0.9, 0.999, 1e-8, weight_decay, step,
-                                                   _lib.ptr(loss), _lib.ptr(ncorr), _lib.stream_ptr()), "txt_train_step")
-        m._fwd_token += 1
-        m._weights_version = m._flat_train._version          # the refresh inside the call keeps the 16-bit copies current
-        return loss, ncorr
+    def _item(self, dl):
+        return self._batch(dl), dl["target"]
 
-    # ---- the same step as separate calls (forward, loss, backward, AdamW): what the fused call is checked against
-    def staged_step(self, ids, mask, token_type_ids, onehot, class_weight, lr, weight_decay, step, seed=None):
-        m, lib = self.model, _lib.lib()
-        if not m.training:
-            m.train()
-        m._clean_grad()
-        m._engine_forward(ids, mask, token_type_ids if self.with_types else None, seed=seed)
-        onehot = onehot.to(self.device, torch.int64).contiguous()
-        cw = None if class_weight is None else class_weight.to(self.device, torch.float32).contiguous()
-        loss = torch.empty(1, device=self.device)
-        ncorr = torch.empty(1, dtype=torch.int32, device=self.device)
-        _lib.check(lib.mmhip_txt_loss(m._handle, _lib.ptr(onehot), _lib.ptr(cw), _lib.ptr(loss), _lib.ptr(ncorr), _lib.stream_ptr()), "txt_loss")
-        m._engine_backward(None)
-        self._adamw_ranges(m.active_ranges(), lr, weight_decay, step, 1.0)
-        m._grad_dirty = False
-        m._refresh_weights()
-        return loss, ncorr
+    def _engine_inputs(self, ids, mask, token_type_ids):
+        return ids, mask, token_type_ids if self.with_types else None
 
     def _clamped_message(self, n):
         return f"index out of range in self: {n} token id(s) outside the embedding tables reached the text tower"
-
-    def check_overflow(self):
-        n = int(self.model._nonfinite[0].item()) - getattr(self, "_nf_seen", 0)
-        if n > 0:
-            self._nf_seen = getattr(self, "_nf_seen", 0) + n
-            if self.model.dtype_name != "f16":
-                raise FloatingPointError(f"non-finite gradients met {n} times ({self.model.dtype_name}): the run has diverged")
-            logger.warning("f16 gradient overflow: %d step(s) were skipped on the device", n)
-        return max(n, 0)
-
-    def train(self, dataloader, val_dataloader, epochs, loss_fn=None, lr=1e-5, weight_decay=0.00025, te_dataloader=None, model_path=None,
-              val_filename=None, te_filename=None, class_weight=None, log_every=50):
-        """reference :124-202.  `loss_fn` is accepted for signature parity: the class weights it carries (nn.CrossEntropyLoss(weight=w),
-        run_txt.py:54) are what the fused step uses."""
-        import pandas as pd
-        class_weight = self._class_weight(loss_fn, class_weight)
-        res_val, res_te, step = [], [], 0
-        for epoch in range(epochs):
-            print(epoch)
-            for it, dl in enumerate(dataloader):
-                ids, mask, tt = self._batch(dl)
-                step += 1
-                loss, ncorr = self.train_step(ids, mask, tt, dl["target"], class_weight, lr, weight_decay, step)
-                if log_every and it % log_every == 0:          # the reference syncs and prints every step (:166-171)
-                    self.check_overflow()
-                    n = ids.shape[0]
-                    print(f"Got {int(ncorr.item())} / {n} with accuracy {float(ncorr.item()) / n * 100:.2f} loss {loss[0].item():.4f}")
-            for loader, store, fname, tag in ((val_dataloader, res_val, val_filename, "val"), (te_dataloader, res_te, te_filename, "test")):
-                if loader is None:
-                    continue
-                print(tag)
-                r = self.eval(loader, class_weight=class_weight)
-                r["epoch"] = epoch
-                store.append(r)
-                if fname is not None and (epoch % 2 == 0 or epoch == epochs - 1):
-                    pd.DataFrame(agg_metrics_val(store, metric_names, self.num_labels)).to_csv(fname, index=False)
-                    logger.info("%s saved!", fname)
-        if model_path is not None:
-            self.save_model(model_path)
-            logger.info("%s saved", model_path)
-
-    def eval(self, dataloader, loss_fn=None, class_weight=None):
-        """reference :204-268 -> {"data_id", "loss" (mean of the batch losses), "predictions", "labels"}"""
-        m, lib = self.model, _lib.lib()
-        class_weight = self._class_weight(loss_fn, class_weight)
-        cw = None if class_weight is None else class_weight.to(self.device, torch.float32).contiguous()
-        m.eval()
-        ids_all, preds, labels, losses, accs = [], [], [], [], []
-        with torch.no_grad():
-            for dl in dataloader:
-                ids, mask, tt = self._batch(dl)
-                out = m._engine_forward(ids, mask, tt)
-                onehot = dl["target"].to(self.device, torch.int64).contiguous()
-                loss = torch.empty(1, device=self.device)
-                _lib.check(lib.mmhip_txt_loss(m._handle, _lib.ptr(onehot), _lib.ptr(cw), _lib.ptr(loss), None, _lib.stream_ptr()), "txt_loss")
-                losses.append(loss)
-                pred, target = out.argmax(dim=1), onehot.argmax(dim=1)
-                accs.append((pred == target).float().mean().reshape(1) * 100)
-                preds.append(pred)
-                labels.append(target)
-                if "data_id" in dl:
-                    ids_all.append(dl["data_id"])
-        eval_loss = float(torch.cat(losses).mean().item()) if losses else float("nan")
-        eval_acc = float(torch.cat(accs).mean().item()) if accs else float("nan")
-        print(f"loss: {eval_loss:.4f} acc: {eval_acc:.4f}\n")
-        self.check_indices()
-        return {"data_id": torch.cat(ids_all).cpu().numpy() if ids_all else np.zeros(0, dtype=np.int64), "loss": eval_loss,
-                "predictions": torch.cat(preds).cpu().numpy() if preds else np.zeros(0, dtype=np.int64),
-                "labels": torch.cat(labels).cpu().numpy() if labels else np.zeros(0, dtype=np.int64)}

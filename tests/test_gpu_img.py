@@ -351,6 +351,43 @@ def test_capacity_growth_between_training_steps_leaves_no_trace(monkeypatch):
     assert res[0][0].isfinite().all() and float(res[0][3][-1]) > 0
 
 
+def test_eval_is_the_forward_and_loss_calls_over_the_loader(capsys):
+    """ImageModel.eval over two loader items (2 images and 1 image of 192 px, as the dataset hands them: [n, 1, 3, S, S]; 1 layer, hidden 128,
+    2 heads) against what this test computes from _engine_forward and mmhip_img_loss on the same items: the loss as the same float computation
+    (the mean of the batch losses, not of the images), predictions, labels, data ids, the printed line"""
+    from smtc_amd.image_only import ImageModel
+    tm = ImageModel(2, 3, "vit", arch=dict(layers=1, hidden=128, heads=2, inter=256, image=192), dtype="bf16", device=DEV, seed=3)
+    m, lib = tm.model, _lib.lib()
+    assert m._capacity == (2,)
+    g, items = torch.Generator().manual_seed(11), []
+    for n, first in ((2, 0), (1, 2)):
+        items.append({"pixel_values": torch.rand(n, 1, 3, 192, 192, generator=g) * 2 - 1, "data_id": torch.arange(first, first + n),
+                      "labels": torch.eye(3, dtype=torch.int64)[torch.randint(0, 3, (n,), generator=g)]})
+    cw = W.to(DEV)
+    m.eval()
+    losses, accs, preds, labels = [], [], [], []
+    with torch.no_grad():
+        for it in items:
+            out = m._engine_forward(it["pixel_values"])
+            onehot, loss = it["labels"].to(DEV), torch.empty(1, device=DEV)
+            _lib.check(lib.mmhip_img_loss(m._handle, _lib.ptr(onehot), _lib.ptr(cw), _lib.ptr(loss), None, _lib.stream_ptr()), "img_loss")
+            losses.append(loss)
+            preds.append(out.argmax(dim=1).cpu())
+            labels.append(it["labels"].argmax(dim=1))
+            accs.append((preds[-1] == labels[-1]).float().mean().reshape(1) * 100)
+    want_loss, want_acc = float(torch.cat(losses).mean().item()), float(torch.cat(accs).mean().item())
+    assert math.isfinite(want_loss) and losses[0].item() != losses[1].item()
+    capsys.readouterr()
+    r = tm.eval(items, class_weight=W)
+    assert capsys.readouterr().out == f"test loss: {want_loss:.4f} test acc: {want_acc:.4f}\n\n"
+    assert list(r) == ["data_id", "loss", "predictions", "labels"] and type(r["loss"]) is float and r["loss"] == want_loss
+    for k, want in (("predictions", torch.cat(preds)), ("labels", torch.cat(labels)), ("data_id", torch.arange(3))):
+        assert r[k].dtype == np.int64 and r[k].tolist() == want.tolist(), k
+    assert not m.training and m._last == {"B": 1}
+    empty = tm.eval([], class_weight=W)
+    assert math.isnan(empty["loss"]) and all(empty[k].dtype == np.int64 and empty[k].shape == (0,) for k in ("data_id", "predictions", "labels"))
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_hf_directory_loads(dtype, tmp_path):
     """a directory written by the installed transformers (its own key generation) loads -- every parameter -- and the eval logits agree with that model;

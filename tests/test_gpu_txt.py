@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -355,6 +356,54 @@ def test_training_steps(kind):
     r = tm.eval([{"ids": c["ids"], "mask": c["mask"], "token_type_ids": c["tt"] if c["tt"] is not None else torch.zeros_like(c["ids"]),
                   "target": c["onehot"], "data_id": torch.arange(4)}], class_weight=c["w"])
     assert set(r) == {"data_id", "loss", "predictions", "labels"} and math.isfinite(r["loss"]) and r["predictions"].shape == (4,)
+
+
+def test_eval_is_the_forward_and_loss_calls_over_the_loader(capsys):
+    """TextModel.eval over two loader items (3 and 2 posts of 8 tokens, padded rows, BERT token types; 1 layer, hidden 128, 2 heads) against what
+    this test computes from _engine_forward and mmhip_txt_loss on the same items: the loss as the same float computation (the mean of the batch
+    losses, not of the posts), predictions, labels, data ids, the printed line; and the evaluation ends with the clamped-index check"""
+    from smtc_amd.text_only import TextModel
+
+    class Cfg:
+        batch_size, num_labels, max_length, dropout, use_loss_correction = 3, 3, 8, 0.1, False
+    name, a = KINDS["bert"]
+    tm = TextModel(Cfg, name, arch=dict(a, layers=1, hidden=128, heads=2, inter=256, vocab=50), dtype="bf16", device=DEV, seed=3)
+    m, lib = tm.model, _lib.lib()
+    assert m._capacity == (3, 8)
+    g, items = torch.Generator().manual_seed(11), []
+    for n, first in ((3, 0), (2, 3)):
+        mask = torch.ones(n, 8, dtype=torch.int64)
+        mask[n - 1, 5:] = 0
+        ids = torch.randint(1, 50, (n, 8), generator=g) * mask
+        tt = (torch.arange(8).expand(n, 8) >= 3).long() * mask
+        items.append({"ids": ids, "mask": mask, "token_type_ids": tt, "target": torch.eye(3, dtype=torch.int64)[torch.randint(0, 3, (n,), generator=g)],
+                      "data_id": torch.arange(first, first + n)})
+    w = torch.tensor([1.0, 2.0, 0.5])
+    cw = w.to(DEV)
+    m.eval()
+    losses, accs, preds, labels = [], [], [], []
+    with torch.no_grad():
+        for it in items:
+            out = m._engine_forward(*tm._batch(it))
+            onehot, loss = it["target"].to(DEV), torch.empty(1, device=DEV)
+            _lib.check(lib.mmhip_txt_loss(m._handle, _lib.ptr(onehot), _lib.ptr(cw), _lib.ptr(loss), None, _lib.stream_ptr()), "txt_loss")
+            losses.append(loss)
+            preds.append(out.argmax(dim=1).cpu())
+            labels.append(it["target"].argmax(dim=1))
+            accs.append((preds[-1] == labels[-1]).float().mean().reshape(1) * 100)
+    want_loss, want_acc = float(torch.cat(losses).mean().item()), float(torch.cat(accs).mean().item())
+    assert math.isfinite(want_loss) and losses[0].item() != losses[1].item()
+    capsys.readouterr()
+    r = tm.eval(items, class_weight=w)
+    assert capsys.readouterr().out == f"loss: {want_loss:.4f} acc: {want_acc:.4f}\n\n"
+    assert list(r) == ["data_id", "loss", "predictions", "labels"] and type(r["loss"]) is float and r["loss"] == want_loss
+    for k, want in (("predictions", torch.cat(preds)), ("labels", torch.cat(labels)), ("data_id", torch.arange(5))):
+        assert r[k].dtype == np.int64 and r[k].tolist() == want.tolist(), k
+    assert not m.training and set(m._last) == {"B", "T", "seed", "ids"} and (m._last["B"], m._last["T"]) == (2, 8)
+    bad = dict(items[1], ids=items[1]["ids"].clone())
+    bad["ids"][0, 1] = 50                                   # == vocab: clamped into the word table by the engine, counted
+    with pytest.raises(IndexError, match="1 token id"):
+        tm.eval([bad], class_weight=w)
 
 
 @pytest.mark.parametrize("kind", ["xlmr", "bert"])
