@@ -332,7 +332,9 @@ int mmhip_image_preprocess(const uint8_t* images, const int32_t* plan_host, cons
  * bf16x3 parity products on fp32 matrices).  Matrices are row-major with explicit leading dimensions (elements). */
 /* C[M,N] = epilogue(A[M,K] . B[N,K]^T): + bias[N] (fp32, may be NULL); act: 0 none, 1 exact-erf GELU, 2 tanh;
  * aux_pre (may be NULL) receives the value before the activation; mul_gelu_grad_of (may be NULL): value *= gelu'(that);
- * dropout (p > 0) on element index m*N+n with (seed, stream_id); + residual (may be NULL); out_f32 selects fp32 C. */
+ * dropout (p > 0) on element index m*N+n with (seed, stream_id); + residual (may be NULL); out_f32 selects fp32 C.
+ * force_slow (here and in mmhip_op_gemm_tn): bit 0 = the generic kernel; bits 4.. = a tile code / TN variant to force (0 = the launcher's rules; the
+ * codes are listed at mmhip_op_last_gemm_path).  A code no launcher has: MMHIP_E_INVALID. */
 int mmhip_op_gemm_nt(int dtype, const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K,
                      const float* bias, int act, void* aux_pre, int ldaux, const void* mul_gelu_grad_of, int ldmul,
                      float p_drop, uint64_t seed, uint32_t stream_id, const void* residual, int ldres, int out_f32,
@@ -501,13 +503,13 @@ int mmhip_op_cast(int dtype, const float* src, void* dst, uint64_t n, int transp
  *              5 parity direct (128 x 128), 6 parity small (few rows, K over the waves), 7 parity scratch-split (operand planes copied, then the deep-pipelined
  *              tile), 8 parity plane pairs through the deep-pipelined tile
  *       out[1] tile code actually used -- the force_slow >> 4 codes: 1 = 128x128, 6 = 128x192, 9 = role-specialised 256x128, 10 = 128x96, 12 = role-specialised
- *              256x96, 20 / 21 = 128x128 on a 4- / 3-deep ring, 13 / 15 = deep-pipelined 256x256 one-shot / persistent, 14 / 16 = 256x128, 17 / 18 = 256x192;
+ *              256x96, 21 = 128x128 on a 3-deep ring, 13 / 15 = deep-pipelined 256x256 one-shot / persistent, 14 / 16 = 256x128, 17 / 18 = 256x192;
  *              family 4: the number of K slices; families 1, 5, 6: 0
  *       out[2] deep-pipelined tiles: epilogue class 0 plain (bias / dropout / residual), 1 GELU, 2 gelu', 3 any (run-time flags); -1 otherwise
  *       out[3] 1 = the persistent loop ran more than one tile per workgroup;  out[4] workgroups, out[5] tiles, out[6] problems in the launch, out[7] 0
  *   TN  out[0] family bits: 1 generic kernel, 2 tile kernel, 4 parity direct kernel, 8 parity scratch-split (through the tile kernel), 16 parity plane pairs
- *       out[1] variant of the tile kernel actually used (1 .. 5: 128x128 2-stage, 128x128 4-stage, 256x128 3-stage, role-specialised 256x128, role-specialised
- *              128x128; 3 / 4 fall back to 1 when an Nn is not a multiple of 256); 0 = tile kernel not used
+ *       out[1] variant of the tile kernel actually used (1 = 128x128 2-stage, 4 = role-specialised 256x128, the default; 4 falls back to 1 when an
+ *              Nn is not a multiple of 256); 0 = tile kernel not used
  *       out[2] problems on the tile kernel, out[3] problems on the generic kernel, out[4] launches of the tile kernel (a group flushes every
  *              mmhip_tn_max_group() problems), out[5] problems on the parity direct kernel, out[6] parity scratch-split problems, out[7] 0 */
 int mmhip_op_last_gemm_path(int which, int32_t* out);

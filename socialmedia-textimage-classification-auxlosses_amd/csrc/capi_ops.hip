@@ -90,6 +90,7 @@ int mmhip_op_gemm_nt(int dtype, const void* A, int lda, const void* B, int ldb, 
                      float p_drop, uint64_t seed, uint32_t stream_id, const void* residual, int ldres, int out_f32,
                      int force_slow, void* stream) {
     if (!A || !B || !C || M < 0 || N < 1 || K < 1 || (dtype != MMHIP_BF16 && dtype != MMHIP_F16 && dtype != MMHIP_F32)) return MMHIP_E_INVALID;
+    if ((force_slow >> 4) && !nt_tile_known(force_slow >> 4)) return MMHIP_E_INVALID;      // a tile code no launcher has
     G g(A, lda, B, ldb, C, ldc, M, N, K);
     if (bias) g.bias(bias);
     if (act == 1) g.gelu();
@@ -124,6 +125,7 @@ int mmhip_tn_max_group(void) { return GEMM_TN_MAX_GROUP; }
 int mmhip_op_gemm_tn(int dtype, const void* A, int lda, const void* B, int ldb, float* C, int ldc, int M, int Nn, int Nc,
                      int accumulate, int force_slow, float* colsum, void* stream) {
     if (!A || !B || !C || M < 1 || Nn < 1 || Nc < 1 || (dtype != MMHIP_BF16 && dtype != MMHIP_F16 && dtype != MMHIP_F32)) return MMHIP_E_INVALID;
+    if ((force_slow >> 4) && !tn_variant_known(force_slow >> 4)) return MMHIP_E_INVALID;      // a variant no launcher has
     GemmTNProblem p{A, B, C, M, Nn, Nc, lda, ldb, ldc, 0, colsum};
     size_t xb = dtype == MMHIP_F32 && !force_slow ? x3_tn_scratch_bytes(M, Nn, Nc) : 0;
     void* xw = xb ? ops_x3_scratch(xb, stream) : nullptr;

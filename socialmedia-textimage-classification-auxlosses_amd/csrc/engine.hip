@@ -136,8 +136,6 @@ struct mmhip_engine {
     // 2304 / 768 / 3072 columns = 288 / 96 / 384 tiles = 3 / 1 / 4 rounds of 96; 12608 rows = 450 / 150 / 600 tiles = 2.8 / 0.94 / 3.75 rounds
     // of 160) instead of racing for CUs launch by launch.  cur_part: the caps of the forward being enqueued (0 = off).
     int part[2] = {-1, -1}, cur_part[2] = {0, 0}; bool part_auto = false;
-    int part_bwd = -1;         // MMHIP_PART_BWD=n: the backward's activation-gradient GEMMs as persistent 256 x 256-tile launches of at most n workgroups
-                               // (the grouped weight-gradient GEMM of the layer above runs beside them on the side stream)
     // mmhip_step_spans: timing events at the phase ends of the last forward / train step (0 fork, 1 image tower end, 2 text tower end,
     // 3 forward end, 4 backward end, 5 step end); recorded only while enabled
     int spans_on = 0; hipEvent_t span_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; bool span_set[6] = {false, false, false, false, false, false};
@@ -617,33 +615,6 @@ int run_gemm(mmhip_engine& e, G& g, hipStream_t s) {
     CHECK_HIP(launch_gemm_nt(g.a, e.dt(), s));
     return 0;
 }
-// two GEMMs of equal N and K (the two towers' same-named GEMM of one layer) in ONE persistent launch; falls back to two launches
-int run_gemm_pair(mmhip_engine& e, G& g0, G& g1, hipStream_t s) {
-    const bool pairable = (e.dt() == DT_BF16 || e.dt() == DT_F16 || (e.dt() == DT_F32 && g0.a.a_pair && g1.a.a_pair)) && g0.a.N == g1.a.N && g0.a.K == g1.a.K;
-    mmhip_engine::Ev* ev = nullptr;
-    if (e.timing && pairable) {
-        if (e.ev_used == e.evs.size()) {
-            mmhip_engine::Ev n;
-            CHECK_HIP(hipEventCreate(&n.a));
-            CHECK_HIP(hipEventCreate(&n.b));
-            e.evs.push_back(n);
-        }
-        ev = &e.evs[e.ev_used];
-        CHECK_HIP(hipEventRecord(ev->a, s));
-    }
-    if (pairable && launch_gemm_nt8_pair(g0.a, g1.a, e.dt(), 0, s)) {
-        CHECK_HIP(hipGetLastError());
-        if (ev) {
-            ev->flops = 2.0 * ((double)g0.a.M + g1.a.M) * (double)g0.a.N * g0.a.K;
-            ev->M = g0.a.M + g1.a.M; ev->N = g0.a.N; ev->K = g0.a.K; ev->flags = g0.a.flags | g1.a.flags; ev->tile = -2; ev->cus = 0;     // -2: a pair
-            CHECK_HIP(hipEventRecord(ev->b, s));
-            e.ev_used++;
-        }
-        return 0;
-    }
-    CHECK_RC(run_gemm(e, g0, s));
-    return run_gemm(e, g1, s);
-}
 
 // ------------------------------------------------------------------------------------------------ side stream
 int side_init(mmhip_engine& e) {
@@ -653,7 +624,7 @@ int side_init(mmhip_engine& e) {
     // The forward's two towers race for the CUs: whichever chain is longer should not be the one that waits.  The image
     // tower gets the high-priority stream when it is the longer chain (plain batch: 34.9 vs 22.3 GF per post), the
     // normal one when the text pass is doubled by the ITM posts.  Measured same-box: -0.17 ms/step on config 2; the
-    // same high priority on config 3 costs +0.38 ms.  MMHIP_VIT_PRIO=0/1 forces the choice.
+    // same high priority on config 3 costs +0.38 ms.
     CHECK_HIP(pool_stream(POOL_SIDE, &e.side));
     CHECK_HIP(pool_stream(POOL_VIT, &e.side_vit[0]));
     CHECK_HIP(pool_stream(POOL_VIT_HI, &e.side_vit[1]));
@@ -701,9 +672,9 @@ int refresh_patch(mmhip_engine& e, const float* base, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------------ forward pieces
-// Every launch of a tower's forward is written once, here.  text_forward, vit_forward and towers_forward_lockstep below are orderings of these pieces
+// Every launch of a tower's forward is written once, here.  text_forward and vit_forward below are orderings of these pieces
 // on the streams they name: a piece takes its stream from the caller and never chooses one (run_gemm picks its scratch by it), and every tower
-// GEMM passes part_gemm (a no-op whenever the forward is not partitioned: cur_part = {0, 0}, as under lockstep).
+// GEMM passes part_gemm (a no-op whenever the forward is not partitioned: cur_part = {0, 0}).
 inline int run_gemm(mmhip_engine& e, G&& g, hipStream_t s) { return run_gemm(e, g, s); }
 
 // text embeddings; opens a forward: MMHIP_CLS_ONLY is read on the engine's first one, and no layer has closed yet
@@ -948,70 +919,6 @@ int text_forward(mmhip_engine& e, hipStream_t s) {
         CHECK_RC(t.ln2(s));
     }
     return 0;
-}
-
-// Both towers layer by layer on ONE stream, each pair of same-named GEMMs (QKV, attention output, FC1, FC2: equal N and K in
-// ViT-B/16 and the BERT-base-sized text tower) as one persistent launch (gemm8.hip, GemmNTPair): alone, the 256 x 256 tiles of
-// M = 8192 x N = 2304 fill 288 of 512 workgroup slots in two rounds and those of M = 12608 fill 450 of 512; together 738 of 768.
-// Same arithmetic as vit_forward + text_forward (same kernels on the same operands), another launch order.
-// Measured (same box, BASELINE config 2): the paired GEMMs run at 0.276 of the MFMA peak against 0.254 for the separate ones
-// (every kernel alone on the chip), and the step takes 11.2 ms against 12.2 ms with the side streams off -- but 10.4 ms with the
-// image tower on its own stream, where kernels of the two towers share CUs.  Hence opt-in: MMHIP_LOCKSTEP=1.
-bool lockstep_ok(const mmhip_engine& e) {
-    // MMHIP_LOCKSTEP=1: opt-in, every dtype.  Round 5 tried it as the default of the parity mode with plane pairs, where every GEMM is three times
-    // as long and the towers' own launches fill 78 % / 75 % of their rounds: the paired launches cut the forward's GEMM time by 14 % (12.4 -> 10.7 ms
-    // measured alone) -- and the forward got 0.5 ms LONGER (13.5 vs 13.0 ms, same box, profiles/r05_x3_lockstep.txt), also with the towers' row
-    // kernels forked onto two streams between the pairs: on two streams one tower's attention / LayerNorm kernels hide under the other's
-    // GEMMs for free, in lockstep they are serial work between launches that wait for each other.  Off by default in every mode.
-    static int on = -2;
-    if (on == -2) on = env_int("MMHIP_LOCKSTEP", 0);
-    return on > 0 && (e.dt() == DT_BF16 || e.dt() == DT_F16 || (e.dt() == DT_F32 && e.px)) && !e.clip() && !e.beit() && e.Hv() == e.cfg.hidden && e.Iv() == e.cfg.inter &&
-           e.cfg.layers_txt > 0 && e.cfg.layers_img > 0;
-}
-int towers_forward_lockstep(mmhip_engine& e, const float* pixels, hipStream_t s) {
-    const mmhip_config& c = e.cfg;
-    CHECK_RC(e.span(0, s));
-    CHECK_RC(vit_embed(e, pixels, s));
-    CHECK_RC(text_embed(e, s));
-    // Between the paired GEMMs the towers' row kernels are independent: the image tower's attention / LayerNorm go to the side stream, beside the
-    // text tower's on `s` (fork / join by events; 71 + 42 us of attention and 18 + 13 us of LayerNorm per layer, each alone on the chip, round 5)
-    hipStream_t sv = use_side(e) ? e.side_vit[0] : s;
-    auto fork = [&]() -> int { if (sv != s) { CHECK_HIP(hipEventRecord(e.ev_fork, s)); CHECK_HIP(hipStreamWaitEvent(sv, e.ev_fork, 0)); } return 0; };
-    auto join = [&]() -> int { if (sv != s) { CHECK_HIP(hipEventRecord(e.ev_vit, sv)); CHECK_HIP(hipStreamWaitEvent(s, e.ev_vit, 0)); } return 0; };
-    const int L = c.layers_txt > c.layers_img ? c.layers_txt : c.layers_img;
-    for (int l = 0; l < L; ++l) {
-        // a tower that has no layer l contributes nothing (its piece is built from its layer 0 and never enqueued); the other's GEMM runs alone
-        const bool ht = l < c.layers_txt, hv = l < c.layers_img;
-        const TextLayer t(e, ht ? l : 0);
-        const ImageLayer v(e, hv ? l : 0);
-        auto both = [&](G gt, G gv) -> int {
-            if (ht && hv) return run_gemm_pair(e, gt, gv, s);
-            return run_gemm(e, ht ? gt : gv, s);
-        };
-        // ---- QKV (image tower: pre-LN; layer 0's runs here, the later layers' beside the text tower's closing LayerNorm of the layer above)
-        if (hv && l == 0) CHECK_RC(v.ln1(s));
-        CHECK_RC(both(t.qkv(), v.qkv()));
-        // ---- attention
-        if (hv) { CHECK_RC(fork()); CHECK_RC(v.attention(sv)); }
-        if (ht) CHECK_RC(t.attention(s));
-        if (hv) CHECK_RC(join());
-        // ---- attention output (+ residual), then the image tower's second LayerNorm beside the text tower's first
-        CHECK_RC(both(t.attn_out(), v.attn_out()));
-        if (hv) { CHECK_RC(fork()); CHECK_RC(v.ln2(sv)); }
-        if (ht) CHECK_RC(t.ln1(s));
-        if (hv) CHECK_RC(join());
-        // ---- feed-forward
-        CHECK_RC(both(t.fc1(), v.fc1()));
-        CHECK_RC(both(t.fc2(), v.fc2()));
-        // ---- the text layer's closing LayerNorm beside the image tower's opening one of the next layer
-        const bool vnext = l + 1 < c.layers_img;
-        if (vnext) { CHECK_RC(fork()); CHECK_RC(ImageLayer(e, l + 1).ln1(sv)); }
-        if (ht) CHECK_RC(t.ln2(s));
-        if (vnext) CHECK_RC(join());
-    }
-    CHECK_RC(vit_close(e, s));
-    CHECK_RC(e.span(1, s));
-    return e.span(2, s);
 }
 
 // The split of the chip's 256 CUs between the two towers of this forward: both towers' big GEMMs run 256 x 256 tiles of K / 64 K-steps
@@ -1308,7 +1215,6 @@ int text_layer_backward(mmhip_engine& e, int l, hipStream_t s) {
     // temporaries that the weight-gradient GEMMs read are double-buffered per layer parity so that the side stream may
     // still be consuming layer l's set while the main stream runs layer l-1 on the other one
     const int set = l & 1;
-    const bool side = use_side(e);
     // last layer in CLS-only mode: its gradient arrives as compact [Bt, H] rows; everything up to d ctx runs on Bt rows
     const bool compact = e.cls_compact && l == c.layers_txt - 1;
     const int Mr = compact ? Bt : Mt, rs = compact ? T * H : H, rmul = compact ? T : 1;
@@ -1326,20 +1232,13 @@ int text_layer_backward(mmhip_engine& e, int l, hipStream_t s) {
     CHECK_HIP(launch_layernorm_bwd(b2, dt, s));
     const char* df = (px || d_ffn.thresh16) ? ddrop2 : dpre2;
     // du = (df . W2) * gelu'(u);  d_a1 = du . W1 + dpre2
-    if (e.part_bwd < 0) e.part_bwd = env_int("MMHIP_PART_BWD", 0);
-    static int bwd_mask = -1;
-    if (bwd_mask < 0) bwd_mask = env_int("MMHIP_PART_BWD_MASK", 15);
-    auto part_bwd = [&](G& g, int bit) {
-        if (e.part_bwd > 0 && (bwd_mask & bit) && side && g.a.M >= 2048 && g.a.N % 256 == 0 && g.a.K % 64 == 0 && (dt == DT_BF16 || dt == DT_F16)) g.tile(15).grid(e.part_bwd);
-    };
-    { G g(df, H, e.ws + w.fc2T, H, du, I, Mr, I, H); g.mul_gelu_grad(e.ws + a.u, I).px_in(px, np).px_out(px, hi1); part_bwd(g, 1); CHECK_RC(run_gemm(e, g, s)); }
+    { G g(df, H, e.ws + w.fc2T, H, du, I, Mr, I, H); g.mul_gelu_grad(e.ws + a.u, I).px_in(px, np).px_out(px, hi1); CHECK_RC(run_gemm(e, g, s)); }
     // the two long-K activation-gradient GEMMs of the layer (768 wide): one role-specialised 256x96 tile per CU when M gives
     // exactly <= 256 of them -- in isolation 7 % faster than the 192 tiles of 256x128, in the step -0.05 ms (same-box A/B; the
-    // same tile in the FORWARD costs +0.3 ms: it leaves no CU to the image tower).  MMHIP_BWD_TILE12=0 turns it off.
-    static int bt12 = -1;
-    if (bt12 < 0) bt12 = env_int("MMHIP_BWD_TILE12", 1);
-    const int nt = (bt12 && Mr >= 4096 && Mr <= 8192 && H % 96 == 0) ? 12 : 0;
-    { G g(du, I, e.ws + w.fc1T, I, dx2, H, Mr, H, I); g.residual(dpre2, H).px_in(px, np); g.tile(nt); part_bwd(g, 2); CHECK_RC(run_gemm(e, g, s)); }
+    // same tile in the FORWARD costs +0.3 ms: it leaves no CU to the image tower).  The non-compact
+    // d ctx GEMM below (K = H) keeps the launcher's own choice.
+    const int nt = (Mr >= 4096 && Mr <= 8192 && H % 96 == 0) ? 12 : 0;
+    { G g(du, I, e.ws + w.fc1T, I, dx2, H, Mr, H, I); g.residual(dpre2, H).px_in(px, np); g.tile(nt); CHECK_RC(run_gemm(e, g, s)); }
     // ---- a1 = LN1(pre1), pre1 = drop(ao(ctx)) + x_in        (dx2 = d_a1)
     const DropCfg d_ao = make_drop(c.p_hidden, e.seed, stream_attn_out(l), tr);
     LNBwdArgs b1{dx2, e.ws + a.pre1, W + o.ln1_w, e.wsp<float>(a.mean1), e.wsp<float>(a.rstd1), dpre1, nullptr, Gd + o.ln1_w, Gd + o.ln1_b, Mr, H,
@@ -1357,8 +1256,6 @@ int text_layer_backward(mmhip_engine& e, int l, hipStream_t s) {
     } else {
         G g(dout, H, e.ws + w.aoT, H, dctx, H, Mt, H, H);
         g.px_in(px, np).px_out(px, hi1);
-        g.tile((bt12 & 2) ? nt : 0);
-        part_bwd(g, 4);
         CHECK_RC(run_gemm(e, g, s));
     }
     AttnBwdArgs ab = attn_bwd_args(e.ws + a.qkv, e.wsp<float>(e.maskbias), e.ws + a.ctx, dctx, e.wsp<float>(a.lse), dqkv, Bt, T, c.heads, H,
@@ -1377,7 +1274,6 @@ int text_layer_backward(mmhip_engine& e, int l, hipStream_t s) {
         G g(dqkv, 3 * H, e.ws + w.qkvT, 3 * H, dx, H, Mt, H, 3 * H);
         g.residual(dpre1, H).px_in(px, np);
         g.tile(nt);
-        part_bwd(g, 8);
         CHECK_RC(run_gemm(e, g, s));
     }
     GemmTNProblem pr[4] = {
@@ -1720,22 +1616,17 @@ int mmhip_forward(mmhip_handle h, const int64_t* ids, const int64_t* mask, const
             if (sscanf(v, "%d,%d", &a, &b) == 2 && a > 0 && b > 0) { e.part[0] = a; e.part[1] = b; }
         }
     }
-    const bool can_part = !imported && use_side(e) && !lockstep_ok(e) && (e.dt() == DT_BF16 || e.dt() == DT_F16);
+    const bool can_part = !imported && use_side(e) && (e.dt() == DT_BF16 || e.dt() == DT_F16);
     e.cur_part[0] = e.cur_part[1] = 0;
     if (can_part && e.part_auto) choose_partition(e);
     else if (can_part && e.part[0] > 0) { e.cur_part[0] = e.part[0]; e.cur_part[1] = e.part[1]; }
-    if (!imported && lockstep_ok(e)) {
-        e.vit_is_long = false;
-        CHECK_RC(towers_forward_lockstep(e, pixels, s));
-    } else if (use_side(e)) {
+    if (use_side(e)) {
         // the frozen image tower does not depend on the text tower: run it on the side stream, join before the heads
         CHECK_HIP(hipEventRecord(e.ev_fork, s));
         CHECK_RC(e.span(0, s));
-        static int force = -2;
-        if (force == -2) force = env_int("MMHIP_VIT_PRIO", -1);
         const bool vit_longer = (double)e.B * e.P() * e.cfg.layers_img > (double)e.Bt * e.T * e.cfg.layers_txt;     // rows x layers of equal width
         e.vit_is_long = vit_longer;
-        hipStream_t sv = e.side_vit[force >= 0 ? (force ? 1 : 0) : (vit_longer ? 1 : 0)];
+        hipStream_t sv = e.side_vit[vit_longer ? 1 : 0];
         if (!imported) {
             CHECK_HIP(hipStreamWaitEvent(sv, e.ev_fork, 0));
             CHECK_RC(vit_forward(e, pixels, sv));

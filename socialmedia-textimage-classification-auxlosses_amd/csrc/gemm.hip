@@ -7,10 +7,7 @@
 // Tiling: 128x128 output tile, BK = 64, 256 threads = 4 waves (2x2), each wave 64x64 = 4x4 MFMA 16x16x32 tiles.
 // Operand tiles go global -> LDS with global_load_lds_dwordx4 (no VGPR round trip), double buffered.
 // LDS images are XOR-swizzled on the *source* address (the LDS-DMA destination is lane-linear) and on the read.
-#include <cstdio>
-#include <cstdlib>
 #include "mmhip_common.h"
-#include <cstdlib>
 #include <type_traits>
 #include "mmhip_kernels.h"
 
@@ -368,7 +365,7 @@ void gemm_tn_kernel(GemmTNGroup g) {
         char* base = smem + buf * C::STAGE;
         size_t ao, bo;
         if (P.pair) {
-            // the three products of one 64-row slice follow each other (second uses of a slice served from L2), g.pair_serial = the round-3 order
+            // the three products of one 64-row slice follow each other (second uses of a slice served from L2); g.pair_serial is always 0 (mmhip_kernels.h)
             const int seg = g.pair_serial ? mstep / msteps : mstep % npr, r = g.pair_serial ? mstep - seg * msteps : mstep / npr;
             ao = (size_t)r * 64 * P.lda + (seg == 1 ? (size_t)P.a_lo : 0);
             bo = (size_t)r * 64 * P.ldb + (seg == 2 ? (size_t)P.b_lo : 0);
@@ -459,7 +456,8 @@ void gemm_tn_kernel(GemmTNGroup g) {
             compute(buf);
             buf = (buf + 1 == NS) ? 0 : buf + 1;
         }
-    } else if constexpr (NS == 2) {
+    } else {
+        static_assert(NS == 2, "without loader waves the kernel is double-buffered");
         stage(0, 0);
         __syncthreads();
         for (int t = 0; t < nsteps; ++t) {
@@ -468,23 +466,6 @@ void gemm_tn_kernel(GemmTNGroup g) {
             cs_now = with_colsum && t < cs_steps && (!P.pair || (pair_ilv ? t % npr != 2 : t < 2 * msteps));
             compute(cur);
             __syncthreads();
-        }
-    } else {
-#pragma unroll
-        for (int p = 0; p < NS - 1; ++p)
-            if (p < nsteps) stage(p, p);
-        int buf = 0, sbuf = NS - 1;
-        for (int t = 0; t < nsteps; ++t) {
-            const int ahead = nsteps - 1 - t;
-            if (ahead >= NS - 2) wait_vmcnt<(NS - 2) * C::LPS>();
-            else if (NS > 3 && ahead == 1) wait_vmcnt<C::LPS>();
-            else wait_vmcnt<0>();
-            __builtin_amdgcn_s_barrier();
-            if (t + NS - 1 < nsteps) stage(sbuf, t + NS - 1);
-            cs_now = with_colsum && t < cs_steps && (!P.pair || (pair_ilv ? t % npr != 2 : t < 2 * msteps));
-            compute(buf);
-            buf = (buf + 1 == NS) ? 0 : buf + 1;
-            sbuf = (sbuf + 1 == NS) ? 0 : sbuf + 1;
         }
     }
     // D[row = n][col = c]: col = lane&15, row = 4*(lane>>4) + reg
@@ -625,9 +606,7 @@ static void launch_nt_t(const GemmNTArgs& a, hipStream_t s) {
 // few rows, long K: K / 384 slices side by side, then the epilogue over their sum (two launches instead of one 128-row block per
 // 128 columns walking all of K: 64 x 768 x 3072 took 54 us)
 static int splitk_rule(const GemmNTArgs& a) {      // everything but the workspace
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("MMHIP_SPLITK"); on = e ? atoi(e) : 1; }
-    if (!on || a.tile || a.M > 128 || a.K < 1536 || a.K % 384 || a.N % 128 || (a.flags & (GEMM_TANH | GEMM_QGELU))) return 0;
+    if (a.tile || a.M > 128 || a.K < 1536 || a.K % 384 || a.N % 128 || (a.flags & (GEMM_TANH | GEMM_QGELU))) return 0;
     return a.K / 384;
 }
 static int splitk_slices(const GemmNTArgs& a) { return a.splitk_ws ? splitk_rule(a) : 0; }
@@ -640,50 +619,23 @@ static void launch_nt_splitk(const GemmNTArgs& a, int slices, hipStream_t s) {
     hipLaunchKernelGGL((gemm_nt_kernel<T, 128, 128, 2, 2, 2, 0, true>), dim3(grid, slices), dim3(C::NTHR), C::LDS, s, a);
 }
 
-// MMHIP_TILE_MAP="MxNxK:tile,MxNxK/FLAGS:tile,..." -- per-shape tile override for same-box A/B runs of the whole step (an entry with
-// /FLAGS matches that epilogue flag set only)
-struct TileMapEntry { int M, N, K, flags, tile; };
-static int tile_map_lookup(const GemmNTArgs& a) {
-    static TileMapEntry tab[32];
-    static int n = -1;
-    if (n < 0) {
-        n = 0;
-        const char* e = getenv("MMHIP_TILE_MAP");
-        while (e && *e && n < 32) {
-            TileMapEntry t{0, 0, 0, -1, 0};
-            int used = 0;
-            if (sscanf(e, "%dx%dx%d/%d:%d%n", &t.M, &t.N, &t.K, &t.flags, &t.tile, &used) == 5 && used > 0) { tab[n++] = t; }
-            else { t.flags = -1; if (sscanf(e, "%dx%dx%d:%d%n", &t.M, &t.N, &t.K, &t.tile, &used) == 4 && used > 0) tab[n++] = t; else break; }
-            e += used;
-            if (*e == ',') ++e;
-        }
-    }
-    for (int i = 0; i < n; ++i)
-        if (tab[i].M == a.M && tab[i].N == a.N && tab[i].K == a.K && (tab[i].flags < 0 || tab[i].flags == a.flags)) return tab[i].tile;
-    return 0;
-}
-// tile choice: explicit (a.tile / MMHIP_NT_TILE / MMHIP_TILE_MAP) or measured rules.  Tiles: 1 = 128x128 (two blocks per CU), 6 = 128x192,
-// 9 = role-specialised 256x128, 10 = 128x96, 12 = role-specialised 256x96, 20 / 21 = 128x128 on a 4- / 3-deep ring (gemm.hip); 13-18 = the deep-pipelined kernel of gemm8.hip
+// tile choice: explicit (a.tile) or measured rules.  Tiles: 1 = 128x128 (two blocks per CU), 6 = 128x192,
+// 9 = role-specialised 256x128, 10 = 128x96, 12 = role-specialised 256x96, 21 = 128x128 on a 3-deep ring (gemm.hip); 13-18 = the deep-pipelined kernel of gemm8.hip
 // (13 / 15 = 256x256 one-shot / persistent, 14 / 16 = 256x128, 17 / 18 = 256x192)
+bool nt_tile_known(int t) { return t == 1 || t == 6 || t == 9 || t == 10 || t == 12 || (t >= 13 && t <= 18) || t == 21; }
 static int choose_nt_tile(const GemmNTArgs& a) {
-    { const int m = tile_map_lookup(a); if (m) return m; }
-    static int env = -1;
-    if (env < 0) { const char* e = getenv("MMHIP_NT_TILE"); env = e ? atoi(e) : 0; }
-    int t = a.tile ? a.tile : env;
+    int t = a.tile;
     if ((t == 13 || t == 15) && a.N % 256) t = 0;
     if ((t == 17 || t == 18 || t == 6) && a.N % 192) t = 0;
     if ((t == 14 || t == 16 || t == 1 || t == 9) && a.N % 128) t = 0;
     if ((t == 10 || t == 12) && a.N % 96) t = 0;
-    if ((t == 20 || t == 21) && a.N % 128) t = 0;
-    if (t == 1 || t == 6 || t == 9 || t == 10 || t == 12 || (t >= 13 && t <= 18) || t == 20 || t == 21) return t;
+    if (t == 21 && a.N % 128) t = 0;
+    if (nt_tile_known(t)) return t;
     // Rules measured inside the training step (same-box A/B of bench.py, profiles/r02_step_ab*.txt, r03_*): the image-tower-sized GEMMs
     // (M >= 12000 rows) take the deep-pipelined persistent tile that fills the rounds of 256 workgroups best; the 8192-row text GEMMs
     // outside the forward's CU partition (i.e. the backward's) keep 128 x 128 at two blocks per CU, and the long-K 768-wide ones the
-    // role-specialised tiles.  MMHIP_NT8=0 turns the deep-pipelined kernel off here; MMHIP_NT8_MINM moves the row threshold.
-    static int nt8 = -1, nt8_minm = -1;
-    if (nt8 < 0) { const char* e = getenv("MMHIP_NT8"); nt8 = e ? atoi(e) : 1; }
-    if (nt8_minm < 0) { const char* e = getenv("MMHIP_NT8_MINM"); nt8_minm = e ? atoi(e) : 12000; }
-    if (nt8 && a.M >= nt8_minm && a.N % 128 == 0 && a.K % 64 == 0) {
+    // role-specialised tiles.
+    if (a.M >= 12000 && a.N % 128 == 0 && a.K % 64 == 0) {
         const long tm = (a.M + 255) / 256;
         const long t256 = a.N % 256 == 0 ? tm * (a.N / 256) : 0, t128 = tm * (a.N / 128);
         const double u256 = t256 ? (double)t256 / (double)(((t256 + 255) / 256) * 256) : 0.0;
@@ -702,10 +654,8 @@ static int choose_nt_tile(const GemmNTArgs& a) {
     }
     // long K on a grid that leaves one block per CU at most (config 5's 4096- and 1152-row GEMMs): nothing else on the CU hides the
     // 2-stage variant's load latency; the 3-deep ring does (microbench profiles/r04_early_gemm.txt: 4096x768x3072 40.1 -> 35.0 us,
-    // 1152x768x3072 40.2 -> 33.4; K = 768 shapes are unchanged -- their 13-15 us are launch + prologue + epilogue).  MMHIP_RING3=0: off
-    static int ring3 = -1;
-    if (ring3 < 0) { const char* e = getenv("MMHIP_RING3"); ring3 = e ? atoi(e) : 1; }
-    if (ring3 && a.N % 128 == 0 && a.K >= 2048 && (long)((a.M + 127) / 128) * (a.N / 128) <= 256) return 21;
+    // 1152x768x3072 40.2 -> 33.4; K = 768 shapes are unchanged -- their 13-15 us are launch + prologue + epilogue)
+    if (a.N % 128 == 0 && a.K >= 2048 && (long)((a.M + 127) / 128) * (a.N / 128) <= 256) return 21;
     if (a.N % 128 == 0 && a.N <= 768 && a.K >= 2048 && a.M >= 4096) return 9;
     if (a.N % 128 == 0) return 1;
     if (a.N % 192 == 0) return 6;
@@ -727,21 +677,14 @@ static void launch_nt_d(const GemmNTArgs& a, hipStream_t s) {
         r[0] = PATH_TILE; r[1] = used; r[2] = -1; r[3] = 0; r[4] = r[5] = ((a.M + bm - 1) / bm) * (a.N / bnn); r[6] = 1;
     }
     switch (used) {
-        case 20: launch_nt_t<T, 128, 128, 2, 2, 4>(a, s); break;      // 128 x 128 on a 4-deep LDS ring (one block per CU): grids of <= 256 tiles, where
+        case 21: launch_nt_t<T, 128, 128, 2, 2, 3>(a, s); break;      // 128 x 128 on a 3-deep LDS ring (one block per CU): grids of <= 256 tiles, where
                                                                       // nothing else on the CU hides the load latency of the 2-stage variant
-        case 21: launch_nt_t<T, 128, 128, 2, 2, 3>(a, s); break;      // ... 3-deep
         case 12: launch_nt_t<T, 256, 96, 4, 2, 3, 4>(a, s); break;    // role-specialised (8 MFMA + 4 LDS-DMA loader waves), 256 tiles for 8192 x 768: one tile per CU
         case 10: launch_nt_t<T, 128, 96, 2, 2, 2>(a, s); break;       // N that only 96 divides
         case 9: launch_nt_t<T, 256, 128, 4, 2, 3, 4>(a, s); break;    // role-specialised, 3-stage ring
         case 6: launch_nt_t<T, 128, 192, 2, 2, 2>(a, s); break;       // N that only 192 divides
         default: launch_nt_t<T, 128, 128, 2, 2, 2>(a, s); break;      // 128 x 128, two blocks per CU
     }
-}
-
-static bool debug_force_slow() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("MMHIP_FORCE_SLOW"); v = e ? atoi(e) : 0; }
-    return v != 0;
 }
 
 GemmPathRecord& gemm_path_record() {
@@ -765,7 +708,7 @@ hipError_t launch_gemm_nt(const GemmNTArgs& a, int dtype, hipStream_t s) {
     return r;
 }
 size_t nt_splitk_scratch_bytes(const GemmNTArgs& a, int dtype) {
-    if ((dtype != DT_BF16 && dtype != DT_F16) || a.M <= 0 || a.N <= 0 || !nt_fast_ok(a) || a.force_slow || debug_force_slow()) return 0;
+    if ((dtype != DT_BF16 && dtype != DT_F16) || a.M <= 0 || a.N <= 0 || !nt_fast_ok(a) || a.force_slow) return 0;
     return (size_t)splitk_rule(a) * a.M * a.N * sizeof(float);
 }
 static hipError_t launch_gemm_nt_untimed(const GemmNTArgs& a, int dtype, hipStream_t s) {
@@ -774,7 +717,7 @@ static hipError_t launch_gemm_nt_untimed(const GemmNTArgs& a, int dtype, hipStre
     rec[2] = -1;
     if (a.M <= 0 || a.N <= 0) return hipSuccess;
     if (dtype == DT_F32) return launch_gemm_nt_x3(a, s);
-    if (nt_fast_ok(a) && !a.force_slow && !debug_force_slow()) {
+    if (nt_fast_ok(a) && !a.force_slow) {
         if (const int slices = splitk_slices(a)) {
             rec[0] = PATH_SPLITK; rec[1] = slices; rec[4] = ((a.M + 127) / 128) * (a.N / 128) * slices; rec[5] = rec[4]; rec[6] = 1;
             if (dtype == DT_BF16) launch_nt_splitk<bf16_t>(a, slices, s);
@@ -800,45 +743,33 @@ static void launch_tn_t(const GemmTNGroup& g, int tiles, hipStream_t s) {
     hipLaunchKernelGGL((gemm_tn_kernel<T, BNN, BNC, WN, WC, NS, NL>), dim3(tiles), dim3(C::NTHR), C::LDS, s, g);
 }
 
-// variant: 1 = 128x128 2-stage, 4 (default, fastest inside the step: 13.5 vs 14.2 ms) = role-specialised 256x128,
-// 2 = 128x128 4-stage ring, 3 = 256x128 3-stage ring, 4 = role-specialised 256x128 (8 MFMA + 4 loader waves, 3-stage
-// ring), 5 = role-specialised 128x128 (4 + 4, 4-stage ring); env MMHIP_TN_TILE overrides
+// variant (force_slow >> 4; 0 = the default, 4): 1 = 128x128 2-stage, 4 (fastest inside the step: 13.5 vs 14.2 ms) = role-specialised
+// 256x128 (8 MFMA + 4 loader waves, 3-stage ring)
+bool tn_variant_known(int v) { return v == 1 || v == 4; }
 hipError_t launch_gemm_tn(const GemmTNProblem* probs, int count, int accumulate, int dtype, int force_slow, hipStream_t s, float alpha, void* x3_ws, size_t x3_ws_bytes) {
     int* rec = gemm_path_record().tn;
     for (int i = 0; i < 8; ++i) rec[i] = 0;
     if (dtype == DT_F32) return launch_gemm_tn_x3(probs, count, accumulate, s, alpha, force_slow ? nullptr : x3_ws, x3_ws_bytes);
-    static int env = -1;
-    if (env < 0) { const char* e = getenv("MMHIP_TN_TILE"); env = e ? atoi(e) : 0; }
-    int variant = (force_slow >> 4) ? (force_slow >> 4) : (env ? env : 4);
-    if (variant == 3 || variant == 4)          // the 256-row tiles need every problem's Nn to be a multiple of 256
+    int variant = (force_slow >> 4) == 1 ? 1 : 4;
+    if (variant == 4)          // the 256-row tile needs every problem's Nn to be a multiple of 256
         for (int i = 0; i < count; ++i)
             if (probs[i].Nn % 256) { variant = 1; break; }
-    force_slow = (force_slow & 1) | (debug_force_slow() ? 1 : 0);
-    const int bnn = (variant == 3 || variant == 4) ? 256 : 128;
+    force_slow &= 1;
+    const int bnn = variant == 4 ? 256 : 128;
     GemmTNGroup g;
     g.count = 0;
     g.accumulate = accumulate;
-    {
-        static int ilv = -1;
-        if (ilv < 0) { const char* e = getenv("MMHIP_X3_INTERLEAVE"); ilv = e ? atoi(e) : 1; }
-        g.pair_serial = !ilv;
-    }
+    g.pair_serial = 0;
     g.alpha = alpha;
     int tiles = 0;
     auto flush = [&]() {
         if (!g.count) return;
-        rec[0] |= TNPATH_TILE; rec[1] = variant >= 2 && variant <= 5 ? variant : 1; rec[2] += g.count; rec[4] += 1;
+        rec[0] |= TNPATH_TILE; rec[1] = variant; rec[2] += g.count; rec[4] += 1;
         if (dtype == DT_BF16) {
             if (variant == 4) launch_tn_t<bf16_t, 256, 128, 4, 2, 3, 4>(g, tiles, s);
-            else if (variant == 5) launch_tn_t<bf16_t, 128, 128, 2, 2, 4, 4>(g, tiles, s);
-            else if (variant == 3) launch_tn_t<bf16_t, 256, 128, 4, 2, 3>(g, tiles, s);
-            else if (variant == 2) launch_tn_t<bf16_t, 128, 128, 2, 2, 4>(g, tiles, s);
             else launch_tn_t<bf16_t, 128, 128, 2, 2, 2>(g, tiles, s);
         } else {
             if (variant == 4) launch_tn_t<f16_t, 256, 128, 4, 2, 3, 4>(g, tiles, s);
-            else if (variant == 5) launch_tn_t<f16_t, 128, 128, 2, 2, 4, 4>(g, tiles, s);
-            else if (variant == 3) launch_tn_t<f16_t, 256, 128, 4, 2, 3>(g, tiles, s);
-            else if (variant == 2) launch_tn_t<f16_t, 128, 128, 2, 2, 4>(g, tiles, s);
             else launch_tn_t<f16_t, 128, 128, 2, 2, 2>(g, tiles, s);
         }
         g.count = 0;

@@ -266,7 +266,8 @@ struct I8 {
 // SEG (parity mode, round 4): A and B are plane pairs written by their producers (mmhip_kernels.h); the reduction runs over THREE segments of
 // K / 64 K-tiles each -- (A hi, B hi), (A lo, B hi), (A hi, B lo) -- by moving the operands' base pointers between the planes at the segment
 // ends: one launch, no scratch copies of the operands (round 3 split every fp32 operand into [hi | lo | hi] copies before each call).
-// SEG = 2: the same three products interleaved per 64-deep k slice (below); 1: three serial segments; 0: plain operands.
+// SEG = 2: the three products interleaved per 64-deep k slice (below); 0: plain operands.  (1 was the three products as serial K segments: 24.93 against
+// 24.19 ms per step, profiles/r04_step_ab.txt.)
 template <typename T, int BN, int EPI, typename ET = T, int SEG = 0>
 __global__ __launch_bounds__(512, 2) void gemm_nt8_kernel(GemmNTPair g, int persistent) {
     using C = P8<BN>;
@@ -284,9 +285,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt8_kernel(GemmNTPair g, int pers
     // SEG = 2 may run only the first two products of every slice -- (A hi, B hi), (A lo, B hi): GemmNTArgs::nprod = 2, B rounded to its hi plane
     const int np2 = SEG == 2 && g.p[0].nprod == 2 ? 1 : 0;
     const int nk = SEG ? (np2 ? 2 : 3) * kseg : kseg;
-    // byte steps of the operand pointers at the two segment ends (on top of the ordinary 128 bytes): A hi -> A lo -> A hi, B hi -> B hi -> B lo
-    const int segA1 = SEG == 1 ? (g.p[0].a_lo - g.p[0].K) * 2 : 0, segA2 = SEG == 1 ? -(g.p[0].a_lo + g.p[0].K) * 2 : 0;
-    const int segB1 = SEG == 1 ? -g.p[0].K * 2 : 0, segB2 = SEG == 1 ? (g.p[0].b_lo - g.p[0].K) * 2 : 0;
     // interleaved order (g.seg_interleave): the three products of ONE 64-deep k slice follow each other -- (A hi, B hi), (A lo, B hi), (A hi, B lo), then
     // the next slice -- so the second use of a B hi / A hi slice comes one / two K-tiles after the first and is served from the XCD's L2
     // instead of, K / 64 tiles later, from beyond it (the K loop runs at the rate its operands arrive: DESIGN.md 7c)
@@ -380,12 +378,8 @@ __global__ __launch_bounds__(512, 2) void gemm_nt8_kernel(GemmNTPair g, int pers
                     gB[p] += lv * (ph == 0 ? 0 : (ph == 1 ? bLo2 : 128 - bLo2));
                     g_ph[p] = ph == 2 ? 0 : ph + 1;
                 }
-            } else if constexpr (SEG == 1) {
-                // g_rem K-tiles of the group's current tile are still to be issued: the next one opens segment 1 / segment 2
-                const int j1 = g_rem[p] == 2 * kseg ? (g_inc[p] >> 7) : 0, j2 = g_rem[p] == kseg ? (g_inc[p] >> 7) : 0;
-                gA[p] += g_inc[p] + j1 * segA1 + j2 * segA2;
-                gB[p] += g_inc[p] + j1 * segB1 + j2 * segB2;
             } else {
+                static_assert(SEG == 0, "SEG is 0 or 2");
                 gA[p] += g_inc[p];
                 gB[p] += g_inc[p];
             }
@@ -659,16 +653,10 @@ static void launch_nt8_t(const GemmNTPair& g, int persistent, hipStream_t s) {
     else launch_nt8_e<T, BN, EP_ANY, ET, SEG>(g, persistent, s);
 }
 static void launch_nt8_d(const GemmNTPair& g, int dtype, int bn, int persistent, hipStream_t s) {
-    static int ilv = -1;
-    if (ilv < 0) { const char* e = getenv("MMHIP_X3_INTERLEAVE"); ilv = e ? atoi(e) : 1; }
-    if (dtype == DT_F32 && g.p[0].a_pair && (ilv || g.p[0].nprod == 2)) {          // parity mode, operands as plane pairs: the three (two) products interleaved per k slice
+    if (dtype == DT_F32 && g.p[0].a_pair) {          // parity mode, operands as plane pairs: the three (two) products interleaved per k slice
         if (bn == 256) launch_nt8_t<bf16_t, 256, float, 2>(g, persistent, s);
         else if (bn == 192) launch_nt8_t<bf16_t, 192, float, 2>(g, persistent, s);
         else launch_nt8_t<bf16_t, 128, float, 2>(g, persistent, s);
-    } else if (dtype == DT_F32 && g.p[0].a_pair) {          // ... as three serial K segments (MMHIP_X3_INTERLEAVE=0)
-        if (bn == 256) launch_nt8_t<bf16_t, 256, float, 1>(g, persistent, s);
-        else if (bn == 192) launch_nt8_t<bf16_t, 192, float, 1>(g, persistent, s);
-        else launch_nt8_t<bf16_t, 128, float, 1>(g, persistent, s);
     } else if (dtype == DT_F32) {          // parity mode: bf16 split planes in (x3.hip scratch copies), fp32 epilogue
         if (bn == 256) launch_nt8_t<bf16_t, 256, float>(g, persistent, s);
         else if (bn == 192) launch_nt8_t<bf16_t, 192, float>(g, persistent, s);
@@ -695,30 +683,6 @@ bool launch_gemm_nt8(const GemmNTArgs& a, int dtype, int bn, int persistent, hip
     GemmNTPair g;
     g.p[0] = a; g.p[1] = a; g.count = 1;
     launch_nt8_d(g, dtype, bn, persistent, s);
-    return true;
-}
-
-// two problems of equal N and K in one persistent launch; bn = 0 picks the tile that fills the rounds of 256 workgroups best.
-// false = rules not met (caller launches them one by one)
-bool launch_gemm_nt8_pair(const GemmNTArgs& a0, const GemmNTArgs& a1, int dtype, int bn, hipStream_t s) {
-    if (dtype == DT_F32) {          // parity mode: both problems on plane pairs with the same plane offsets (the K loop reads them from problem 0), all three products
-        if (!a0.a_pair || !a0.b_pair || !a1.a_pair || !a1.b_pair || a0.a_lo != a1.a_lo || a0.b_lo != a1.b_lo || a0.nprod != a1.nprod || a0.nprod == 1) return false;
-        if (a0.M <= 128 || a1.M <= 128) return false;      // the <= 128-row problems of the parity mode take the direct kernel (x3.hip)
-    } else if (dtype != DT_BF16 && dtype != DT_F16) return false;
-    if (a0.N != a1.N || a0.K != a1.K) return false;
-    if (bn == 0) {
-        double best = 0;
-        for (int cand : {256, 192, 128}) {
-            if (a0.N % cand) continue;
-            const long t = (long)((a0.M + 255) / 256 + (a1.M + 255) / 256) * (a0.N / cand);
-            const double u = (double)t / (double)(((t + 255) / 256) * 256) + (cand == 256 ? 0.04 : (cand == 192 ? 0.02 : 0.0));   // ties -> wider
-            if (u > best) { best = u; bn = cand; }
-        }
-    }
-    if ((bn != 256 && bn != 192 && bn != 128) || !nt8_ok(a0, bn) || !nt8_ok(a1, bn) || !nt8_fits(a0, 2, bn)) return false;
-    GemmNTPair g;
-    g.p[0] = a0; g.p[1] = a1; g.count = 2;
-    launch_nt8_d(g, dtype, bn, 1, s);
     return true;
 }
 

@@ -223,12 +223,11 @@ inline hipError_t pool_stream(int which, hipStream_t* out) {
     if (r != hipSuccess) return r;
     if (dev < 0 || dev >= 16 || which < 0 || which >= POOL_STREAMS) return hipErrorInvalidValue;
     if (!pool[dev][0]) {
-        // MMHIP_SIDE_PRIO: HIP priority of the backward's side stream (lower = higher; default: equal to the caller's)
-        const char* v = getenv("MMHIP_SIDE_PRIO");
+        // the backward's side stream has the caller's priority (a static priority of its own: no gain)
         int least = 0, greatest = 0;
         if ((r = hipDeviceGetStreamPriorityRange(&least, &greatest)) != hipSuccess) return r;
         hipStream_t s[POOL_STREAMS] = {};
-        r = v ? hipStreamCreateWithPriority(&s[POOL_SIDE], hipStreamNonBlocking, atoi(v)) : hipStreamCreateWithFlags(&s[POOL_SIDE], hipStreamNonBlocking);
+        r = hipStreamCreateWithFlags(&s[POOL_SIDE], hipStreamNonBlocking);
         if (r == hipSuccess) r = hipStreamCreateWithFlags(&s[POOL_VIT], hipStreamNonBlocking);
         if (r == hipSuccess) r = hipStreamCreateWithPriority(&s[POOL_VIT_HI], hipStreamNonBlocking, greatest);
         if (r != hipSuccess) {

@@ -35,7 +35,7 @@ struct GemmNTArgs {
     int M, N, K, lda, ldb, ldc, ldaux, ldres, ldmul;
     int flags;
     int force_slow;
-    int tile;                 // 0 = auto, 1 = 128x128, 2 = 256x128, 3 = 256x256, ...
+    int tile;                 // 0 = auto, else a code of gemm.hip choose_nt_tile (nt_tile_known)
     int drop_row_mul;         // dropout element index uses row m * drop_row_mul (0 = 1): compact CLS-row GEMMs keep the
                               // masks of the full [posts*T, N] tensor
     DropCfg drop;
@@ -69,8 +69,9 @@ struct GemmTNGroup {
     GemmTNProblem p[GEMM_TN_MAX_GROUP];
     int count, accumulate;
     float alpha;              // C (+)= alpha * A^T B   (un-does the f16 gradient scale)
-    int pair_serial;          // plane pairs: 1 = three passes over all M rows one after the other (round-4 first form); 0 = the three products of a
-                              // 64-row slice follow each other
+    int pair_serial;          // always 0: the three products of a plane pair's 64-row slice follow each other.  (1 was the serial order of three passes
+                              // over all M rows; no launcher sets it any more.  The field and the kernel's test of it stay until a change that
+                              // re-measures gemm_tn_kernel: taking them out alters every instantiation's instructions.)
 };
 struct SmallGemmArgs {
     const void* A; const float* W; const float* bias; float* out;
@@ -80,7 +81,7 @@ struct SmallGemmArgs {
 hipError_t launch_gemm_nt(const GemmNTArgs& a, int dtype, hipStream_t s);
 // What the launchers actually launched for the calling thread's most recent launch_gemm_nt / launch_gemm_tn call (host-side, thread_local, no device
 // work; include/mmhip.h mmhip_op_last_gemm_path documents the fields).  Every silent fallback of the launchers shows here: a forced tile whose N does
-// not divide, launch_gemm_nt8 returning false, nt_fast_ok / the TN shape rules dropping to the generic kernels, TN variants 3 / 4 dropping to 1.
+// not divide, launch_gemm_nt8 returning false, nt_fast_ok / the TN shape rules dropping to the generic kernels, TN variant 4 dropping to 1.
 enum { PATH_NONE = 0, PATH_GENERIC = 1, PATH_TILE = 2, PATH_DEEP = 3, PATH_SPLITK = 4, PATH_X3_DIRECT = 5, PATH_X3_SMALL = 6, PATH_X3_SPLIT = 7, PATH_X3_PAIR = 8 };
 enum { TNPATH_GENERIC = 1, TNPATH_TILE = 2, TNPATH_X3_DIRECT = 4, TNPATH_X3_SPLIT = 8, TNPATH_X3_PAIR = 16 };
 struct GemmPathRecord {
@@ -88,6 +89,9 @@ struct GemmPathRecord {
     int tn[8];      // family bits, variant of the tile kernel, problems on it, problems on the generic kernel, launches of the tile kernel, parity direct, parity scratch-split, 0
 };
 GemmPathRecord& gemm_path_record();
+// the forced codes the launchers take (GemmNTArgs::tile; launch_gemm_tn's force_slow >> 4); the op entry points refuse every other non-zero code
+bool nt_tile_known(int tile);
+bool tn_variant_known(int variant);
 // fp32 scratch bytes the split-K path of launch_gemm_nt would use for `a` (0: its rules -- splitk_slices, nt_fast_ok -- do not hold; a.splitk_ws itself is not looked at)
 size_t nt_splitk_scratch_bytes(const GemmNTArgs& a, int dtype);
 // Measurement hook (round 5): while a sink is set on the calling thread, launch_gemm_nt brackets every launch with HIP events recorded on the
@@ -99,10 +103,8 @@ struct GemmTimingSink {
 void gemm_timing_sink(GemmTimingSink* sink);      // nullptr = off
 // deep-pipelined 256 x bn tiles (gemm8.hip); false = shape rules not met, nothing launched
 bool launch_gemm_nt8(const GemmNTArgs& a, int dtype, int bn, int persistent, hipStream_t s);
-// two problems of equal N and K in one persistent launch (the two towers' GEMMs of one layer); bn = 0: best-filling tile
 // split-K finish: C = epilogue(sum over `slices` partial products in a.splitk_ws), same flags as the fused epilogue
 hipError_t launch_splitk_finish(const GemmNTArgs& a, int dtype, int slices, hipStream_t s);
-bool launch_gemm_nt8_pair(const GemmNTArgs& a0, const GemmNTArgs& a1, int dtype, int bn, hipStream_t s);
 hipError_t launch_gemm_tn(const GemmTNProblem* probs, int count, int accumulate, int dtype, int force_slow, hipStream_t s, float alpha = 1.0f,
                           void* x3_ws = nullptr, size_t x3_ws_bytes = 0);
 // parity mode (fp32 activations, three bf16 MFMA products of split operands / fp32 attention): csrc/x3.hip

@@ -305,11 +305,9 @@ hipError_t launch_gemm_nt_x3(const GemmNTArgs& a, hipStream_t s) {
                       (!a.a_pair || (a.a_lo % 8 == 0 && a.lda % 8 == 0)) && (!a.b_pair || (a.b_lo % 8 == 0 && a.ldb % 8 == 0)) && (!(a.flags & GEMM_OUT_PAIR) || a.c_lo % 4 == 0) &&
                       (!(a.flags & GEMM_RESIDUAL) || (a.ldres % 4 == 0 && al(a.residual))) && (!(a.flags & GEMM_AUX_PRE) || (a.ldaux % 4 == 0 && al(a.aux))) &&
                       (!(a.flags & GEMM_MUL_GELU_GRAD) || (a.ldmul % 4 == 0 && al(a.mul_in))) && (!(a.flags & GEMM_BIAS) || al(a.bias));
-    static int small_on = -1;
-    if (small_on < 0) { const char* e = getenv("MMHIP_X3_SMALL"); small_on = e ? atoi(e) : 1; }
     int* rec = gemm_path_record().nt;
     rec[6] = 1;
-    if (fast && small_on && a.M <= 128 && a.K % 128 == 0 && a.N % 16 == 0) {          // few rows: K split over the waves of a 64 x 16 tile (MMHIP_X3_SMALL=0: the 128 x 128 kernel)
+    if (fast && a.M <= 128 && a.K % 128 == 0 && a.N % 16 == 0) {          // few rows: K split over the waves of a 64 x 16 tile
         rec[0] = PATH_X3_SMALL;
         hipLaunchKernelGGL(gemm_nt_x3_small_kernel, dim3(a.N / 16, (a.M + 63) / 64), dim3(256), 0, s, a);
     } else if (fast) { rec[0] = PATH_X3_DIRECT; hipLaunchKernelGGL(gemm_nt_x3_kernel, dim3((a.N + 127) / 128, (a.M + 127) / 128), dim3(256), 0, s, a); }

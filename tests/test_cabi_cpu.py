@@ -82,3 +82,22 @@ def test_create_rejects_bad_configs(lib):
         cfg = _cfg(**bad)
         assert lib.mmhip_create(C.byref(cfg), C.byref(h)) == -1, bad
     assert lib.mmhip_forward(None, None, None, None, None, None, 1, 1, 0, 0, None, None, None, None, None) == -2
+
+
+def test_environment_switches_match_the_design_table():
+    """every MMHIP_* variable the library (getenv / env_int in csrc/) and the package (os.environ) read is a row of DESIGN.md's
+    "Environment switches" table, and the table names nothing the code does not read"""
+    pkg = os.path.dirname(os.path.abspath(smtc_amd.__file__))
+    read = set()
+    for name in os.listdir(os.path.join(pkg, "csrc")):
+        read |= set(re.findall(r'\b(?:getenv|env_int)\(\s*"(MMHIP_[A-Z0-9_]+)"', open(os.path.join(pkg, "csrc", name)).read()))
+    for name in os.listdir(pkg):
+        if name.endswith(".py"):
+            read |= set(re.findall(r'os\.environ(?:\.get|\.setdefault|\.pop)?\s*[\(\[]\s*["\'](MMHIP_[A-Z0-9_]+)["\']', open(os.path.join(pkg, name)).read()))
+    assert read, "the patterns found no switch at all"
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    section = re.search(r"^### Environment switches\n(.*?)^##", design, re.S | re.M)
+    assert section, "DESIGN.md has no 'Environment switches' section"
+    rows = re.findall(r"^\| `(MMHIP_[A-Z0-9_]+)` \|", section.group(1), re.M)
+    assert len(rows) == len(set(rows)), "a switch is listed twice"
+    assert set(rows) == read, {"read but not in the table": sorted(read - set(rows)), "in the table but not read": sorted(set(rows) - read)}

@@ -741,10 +741,9 @@ def test_tiny_image_tower_splits_k_beside_the_text_tower():
 
 @pytest.mark.parametrize("layers_txt,layers_img", [(1, 3), (3, 1)])
 def test_unequal_tower_depths_match_oracle(layers_txt, layers_img):
-    """towers of unequal depth, either one the deeper: under MMHIP_LOCKSTEP=1 (the lockstep test runs this one in its subprocess too) the layers
-    the shorter tower does not have contribute nothing and the deeper tower's GEMMs run alone; on separate streams the two loops simply differ
-    in length.  Five image tokens (image 32 / patch 16), B * T and B * 5 no multiple of any tile.  Outputs match the oracle within the bf16
-    bands of the goldens and repeat bit for bit."""
+    """towers of unequal depth, either one the deeper: the two towers' loops, each on its own stream, simply differ in length.
+    Five image tokens (image 32 / patch 16), B * T and B * 5 no multiple of any tile.  Outputs match the oracle within the bf16 bands of the goldens
+    and repeat bit for bit."""
     kw = dict(layers_txt=layers_txt, layers_img=layers_img, vocab=1000, max_pos=130, image=32, patch=16, p_hidden=0.0, p_attn=0.0)
     cfg = O.OracleConfig(num_labels=3, p_head=0.0, **kw)
     B, T = 3, 20
@@ -1207,17 +1206,6 @@ def test_eval_loop_matches_reference_golden(dtype, tag, itc, itm):
     assert rel < {"bf16x3": 1e-4, "bf16": 5e-3, "f16": 1e-3}[dtype], (res["loss"], ref_loss)
     assert sure.sum() >= (len(sure) - 2 if dtype == "bf16x3" else 1)
     assert np.array_equal(res["predictions"][sure], z[tag + ".predictions"][sure])
-
-
-def test_lockstep_forward_of_both_towers_matches_reference_golden():
-    """MMHIP_LOCKSTEP=1 (opt-in): both towers layer by layer on one stream, same-named GEMMs of a layer paired in one persistent
-    launch (csrc/gemm8.hip GemmNTPair) -- same goldens, same bands; the switch is read once per process, hence the subprocess"""
-    import subprocess, sys
-    env = dict(os.environ, MMHIP_LOCKSTEP="1")
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-k",
-                        "(forward_matches_reference_golden or train_losses_and_grads or ragged_shapes or unequal_tower_depths) and not bf16x3 and not lockstep"],
-                       env=env, capture_output=True, text=True, timeout=900, cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    assert r.returncode == 0 and " passed" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
 
 
 def test_gemm_timing_counts_the_steps_nt_launches():

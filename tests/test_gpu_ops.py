@@ -76,14 +76,13 @@ def _gemm_ref(A, B, bias, act, resid, mulg, keep, scale):
                                         (200, 192, 64, 272), (1000, 768, 768, 272), (8192, 3072, 768, 272), (12608, 768, 3072, 272), (300, 384, 128, 272),
                                         (8192, 3072, 768, 288), (12608, 768, 768, 288), (8192, 3072, 64, 288), (70000, 192, 128, 288), (16384, 2304, 192, 288),
                                         (256, 256, 320, 208), (256, 128, 320, 224), (256, 192, 320, 272), (35000, 256, 192, 240), (35000, 384, 192, 288),
-                                        (4096, 768, 3072, 320), (1152, 768, 2048, 320), (200, 128, 64, 320), (300, 256, 128, 320),
                                         (4096, 768, 3072, 336), (1152, 768, 3072, 336), (200, 128, 64, 336), (300, 384, 192, 336), (4096, 768, 2304, 0)])
 def test_gemm_nt_epilogues(dt, M, N, K, slow):
     """`slow`: bit 0 forces the generic kernel, bits 4.. pick the tile variant (16 = 128x128, 96 = 128x192, 144 = role-specialised 256x128
     (MFMA waves + LDS-DMA loader waves), 160 = 128x96, 192 = role-specialised 256x96, 208 / 224 = deep-pipelined 256x256 / 256x128
     (gemm8.hip: interleaved K-loop schedule, counted vmcnt across raw barriers, register epilogue, bias from LDS), 240 / 256 = the same,
-    persistent, 272 / 288 = deep-pipelined 256x192, one-shot / persistent, 320 / 336 = 128x128 on a 4- / 3-deep LDS ring (round 4: long K on
-    grids of <= 256 tiles; (4096, 768, 2304, 0) takes the 3-deep one by the measured rule))"""
+    persistent, 272 / 288 = deep-pipelined 256x192, one-shot / persistent, 336 = 128x128 on a 3-deep LDS ring (round 4: long K on
+    grids of <= 256 tiles; (4096, 768, 2304, 0) takes it by the measured rule))"""
     code, tdt = DT[dt]
     g = torch.Generator(device="cpu").manual_seed(M + N + K)
     A = (torch.randn(M, K, generator=g) * 0.5).to(tdt).to(dev())

@@ -1,15 +1,15 @@
 """-m gpu: the GEMMs (mmhip_op_gemm_nt, mmhip_op_gemm_tn, mmhip_op_gemm_tn_group), LayerNorm forward / backward and mmhip_op_colsum per element against
 fp64 with the derived bounds of tests/op_bounds.py (gemm_nt_reference, gemm_tn_reference, ln_bounds, ln_bwd_reference, colsum_reference), and -- through
 mmhip_op_last_gemm_path -- the proof of WHICH kernel ran: the launchers fall back silently (a forced tile whose width does not divide N, a deep-pipelined
-tile whose shape rules fail, unaligned operands, TN variants 3 / 4 with Nn % 256), so every case named after a kernel asserts that kernel.
+tile whose shape rules fail, unaligned operands, TN variant 4 with Nn % 256), so every case named after a kernel asserts that kernel.
 
 Every (dtype, shape, slow) case of tests/test_gpu_ops.py's test_gemm_nt_epilogues / test_x3_gemm_nt / test_gemm_tn / test_x3_gemm_tn /
 test_gemm_tn_group_matches_single_problems / test_layernorm_fwd_bwd / test_colsum_and_casts runs here as well (those tests keep their aggregate
 assertions where they are); the per-element checks, NaN pre-fill, guard bands and path assertions are what this module adds.
 
 Path coverage (each in bf16 and f16 unless noted; `slow` = tile code << 4, bit 0 = generic):
-    NT tile kernels (gemm.hip)         1 128x128, 6 128x192, 9 role-specialised 256x128, 10 128x96, 12 role-specialised 256x96, 20 / 21 128x128 on a
-                                       4- / 3-deep ring: the test_gpu_ops.py shapes + test_gemm_nt_tile_edges (K = 1, 2, ring depth, ring depth + 1
+    NT tile kernels (gemm.hip)         1 128x128, 6 128x192, 9 role-specialised 256x128, 10 128x96, 12 role-specialised 256x96, 21 128x128 on a
+                                       3-deep ring: the test_gpu_ops.py shapes + test_gemm_nt_tile_edges (K = 1, 2, ring depth, ring depth + 1
                                        k-tiles of 64; M = 1, BM - 1, BM + 1; N = 1 and 9 tiles wide; guard bands on every buffer)
     NT deep-pipelined (gemm8.hip)      13 / 15 256x256, 14 / 16 256x128, 17 / 18 256x192 (one-shot / persistent): the same two tests; the persistent
                                        loop with more tiles than workgroups on the 8192 / 12608 / 16384 / 35000 / 40000 / 70000-row shapes (asserted)
@@ -18,7 +18,7 @@ Path coverage (each in bf16 and f16 unless noted; `slow` = tile code << 4, bit 0
     NT split-K                         test_gemm_nt_splitk (and not taken with tanh)
     NT generic                         slow = 1, and test_gemm_nt_unaligned_falls_back (A, B, C or the bias off 16-byte alignment)
     parity (x3, fp32 tensors)          direct, small, scratch-split and generic NT: test_x3_gemm_nt_per_element; TN direct and scratch-split
-    TN variants 1 - 5, TN generic      test_gemm_tn_variants (Nn % 256 == 0 and == 128: 3 / 4 fall back to 1), test_gemm_tn_per_element, test_gemm_tn_edges
+    TN variants 1 and 4, TN generic    test_gemm_tn_variants (Nn % 256 == 0 and == 128: 4 falls back to 1), test_gemm_tn_per_element, test_gemm_tn_edges
     TN group                           the test_gpu_ops.py group and one of more than mmhip_tn_max_group() fast problems (flush in the middle)
 
 References: fp64 on the CPU; for shapes of more than 2048 rows the SAME op_bounds code runs on device tensors (torch's fp64 matmul and element-wise
@@ -39,10 +39,10 @@ if torch.cuda.is_available():
 
 SEED, SID = 0x123456789ABCDEF, 21
 VARIANTS = ("plain", "bias_gelu_aux", "bias_drop_resid", "mulgrad_resid", "bias_tanh_f32", "plain_f32")
-TILE_FAMILY = {1: 2, 6: 2, 9: 2, 10: 2, 12: 2, 20: 2, 21: 2, 13: 3, 14: 3, 15: 3, 16: 3, 17: 3, 18: 3}      # _lib.NT_TILE / NT_DEEP
-TILE_BM = {1: 128, 6: 128, 9: 256, 10: 128, 12: 256, 20: 128, 21: 128, 13: 256, 14: 256, 15: 256, 16: 256, 17: 256, 18: 256}
-TILE_BN = {1: 128, 6: 192, 9: 128, 10: 96, 12: 96, 20: 128, 21: 128, 13: 256, 14: 128, 15: 256, 16: 128, 17: 192, 18: 192}
-TILE_DEPTH = {1: 2, 6: 2, 9: 3, 10: 2, 12: 3, 20: 4, 21: 3, 13: 2, 14: 3, 15: 2, 16: 3, 17: 2, 18: 2}          # LDS ring depth in k-tiles of 64 (NTCfg NS, P8::NBUF)
+TILE_FAMILY = {1: 2, 6: 2, 9: 2, 10: 2, 12: 2, 21: 2, 13: 3, 14: 3, 15: 3, 16: 3, 17: 3, 18: 3}      # _lib.NT_TILE / NT_DEEP
+TILE_BM = {1: 128, 6: 128, 9: 256, 10: 128, 12: 256, 21: 128, 13: 256, 14: 256, 15: 256, 16: 256, 17: 256, 18: 256}
+TILE_BN = {1: 128, 6: 192, 9: 128, 10: 96, 12: 96, 21: 128, 13: 256, 14: 128, 15: 256, 16: 128, 17: 192, 18: 192}
+TILE_DEPTH = {1: 2, 6: 2, 9: 3, 10: 2, 12: 3, 21: 3, 13: 2, 14: 3, 15: 2, 16: 3, 17: 2, 18: 2}          # LDS ring depth in k-tiles of 64 (NTCfg NS, P8::NBUF)
 # default dispatch the launcher documents (gemm.hip choose_nt_tile): (family, tile, persistent loop ran several tiles per workgroup or None = not asserted)
 DEFAULT_PATH = {(4096, 768, 2304): (2, 21, None), (512, 768, 3072): (2, 21, None), (300, 480, 128): (2, 10, None),
                 (12608, 2304, 768): (3, 15, 1), (12608, 768, 768): (3, 17, 0)}
@@ -206,7 +206,6 @@ NT_CASES = [(256, 256, 128, 0), (200, 128, 64, 0), (1000, 768, 768, 0), (8192, 2
             (200, 192, 64, 272), (1000, 768, 768, 272), (8192, 3072, 768, 272), (12608, 768, 3072, 272), (300, 384, 128, 272),
             (8192, 3072, 768, 288), (12608, 768, 768, 288), (8192, 3072, 64, 288), (70000, 192, 128, 288), (16384, 2304, 192, 288),
             (256, 256, 320, 208), (256, 128, 320, 224), (256, 192, 320, 272), (35000, 256, 192, 240), (35000, 384, 192, 288),
-            (4096, 768, 3072, 320), (1152, 768, 2048, 320), (200, 128, 64, 320), (300, 256, 128, 320),
             (4096, 768, 3072, 336), (1152, 768, 3072, 336), (200, 128, 64, 336), (300, 384, 192, 336), (4096, 768, 2304, 0),
             (12608, 2304, 768, 0), (12608, 768, 768, 0)]          # the last two: the image-tower shapes on the launcher's own choice
 
@@ -248,6 +247,12 @@ def test_gemm_nt_tile_edges(dt, tile):
     off the tile edge on either side, N one tile and nine tiles wide -- every buffer inside guard bands"""
     for M, N, K in _edge_shapes(tile):
         _run_nt(dt, M, N, K, tile << 4, expect=_expect_forced(dt, M, N, K, tile << 4), guard=True, family="_edge")
+    # a code no launcher has (20 was the 4-deep ring, TN variant 2 its counterpart): refused, not run on some other kernel
+    code, tdt = DT[dt]
+    A, B, Cd = torch.zeros(128, 64, dtype=tdt, device=dev()), torch.zeros(128, 64, dtype=tdt, device=dev()), torch.zeros(128, 128, device=dev())
+    lib = _lib.lib()
+    assert lib.mmhip_op_gemm_nt(code, ptr(A), 64, ptr(B), 64, ptr(Cd), 128, 128, 128, 64, None, 0, None, 0, None, 0, 0.0, 0, 0, None, 0, 1, 20 << 4, stream()) == -1
+    assert lib.mmhip_op_gemm_tn(code, ptr(A), 64, ptr(B), 64, ptr(Cd), 64, 128, 64, 64, 0, 2 << 4, None, stream()) == -1
 
 
 @pytest.mark.parametrize("dt", ["bf16", "f16"])
@@ -299,9 +304,9 @@ def _expect_tn(dt, M, Nn, Nc, slow):
         split = not slow and M % 64 == 0 and Nn % 256 == 0 and Nc % 128 == 0
         return (_lib.TN_TILE | _lib.TN_X3_SPLIT, 4) if split else (_lib.TN_X3_DIRECT, 0)
     v = (slow >> 4) or 4
-    if v in (3, 4) and Nn % 256:
+    if v == 4 and Nn % 256:
         v = 1
-    fast = not (slow & 1) and M % 64 == 0 and Nn % (256 if v in (3, 4) else 128) == 0 and Nc % 128 == 0
+    fast = not (slow & 1) and M % 64 == 0 and Nn % (256 if v == 4 else 128) == 0 and Nc % 128 == 0
     return (_lib.TN_TILE, v) if fast else (_lib.TN_GENERIC, 0)
 
 
@@ -349,12 +354,12 @@ def test_gemm_tn_per_element(dt, M, Nn, Nc, slow):
 
 
 @pytest.mark.parametrize("dt", ["bf16", "f16"])
-@pytest.mark.parametrize("variant", [1, 2, 3, 4, 5])
+@pytest.mark.parametrize("variant", [1, 4])
 @pytest.mark.parametrize("M,Nn,Nc", [(256, 256, 384), (192, 384, 256)])
 def test_gemm_tn_variants(dt, variant, M, Nn, Nc):
-    """slow >> 4 picks the tile kernel: 1 = 128x128 2-stage, 2 = 4-stage ring, 3 = 256x128 3-stage, 4 = role-specialised 256x128, 5 = role-specialised 128x128;
-    with Nn % 256 == 128 the 256-row variants 3 / 4 fall back to 1 -- seen through the path report"""
-    want = 1 if (variant in (3, 4) and Nn % 256) else variant
+    """slow >> 4 picks the tile kernel: 1 = 128x128 2-stage, 4 = role-specialised 256x128;
+    with Nn % 256 == 128 the 256-row variant 4 falls back to 1 -- seen through the path report"""
+    want = 1 if (variant == 4 and Nn % 256) else variant
     assert _expect_tn(dt, M, Nn, Nc, variant << 4) == (_lib.TN_TILE, want)
     _run_tn(dt, M, Nn, Nc, variant << 4, (_lib.TN_TILE, want), family="_variant")
 

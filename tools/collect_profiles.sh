@@ -43,7 +43,7 @@ fi
 if [ "$PART" = b ]; then
 step diagnostics
 cd $R
-{ BENCH_ARGS="--no-at-tolerance --no-parity" tools/ab_env.sh "BASE=1" "MMHIP_EARLY_ADAMW=0" "MMHIP_OVERLAP=0" "MMHIP_DETERMINISTIC=1"; BENCH_ARGS="--dtype bf16x3 --steps 6 --warmup 3 --no-parity --no-at-tolerance" tools/ab_env.sh "MMHIP_X3_BWD=3" "MMHIP_X3_BWD=2" "MMHIP_X3_BWD=1" "MMHIP_X3_BWD=1 MMHIP_LOCKSTEP=1"; BENCH_ARGS="--config 5 --steps 12 --warmup 4" tools/ab_env.sh "BASE=1" "MMHIP_EARLY_ADAMW=0" "MMHIP_EARLY_STREAMS=0"; } > $O/step_ab.txt 2>/dev/null
+{ BENCH_ARGS="--no-at-tolerance --no-parity" tools/ab_env.sh "BASE=1" "MMHIP_EARLY_ADAMW=0" "MMHIP_OVERLAP=0" "MMHIP_DETERMINISTIC=1"; BENCH_ARGS="--dtype bf16x3 --steps 6 --warmup 3 --no-parity --no-at-tolerance" tools/ab_env.sh "MMHIP_X3_BWD=3" "MMHIP_X3_BWD=2" "MMHIP_X3_BWD=1"; BENCH_ARGS="--config 5 --steps 12 --warmup 4" tools/ab_env.sh "BASE=1" "MMHIP_EARLY_ADAMW=0" "MMHIP_EARLY_STREAMS=0"; } > $O/step_ab.txt 2>/dev/null
 python3 tools/loader_bench.py > $O/loader_bench.txt 2>/dev/null
 python3 tools/loader_bench.py --epoch_prefetch >> $O/loader_bench.txt 2>/dev/null
 python3 -m pytest tests/test_gpu_model.py -q -s -k "train_losses_and_grads or dropout_train_step or forward_matches or config4 or eval_loop" 2>&1 | grep -v "^$" > $O/parity.txt
