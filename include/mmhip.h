@@ -220,6 +220,40 @@ int mmhip_adamw_rows_guarded(float* p, float* g, float* m, float* v, int rows, i
                              float beta2, float eps, float weight_decay, int step, float grad_scale, int zero_grad, void* stream,
                              uint32_t* guard_words2);
 int mmhip_set_loss_scale(mmhip_handle h, float loss_scale);
+
+/* ---- global-norm gradient clipping (torch.nn.utils.clip_grad_norm_, HF max_grad_norm; opt-in, no reference counterpart in the trainers).
+ * Over the parameters that receive a gradient for the step's flag set -- the merged ranges the step hands to AdamW plus the word-table rows
+ * whose row_state bit0 is set:
+ *     total = grad_scale * sqrt(sum g^2)        coef = min(1, max_norm / (total + 1e-6))        g_used = g * (grad_scale * coef)
+ * The product is formed inside AdamW; the gradient buffer is not rewritten.  coef is exactly 1.0f whenever total + 1e-6 <= max_norm, and an
+ * unclipped step then updates with the same bits as a step whose AdamW launches all follow the backward (MMHIP_EARLY_ADAMW=0).  A non-finite
+ * element adds 0 to the sum (AdamW reads it as 0 and counts it, as before); unflagged word-table rows are not read.  The flat gradient holds
+ * unscaled gradients in f16 too (the loss scale is divided out where weight gradients are written), so grad_scale is the only factor.
+ * The state block is the caller's: the size the state_bytes call returns, 16-byte aligned, ZERO before first use.  Its first 16 bytes are public,
+ *     {float coef, float total_norm, uint32 clipped_steps, uint32 steps}
+ * (steps: norms taken; clipped_steps: those with coef < 1; on a void f16 step -- guard flag set -- neither advances and coef is irrelevant);
+ * the rest is scratch for the partial sums.  The sum is bit-reproducible: fixed grids, a fixed order, no float atomics -- the same gradient
+ * gives the same four words on every device and under every CU cap.  No workspace size and no parameter offset changes.
+ * The set call arms the handle (any handle kind; the txt / img forms below check the kind first): while armed, every AdamW launch of the
+ * fused steps follows the backward and the norm (three launches: dense partials, row partials, finalize) and reads the coefficient.
+ * clip_state NULL or max_norm <= 0 disarms; NaN / inf: MMHIP_E_INVALID.  The data-parallel train step on an armed handle returns
+ * MMHIP_E_STATE before anything is enqueued (the word-table rows arrive after the dense optimizer; a sharded optimizer would need a sum of
+ * partial norms across ranks).
+ * The op form enqueues everything from the gradients to the four words for a caller that runs the optimizer itself: up to 16 dense
+ * segments {seg_g[i], seg_n[i]} (host arrays of device pointers / element counts; any n, 16-byte aligned starts) and the rows of
+ * row_g [rows, width] with row_state[r] & 1 (rows = 0: none).  guard_words2: the step guard's {counter, flag} or NULL.  MMHIP_E_INVALID, nothing
+ * enqueued: segments < 0 or > 16, a null or misaligned pointer, width % 4, rows without row_state, max_norm not a positive finite number.
+ * The clipped AdamW forms take the guarded forms' arguments and the state block (NULL: exactly the guarded form). */
+uint64_t mmhip_grad_clip_state_bytes(void);
+int mmhip_set_grad_clip(mmhip_handle h, float max_norm, void* clip_state);
+int mmhip_op_grad_clip(const float* const* seg_g, const uint64_t* seg_n, int segments, const float* row_g, int rows, int width,
+                       const uint8_t* row_state, float max_norm, float grad_scale, const uint32_t* guard_words2, void* clip_state, void* stream);
+int mmhip_adamw_clipped(float* p, float* g, float* m, float* v, uint64_t n, float lr, float beta1, float beta2, float eps,
+                        float weight_decay, int step, float grad_scale, int zero_grad, void* stream, uint32_t* guard_words2,
+                        const void* clip_state);
+int mmhip_adamw_rows_clipped(float* p, float* g, float* m, float* v, int rows, int width, uint8_t* row_state, float lr, float beta1,
+                             float beta2, float eps, float weight_decay, int step, float grad_scale, int zero_grad, void* stream,
+                             uint32_t* guard_words2, const void* clip_state);
 /* Clamped-index counter.  mmhip_forward / mmhip_train_step clamp token ids into [0, vocab) on their way into the engine (above: why); the reference
  * raises IndexError for such an id on the CPU (nn.Embedding).  With a device word registered here every clamped index adds 1 to it, so a caller can
  * turn the silent wrong row into the reference's error one step late and without a synchronisation (the shipped binding copies the word to pinned
@@ -624,6 +658,8 @@ int mmhip_txt_backward(mmhip_txt_handle h, const float* d_logits, void* stream);
 int mmhip_txt_train_step(mmhip_txt_handle h, const int64_t* ids, const int64_t* mask, const int64_t* type_ids, const int64_t* onehot, const float* class_w,
                          int B, int T, uint64_t seed, float* adam_m, float* adam_v, float lr, float beta1, float beta2, float eps, float weight_decay,
                          int step, float* loss, int* n_correct, void* stream);
+/* global-norm gradient clipping of the fused step, as mmhip_set_grad_clip on this handle kind */
+int mmhip_txt_set_grad_clip(mmhip_txt_handle h, float max_norm, void* clip_state);
 /* the head's two launches alone (operator tests).  x: CLS rows, row b at element b * x_stride, x_dtype MMHIP_BF16 | _F16 | _F32 | _PAIR (pair rows count
  * 4-byte elements); dropout p with the engine's hash (stream 2, element b * H + c).  Limits: C <= 16, H % 64 == 0, H <= 1024.
  * fwd: logits [B,C]; with onehot also loss [1], n_correct [1], d_logits [B,C] (each optional).  bwd: dW [C,H], db [C] (accumulate != 0: added),
@@ -690,6 +726,7 @@ int mmhip_img_backward(mmhip_img_handle h, const float* d_logits, void* stream);
  * operand refresh on the side stream beside the stages below -> the remaining dense ranges.  Single process. */
 int mmhip_img_train_step(mmhip_img_handle h, const float* pixels, const int64_t* onehot, const float* class_w, int B, float* adam_m, float* adam_v,
                          float lr, float beta1, float beta2, float eps, float weight_decay, int step, float* loss, int* n_correct, void* stream);
+int mmhip_img_set_grad_clip(mmhip_img_handle h, float max_norm, void* clip_state);          /* as mmhip_txt_set_grad_clip */
 /* Backward of the ViT token assembly alone (operator tests; csrc/rowops.hip launch_vit_embed_bwd).  dx [B*P, H] in `dtype` (MMHIP_BF16 | _F16 | _F32;
  * MMHIP_PAIR reads fp32 like _F32).  dpos fp32 [P, H] += alpha * sum_b dx[b, p, :]; dcls fp32 [H] += alpha * sum_b dx[b, 0, :]; dpe [B*(P-1), H]: the
  * patch rows, compact -- the same words for _BF16 / _F16 / _F32, rows [hi(H) | lo(H)] bf16 for _PAIR (pair_hi_only != 0: the hi plane alone).

@@ -103,6 +103,13 @@ _SIGS = {
     "mmhip_set_guard": (I, [P, P]),
     "mmhip_adamw_guarded": (I, [P, P, P, P, U64, F, F, F, F, F, I, F, I, P, P]),
     "mmhip_adamw_rows_guarded": (I, [P, P, P, P, I, I, P, F, F, F, F, F, I, F, I, P, P]),
+    "mmhip_grad_clip_state_bytes": (U64, []),
+    "mmhip_set_grad_clip": (I, [P, F, P]),
+    "mmhip_txt_set_grad_clip": (I, [P, F, P]),
+    "mmhip_img_set_grad_clip": (I, [P, F, P]),
+    "mmhip_op_grad_clip": (I, [P, P, I, P, I, I, P, F, F, P, P, P]),
+    "mmhip_adamw_clipped": (I, [P, P, P, P, U64, F, F, F, F, F, I, F, I, P, P, P]),
+    "mmhip_adamw_rows_clipped": (I, [P, P, P, P, I, I, P, F, F, F, F, F, I, F, I, P, P, P]),
     "mmhip_set_loss_scale": (I, [P, F]),
     "mmhip_set_backward_products": (I, [P, I]),
     "mmhip_set_drop_path": (I, [P, F]),

@@ -568,4 +568,24 @@ int mmhip_op_embed_bwd(int dtype, const void* dx, const void* xhat, const float*
     return r == hipErrorInvalidValue ? MMHIP_E_INVALID : (int)r;
 }
 
+// ------------------------------------------------------------------------------------------------ global-norm gradient clipping
+uint64_t mmhip_grad_clip_state_bytes(void) { return (uint64_t)grad_clip_state_bytes(); }
+// everything from the gradients to the four public words; every argument is checked on the host before the first launch
+int mmhip_op_grad_clip(const float* const* seg_g, const uint64_t* seg_n, int segments, const float* row_g, int rows, int width, const uint8_t* row_state,
+                       float max_norm, float grad_scale, const uint32_t* guard_words2, void* clip_state, void* stream) {
+    if (segments < 0 || segments > GRADNORM_MAX_SEGMENTS || (segments > 0 && (!seg_g || !seg_n))) return MMHIP_E_INVALID;
+    if (!clip_state || ((uintptr_t)clip_state & 15) || ((uintptr_t)guard_words2 & 3)) return MMHIP_E_INVALID;
+    if (!(max_norm > 0.f) || std::isinf(max_norm) || std::isnan(grad_scale) || std::isinf(grad_scale)) return MMHIP_E_INVALID;
+    if (rows < 0 || (rows > 0 && (!row_g || !row_state || ((uintptr_t)row_g & 15) || width <= 0 || width % 4))) return MMHIP_E_INVALID;
+    GradNormSegments sg{};
+    for (int i = 0; i < segments; ++i) {
+        if (!seg_g[i] || ((uintptr_t)seg_g[i] & 15)) return MMHIP_E_INVALID;
+        sg.g[i] = seg_g[i]; sg.n[i] = (size_t)seg_n[i];
+    }
+    sg.count = segments;
+    const hipError_t r = launch_grad_clip(sg, rows > 0 ? row_g : nullptr, rows, width, row_state, max_norm, grad_scale, guard_words2 ? guard_words2 + 1 : nullptr,
+                                          clip_state, (hipStream_t)stream);
+    return r == hipErrorInvalidValue ? MMHIP_E_INVALID : (int)r;
+}
+
 }  // extern "C"

@@ -69,6 +69,8 @@ struct mmhip_engine {
     unsigned* bad_index = nullptr;         // caller-owned device word counting token ids that had to be clamped into the word table (mmhip_set_index_counter)
     unsigned* guard = nullptr;             // caller-owned overflow-guard words of THIS handle, {counter, void-step flag} (mmhip_set_guard); null: the
                                            // process-wide registration of mmhip_set_step_guard, if any
+    void* clip_state = nullptr;            // caller-owned state block of global-norm gradient clipping (mmhip_set_grad_clip); null: not armed
+    float clip_max = 0.f;                  // its threshold (> 0 while armed)
     size_t g_set[2][6];      // double-buffered backward temporaries read by the side stream: dpre2, ddrop2, du, dpre1, ddrop1, dqkv
     size_t g_dx, g_dx2, g_dpre, g_ddrop, g_dpre1, g_ddrop1, g_dqkv, g_dctx, g_du;                               // backward temporaries
     // heads (fp32) ----------------------------------------------------------------------
@@ -1829,6 +1831,14 @@ int mmhip_set_drop_path(mmhip_handle h, float rate) {
     h->drop_path = rate;
     return 0;
 }
+// global-norm gradient clipping of the fused steps: armed with a threshold and the caller's state block, disarmed by NULL or max_norm <= 0
+int mmhip_set_grad_clip(mmhip_handle h, float max_norm, void* clip_state) {
+    if (!h || std::isnan(max_norm) || std::isinf(max_norm) || ((uintptr_t)clip_state & 15)) return MMHIP_E_INVALID;
+    const bool arm = clip_state && max_norm > 0.f;
+    h->clip_state = arm ? clip_state : nullptr;
+    h->clip_max = arm ? max_norm : 0.f;
+    return 0;
+}
 int mmhip_set_loss_scale(mmhip_handle h, float loss_scale) {
     if (!h || !(loss_scale >= 0.f)) return MMHIP_E_INVALID;
     h->cfg.loss_scale = loss_scale;
@@ -1836,11 +1846,14 @@ int mmhip_set_loss_scale(mmhip_handle h, float loss_scale) {
 }
 
 static int adamw_impl(float* p, float* g, float* m, float* v, uint64_t n, float lr, float beta1, float beta2, float eps,
-                      float weight_decay, int step, float grad_scale, int zero_grad, void* stream, unsigned* g_nonfinite, const unsigned* g_skip) {
+                      float weight_decay, int step, float grad_scale, int zero_grad, void* stream, unsigned* g_nonfinite, const unsigned* g_skip,
+                      const void* clip_state = nullptr) {
     if (!p || !g || !m || !v || step < 1) return MMHIP_E_INVALID;
     if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return MMHIP_E_INVALID;
+    if ((uintptr_t)clip_state & 15) return MMHIP_E_INVALID;
     AdamWArgs a = adamw_args(lr, beta1, beta2, eps, weight_decay, step, grad_scale, zero_grad, g_nonfinite, g_skip);
     a.p = p; a.g = g; a.m = m; a.v = v; a.n = n;
+    a.clip = static_cast<const float*>(clip_state);          // word 0 of the block: the coefficient
     CHECK_HIP(launch_adamw(a, (hipStream_t)stream));
     return 0;
 }
@@ -1853,6 +1866,12 @@ int mmhip_adamw_guarded(float* p, float* g, float* m, float* v, uint64_t n, floa
     if ((uintptr_t)guard_words2 & 3) return MMHIP_E_INVALID;
     return adamw_impl(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, zero_grad, stream, guard_words2, guard_words2 ? guard_words2 + 1 : nullptr);
 }
+int mmhip_adamw_clipped(float* p, float* g, float* m, float* v, uint64_t n, float lr, float beta1, float beta2, float eps,
+                        float weight_decay, int step, float grad_scale, int zero_grad, void* stream, uint32_t* guard_words2, const void* clip_state) {
+    if ((uintptr_t)guard_words2 & 3) return MMHIP_E_INVALID;
+    return adamw_impl(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, zero_grad, stream, guard_words2, guard_words2 ? guard_words2 + 1 : nullptr,
+                      clip_state);
+}
 
 int mmhip_set_row_state(mmhip_handle h, uint8_t* row_state) {
     if (!h) return MMHIP_E_INVALID;
@@ -1862,11 +1881,14 @@ int mmhip_set_row_state(mmhip_handle h, uint8_t* row_state) {
 }
 
 static int adamw_rows_impl(float* p, float* g, float* m, float* v, int rows, int width, uint8_t* row_state, float lr, float beta1, float beta2,
-                           float eps, float weight_decay, int step, float grad_scale, int zero_grad, void* stream, unsigned* g_nonfinite, const unsigned* g_skip) {
+                           float eps, float weight_decay, int step, float grad_scale, int zero_grad, void* stream, unsigned* g_nonfinite, const unsigned* g_skip,
+                           const void* clip_state = nullptr) {
     if (!p || !g || !m || !v || !row_state || step < 1 || rows < 0 || width <= 0 || width % 4) return MMHIP_E_INVALID;
     if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return MMHIP_E_INVALID;
+    if ((uintptr_t)clip_state & 15) return MMHIP_E_INVALID;
     AdamWArgs a = adamw_args(lr, beta1, beta2, eps, weight_decay, step, grad_scale, zero_grad, g_nonfinite, g_skip);
     a.p = p; a.g = g; a.m = m; a.v = v; a.n = (size_t)rows * width;
+    a.clip = static_cast<const float*>(clip_state);
     CHECK_HIP(launch_adamw_rows(a, rows, width, row_state, (hipStream_t)stream));
     return 0;
 }
@@ -1880,9 +1902,60 @@ int mmhip_adamw_rows_guarded(float* p, float* g, float* m, float* v, int rows, i
     return adamw_rows_impl(p, g, m, v, rows, width, row_state, lr, beta1, beta2, eps, weight_decay, step, grad_scale, zero_grad, stream, guard_words2,
                            guard_words2 ? guard_words2 + 1 : nullptr);
 }
+int mmhip_adamw_rows_clipped(float* p, float* g, float* m, float* v, int rows, int width, uint8_t* row_state, float lr, float beta1, float beta2,
+                             float eps, float weight_decay, int step, float grad_scale, int zero_grad, void* stream, uint32_t* guard_words2,
+                             const void* clip_state) {
+    if ((uintptr_t)guard_words2 & 3) return MMHIP_E_INVALID;
+    return adamw_rows_impl(p, g, m, v, rows, width, row_state, lr, beta1, beta2, eps, weight_decay, step, grad_scale, zero_grad, stream, guard_words2,
+                           guard_words2 ? guard_words2 + 1 : nullptr, clip_state);
+}
 
 static int step_backward_update(mmhip_handle h, int use_itc, int use_itm, float* adam_m, float* adam_v, float lr, float beta1, float beta2, float eps,
                                 float weight_decay, int step, float grad_scale, void* stream, mmhip_exchange_cb cb, void* user);
+
+// The range walk of a fused step, written once: the merged [begin, end) ranges of the active gradient groups in address order, as the dense part of
+// each (below the word table) and whether the word table is among them.  layer_done (may be null): text layers whose optimizer has already run beside
+// the backward are skipped.  The AdamW launches, the norm of an armed clip and the check ahead of an armed step all go over this list.
+struct StepRange { uint64_t b, e; };
+static void collect_step_ranges(const mmhip_engine& e, int use_itc, int use_itm, const std::vector<char>* layer_done, std::vector<StepRange>& dense, bool& rows_due) {
+    const bool act[6] = {false, use_itc != 0, use_itm != 0, e.cfg.fusion == MMHIP_FUSION_ATTENTION, true, false};
+    const uint64_t w0 = e.is_image() ? e.n_train : e.t_word;          // (no word table in an image-only handle)
+    const std::vector<LayerOff>& lay = e.lay();
+    const int L = e.nl();
+    uint64_t rb = 0, re = 0;
+    bool open = false;
+    dense.clear();
+    rows_due = false;
+    auto flush = [&]() {
+        if (!open || re <= rb) return;
+        const uint64_t dense_end = re < w0 ? re : w0;
+        if (dense_end > rb) dense.push_back(StepRange{rb, dense_end});
+        if (re > w0) rows_due = true;          // the word table goes last: under data parallelism its rows are still travelling
+    };
+    auto in_layer = [&](uint64_t off) {          // a text layer whose optimizer has already run (beside the backward)
+        if (!layer_done) return false;
+        for (int l = 0; l < L; ++l) if ((*layer_done)[l] && off >= lay[l].begin && off < lay[l].end) return true;
+        return false;
+    };
+    for (const auto& p : e.params) {
+        if (p.buffer != 1 || !act[p.group] || in_layer(p.offset)) continue;
+        const uint64_t b = p.offset, en = p.offset + ((p.numel + 3) & ~(uint64_t)3);
+        if (open && b == re) { re = en; continue; }
+        flush();
+        rb = b; re = en; open = true;
+    }
+    flush();
+}
+// An armed clip's refusals are known from the layout and the handle: more merged ranges than one norm launch takes, a word table without its row
+// flags.  Asked before the step's forward, so that a refusal enqueues nothing (as the data-parallel refusal does).
+static int clip_step_check(const mmhip_engine& e, int use_itc, int use_itm) {
+    if (!e.clip_state) return 0;
+    std::vector<StepRange> dense;
+    bool rows_due = false;
+    collect_step_ranges(e, use_itc, use_itm, nullptr, dense, rows_due);
+    if (dense.size() > (size_t)GRADNORM_MAX_SEGMENTS || (rows_due && !e.word_row_state)) return MMHIP_E_STATE;
+    return 0;
+}
 
 // One fused training step, enqueued natively (no per-stage host round trips): forward (train mode) -> loss -> backward ->
 // AdamW over the ranges that receive gradients for this flag set (torch skips `grad is None` tensors) ->
@@ -1897,6 +1970,7 @@ static int train_step_impl(mmhip_handle h, const int64_t* ids, const int64_t* ma
     if (use_itm && (!tim_ids || !lbl_tim)) return MMHIP_E_INVALID;
     mmhip_engine& e = *h;
     if (e.aspect() && (use_itm || tim_ids)) return MMHIP_E_INVALID;      // models/mm_late.py:181 (mmhip_forward)
+    CHECK_RC(clip_step_check(e, use_itc, use_itm));
     e.skip_itc = !use_itc;
     const int rf = mmhip_forward(h, ids, mask, pixels, use_itm ? tim_ids : nullptr, use_itm ? tim_mask : nullptr, B, T, 1, seed, nullptr, nullptr,
                                  nullptr, nullptr, stream);
@@ -1925,7 +1999,13 @@ static int step_backward_update(mmhip_handle h, int use_itc, int use_itm, float*
     // f16 with the step guard armed: a void step is only known when the backward has reached the embeddings, so every AdamW waits for it
     unsigned* gc = guard_counter(e);
     unsigned* gf = guard_flag(e);
-    const int early = (e.dt() == DT_F16 && gf) ? 0 : env_int("MMHIP_EARLY_ADAMW", 1);          // read per step: tests compare both orders in one process
+    // global-norm clipping armed: the coefficient is known only when the whole gradient is, so -- by the same rule -- every AdamW waits for the backward
+    const void* clip = e.clip_state;
+    const int early = ((e.dt() == DT_F16 && gf) || clip) ? 0 : env_int("MMHIP_EARLY_ADAMW", 1);          // read per step: tests compare both orders in one process
+    if (clip && !getenv("MMHIP_EARLY_ADAMW")) {
+        static bool told = false;
+        if (!told && getenv("MMHIP_VERBOSE")) { fprintf(stderr, "[mmhip] gradient clipping armed: every AdamW launch follows the backward and the norm (no per-layer optimizer beside it)\n"); told = true; }
+    }
     if (e.dt() == DT_F16 && gf && !getenv("MMHIP_EARLY_ADAMW")) {
         static bool told = false;
         if (!told && getenv("MMHIP_VERBOSE")) { fprintf(stderr, "[mmhip] f16 with the step guard armed: every AdamW launch follows the backward (no per-layer optimizer beside it)\n"); told = true; }
@@ -2001,32 +2081,23 @@ static int step_backward_update(mmhip_handle h, int use_itc, int use_itm, float*
     }
     CHECK_RC(e.span(4, s));
     // merged [begin, end) ranges of the active gradient groups, in address order (text layers already stepped: skipped)
-    bool act[6] = {false, use_itc != 0, use_itm != 0, e.cfg.fusion == MMHIP_FUSION_ATTENTION, true, false};
     const uint64_t w0 = e.is_image() ? e.n_train : e.t_word, V = (uint64_t)e.cfg.vocab, H = (uint64_t)e.cfg.hidden;      // (no word table in an image-only handle)
-    uint64_t rb = 0, re = 0;
-    bool open = false;
+    std::vector<StepRange> dense;
     bool rows_due = false;
-    auto flush = [&]() -> int {
-        if (!open || re <= rb) return 0;
-        const uint64_t dense_end = re < w0 ? re : w0;
-        if (dense_end > rb && !dense_by_caller)
-            CHECK_RC(adamw_impl(e.train + rb, e.grad + rb, adam_m + rb, adam_v + rb, dense_end - rb, lr, beta1, beta2, eps, weight_decay, step,
-                                   grad_scale, 1, stream, gc, gf));
-        if (re > w0) rows_due = true;          // the word table goes last: under data parallelism its rows are still travelling
-        return 0;
-    };
-    auto in_layer = [&](uint64_t off) {          // a text layer whose optimizer has already run (beside the backward)
-        for (int l = 0; l < L; ++l) if (layer_done[l] && off >= lay[l].begin && off < lay[l].end) return true;
-        return false;
-    };
-    for (const auto& p : e.params) {
-        if (p.buffer != 1 || !act[p.group] || in_layer(p.offset)) continue;
-        const uint64_t b = p.offset, en = p.offset + ((p.numel + 3) & ~(uint64_t)3);
-        if (open && b == re) { re = en; continue; }
-        CHECK_RC(flush());
-        rb = b; re = en; open = true;
+    collect_step_ranges(e, use_itc, use_itm, &layer_done, dense, rows_due);
+    if (clip) {
+        // (more than GRADNORM_MAX_SEGMENTS ranges, or a word table without row flags: clip_step_check refused the step before its forward)
+        // the norm over exactly what is stepped below: the dense ranges and the word-table rows the backward flagged (an unflagged row's gradient is
+        // zero by the row-lazy contract).  The flat gradient holds UNSCALED gradients in f16 as well (1 / gscale() is applied where they are written),
+        // so the factor is AdamW's grad_scale and nothing else
+        GradNormSegments sg{};
+        for (const StepRange& r : dense) { sg.g[sg.count] = e.grad + r.b; sg.n[sg.count] = r.e - r.b; ++sg.count; }
+        CHECK_HIP(launch_grad_clip(sg, rows_due ? e.grad + w0 : nullptr, rows_due ? (int)V : 0, (int)H, e.word_row_state, e.clip_max, grad_scale, gf, e.clip_state, s));
     }
-    CHECK_RC(flush());
+    if (!dense_by_caller)
+        for (const StepRange& r : dense)
+            CHECK_RC(adamw_impl(e.train + r.b, e.grad + r.b, adam_m + r.b, adam_v + r.b, r.e - r.b, lr, beta1, beta2, eps, weight_decay, step, grad_scale, 1,
+                                stream, gc, gf, clip));
     for (int l = 0; l < L; ++l)          // 16-bit GEMM operand copies of the layers stepped just now: no word-table dependence
         if (!layer_done[l]) CHECK_RC(refresh_layer(e, e.train, lay[l], lay16[l], true, s, lH, lI));
     if (e.is_image())          // the patch weight was stepped with the embeddings' range just now
@@ -2035,7 +2106,7 @@ static int step_backward_update(mmhip_handle h, int use_itc, int use_itm, float*
         if (cb) CHECK_RC(cb(user, MMHIP_CB_FINISH_ROWS));                 // the exchanged word rows are summed into the gradient
         if (!e.word_row_state) return MMHIP_E_STATE;
         CHECK_RC(adamw_rows_impl(e.train + w0, e.grad + w0, adam_m + w0, adam_v + w0, (int)V, (int)H, e.word_row_state, lr, beta1, beta2, eps,
-                                    weight_decay, step, grad_scale, 1, stream, gc, gf));
+                                    weight_decay, step, grad_scale, 1, stream, gc, gf, clip));
     }
     return e.span(5, s);
 }
@@ -2054,6 +2125,9 @@ int mmhip_train_step_dp(mmhip_handle h, const int64_t* ids, const int64_t* mask,
                         float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, float* loss,
                         int* n_correct, void* stream, mmhip_exchange_cb on_stage, void* user) {
     if (!on_stage) return MMHIP_E_INVALID;
+    // global-norm clipping needs the whole summed gradient before the first AdamW launch; here the word-table rows arrive after the dense optimizer
+    // (and a sharded caller holds partial norms only): refused before anything is enqueued
+    if (h && h->clip_state) return MMHIP_E_STATE;
     return train_step_impl(h, ids, mask, pixels, tim_ids, tim_mask, lbl_tim, onehot, class_w, B, T, seed, use_itc, use_itm, w_cls, w_itc, w_itm,
                            adam_m, adam_v, lr, beta1, beta2, eps, weight_decay, step, grad_scale, loss, n_correct, stream, on_stage, user);
 }
@@ -2244,10 +2318,14 @@ int mmhip_txt_backward(mmhip_txt_handle h, const float* d_logits, void* stream) 
     if (!is_kind(h, Kind::TEXT)) return MMHIP_E_STATE;
     return mmhip_backward(h, d_logits, nullptr, nullptr, nullptr, stream);
 }
+int mmhip_txt_set_grad_clip(mmhip_txt_handle h, float max_norm, void* clip_state) {
+    return is_kind(h, Kind::TEXT) ? mmhip_set_grad_clip(h, max_norm, clip_state) : MMHIP_E_INVALID;
+}
 int mmhip_txt_train_step(mmhip_txt_handle h, const int64_t* ids, const int64_t* mask, const int64_t* type_ids, const int64_t* onehot, const float* class_w,
                          int B, int T, uint64_t seed, float* adam_m, float* adam_v, float lr, float beta1, float beta2, float eps, float weight_decay,
                          int step, float* loss, int* n_correct, void* stream) {
     CHECK_RC(one_tower_step_guard(h, Kind::TEXT, adam_m, adam_v, onehot, step));
+    CHECK_RC(clip_step_check(*h, 0, 0));
     CHECK_RC(txt_forward_impl(h, ids, mask, type_ids, B, T, 1, seed, onehot, class_w, nullptr, loss, n_correct, stream));
     return step_backward_update(h, 0, 0, adam_m, adam_v, lr, beta1, beta2, eps, weight_decay, step, 1.0f, stream, nullptr, nullptr);
 }
@@ -2321,9 +2399,13 @@ int mmhip_img_backward(mmhip_img_handle h, const float* d_logits, void* stream) 
     if (!is_kind(h, Kind::IMAGE)) return MMHIP_E_STATE;
     return mmhip_backward(h, d_logits, nullptr, nullptr, nullptr, stream);
 }
+int mmhip_img_set_grad_clip(mmhip_img_handle h, float max_norm, void* clip_state) {
+    return is_kind(h, Kind::IMAGE) ? mmhip_set_grad_clip(h, max_norm, clip_state) : MMHIP_E_INVALID;
+}
 int mmhip_img_train_step(mmhip_img_handle h, const float* pixels, const int64_t* onehot, const float* class_w, int B, float* adam_m, float* adam_v,
                          float lr, float beta1, float beta2, float eps, float weight_decay, int step, float* loss, int* n_correct, void* stream) {
     CHECK_RC(one_tower_step_guard(h, Kind::IMAGE, adam_m, adam_v, onehot, step));
+    CHECK_RC(clip_step_check(*h, 0, 0));
     CHECK_RC(img_forward_impl(h, pixels, B, 1, onehot, class_w, nullptr, loss, n_correct, stream));
     return step_backward_update(h, 0, 0, adam_m, adam_v, lr, beta1, beta2, eps, weight_decay, step, 1.0f, stream, nullptr, nullptr);
 }

@@ -506,12 +506,13 @@ __global__ __launch_bounds__(256) void adamw_kernel(AdamWArgs a) {
     bool bad = false;
     const float one_m_b1 = 1.f - a.beta1, one_m_b2 = 1.f - a.beta2;
     const float decay = 1.f - a.lr * a.wd, step = a.lr / a.bc1;
+    const float gscale = a.clip ? a.grad_scale * *a.clip : a.grad_scale;          // global-norm clipping: the coefficient of launch_grad_clip
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
         f32x4 p = reinterpret_cast<f32x4*>(a.p)[i], g = reinterpret_cast<f32x4*>(a.g)[i];
         f32x4 m = reinterpret_cast<f32x4*>(a.m)[i], v = reinterpret_cast<f32x4*>(a.v)[i];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const float ge = guard_finite(g[e] * a.grad_scale, bad);
+            const float ge = guard_finite(g[e] * gscale, bad);
             p[e] *= decay;
             m[e] = m[e] + one_m_b1 * (ge - m[e]);
             v[e] = v[e] * a.beta2 + one_m_b2 * ge * ge;
@@ -525,7 +526,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(AdamWArgs a) {
     }
     if (blockIdx.x == 0 && threadIdx.x < (a.n & 3)) {          // the n & 3 tail: its non-finite elements count with the thread's others
         const size_t i = n4 * 4 + threadIdx.x;
-        const float ge = guard_finite(a.g[i] * a.grad_scale, bad);
+        const float ge = guard_finite(a.g[i] * gscale, bad);
         float p = a.p[i] * decay;
         const float m = a.m[i] + one_m_b1 * (ge - a.m[i]);
         const float v = a.v[i] * a.beta2 + one_m_b2 * ge * ge;
@@ -625,6 +626,7 @@ __global__ __launch_bounds__(256) void adamw_rows_kernel(AdamWArgs a, int rows, 
     const float one_m_b1 = 1.f - a.beta1, one_m_b2 = 1.f - a.beta2;
     const float decay = 1.f - a.lr * a.wd, step = a.lr / a.bc1;
     bool bad = false;
+    const float gscale = a.clip ? a.grad_scale * *a.clip : a.grad_scale;
     if (a.skip && *a.skip) {          // void step: rows that received a gradient lose it (and the flag), nothing else moves
         for (int row = blockIdx.x * 4 + (threadIdx.x >> 6); row < rows; row += gridDim.x * 4) {
             const int st = state[row];
@@ -660,7 +662,7 @@ __global__ __launch_bounds__(256) void adamw_rows_kernel(AdamWArgs a, int rows, 
             f32x4 g = has_g ? g4[c] : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float ge = guard_finite(g[e] * a.grad_scale, bad);
+                const float ge = guard_finite(g[e] * gscale, bad);
                 p[e] *= decay;
                 m[e] = m[e] + one_m_b1 * (ge - m[e]);
                 v[e] = v[e] * a.beta2 + one_m_b2 * ge * ge;

@@ -411,11 +411,27 @@ struct AdamWArgs {
     unsigned* nonfinite;  // optional device counter: a non-finite gradient element is treated as 0 (its moments are not poisoned) and counted
     const unsigned* skip; // optional device word: non-zero = this step's gradients are void (the backward met a non-finite value in its
                           // 16-bit chain): nothing is updated, the gradient is only cleared (zero_grad) -- the whole step is skipped
+    const float* clip;    // optional device word, the coefficient of launch_grad_clip: gradients are multiplied by grad_scale * *clip.  Null: today's
+                          // arithmetic (grad_scale alone); a coefficient of exactly 1.0f gives the same bits
 };
 hipError_t launch_adamw(const AdamWArgs& a, hipStream_t s);
 // row-lazy AdamW over a [rows, width] table (a.p .. a.v, a.n = rows*width): rows whose state byte is 0 (no gradient now,
 // moments still exactly zero) only take the decoupled decay -- bit-identical to the dense update, a quarter of its traffic
 enum { ROW_HAS_GRAD = 1, ROW_HAS_MOMENTS = 2 };
 hipError_t launch_adamw_rows(const AdamWArgs& a, int rows, int width, uint8_t* row_state, hipStream_t s);
+
+// ---------------------------------------------------------------- global-norm gradient clipping (gradnorm.hip)
+// total = grad_scale * sqrt(sum g^2) over the dense segments and over the rows of [rows, width] whose state byte has ROW_HAS_GRAD;
+// coef = min(1, max_norm / (total + 1e-6)).  clip_state: grad_clip_state_bytes() of device memory, 16-byte aligned -- four public words
+// {coef f32, total f32, clipped steps u32, steps u32}, then the partial sums.  Three launches at most (dense partials, row partials, finalize), fixed
+// grids: the bits do not depend on the device.  void_flag (may be null) set on the device: the counters are left alone.
+enum { GRADNORM_MAX_SEGMENTS = 16, GRADNORM_BLOCKS = 512, GRADNORM_ROW_BLOCKS = 512, GRADNORM_UNROLL = 4 };
+struct GradNormSegments {
+    const float* g[GRADNORM_MAX_SEGMENTS]; size_t n[GRADNORM_MAX_SEGMENTS];     // 16-byte aligned starts; n in elements, any value
+    int count;
+};
+size_t grad_clip_state_bytes();
+hipError_t launch_grad_clip(const GradNormSegments& sg, const float* row_g, int rows, int width, const uint8_t* row_state, float max_norm, float grad_scale,
+                            const unsigned* void_flag, void* clip_state, hipStream_t s);
 
 }  // namespace mmhip

@@ -6,6 +6,7 @@ setters and binds (the hooks of EngineModule).
 """
 import ctypes as C
 import json
+import math
 import os
 
 import torch
@@ -163,6 +164,7 @@ class GuardedEngineModule(EngineModule):
 
     _loss_scale = 0.0         # of the f16 gradients (0: the engine's own); the late-fusion trainer moves it
     _word_info = None         # no word table unless WordTableEngineModule finds one: FlatTrainer steps the whole buffer densely
+    _grad_clip = None         # (max_norm, state block) while global-norm gradient clipping is armed (set_grad_clip)
 
     def _on_registered(self):
         # device words of every handle: [0:2] include/mmhip.h mmhip_set_guard {non-finite counter, void-step flag}; [2] the word table's
@@ -174,6 +176,24 @@ class GuardedEngineModule(EngineModule):
         _lib.check(lib.mmhip_set_guard(h, _lib.ptr(self._nonfinite)), "set_guard")
         if self.backward_products is not None:
             _lib.check(lib.mmhip_set_backward_products(h, self.backward_products), "set_backward_products")
+        if self._grad_clip is not None:
+            _lib.check(lib.mmhip_set_grad_clip(h, self._grad_clip[0], _lib.ptr(self._grad_clip[1])), "set_grad_clip")
+
+    def set_grad_clip(self, max_norm):
+        """arm global-norm gradient clipping of the fused steps at `max_norm` (include/mmhip.h mmhip_set_grad_clip), or disarm it with None.  The
+        state block -- four public words {coef, norm, clipped steps, steps}, then the partial sums -- is device memory of the module, like the
+        guard words: every handle is pointed at it."""
+        lib = _lib.lib()
+        if max_norm is None:
+            self._grad_clip = None
+            _lib.check(lib.mmhip_set_grad_clip(self._handle, 0.0, None), "set_grad_clip")
+            return
+        max_norm = float(max_norm)
+        if not math.isfinite(max_norm) or max_norm <= 0.0:
+            raise ValueError(f"max_grad_norm must be a positive finite number, got {max_norm!r}")
+        state = self._grad_clip[1] if self._grad_clip is not None else torch.zeros(int(lib.mmhip_grad_clip_state_bytes()), dtype=torch.uint8, device=self.device_)
+        _lib.check(lib.mmhip_set_grad_clip(self._handle, max_norm, _lib.ptr(state)), "set_grad_clip")
+        self._grad_clip = (max_norm, state)
 
 
 class WordTableEngineModule(GuardedEngineModule):
@@ -234,23 +254,78 @@ class FlatTrainer(object):
                 m._word_row_state.bitwise_and_(1)                  # fresh moments: no row has any yet
         return self._opt
 
+    # ---- global-norm gradient clipping (opt-in: max_grad_norm=None builds nothing and calls nothing new)
+    max_grad_norm = None      # the threshold while armed (set_max_grad_norm)
+
+    @staticmethod
+    def _refuse_grad_clip_under_dp(max_grad_norm, world_size):
+        if max_grad_norm is not None and world_size > 1:
+            raise NotImplementedError(
+                f"max_grad_norm with a gradient exchange (world size {world_size}): the norm needs the whole summed gradient before the first AdamW launch, but under data "
+                "parallelism the word-table rows arrive after the dense optimizer has run, and the sharded optimizer holds only its own shard -- it "
+                "would need a sum of partial norms across ranks.  Data-parallel clipping is not implemented; run one process or drop the flag")
+
+    def set_max_grad_norm(self, max_grad_norm):
+        """arm global-norm gradient clipping of this trainer's steps at `max_grad_norm`, or disarm it with None (the constructors' keyword)"""
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        if max_grad_norm is not None or getattr(self.model, "_grad_clip", None) is not None:
+            self.model.set_grad_clip(self.max_grad_norm)
+
+    def _grad_clip_norm(self, ranges, grad_scale):
+        """staged form of the fused step's norm (include/mmhip.h mmhip_op_grad_clip): over the dense parts of `ranges` and the flagged word-table
+        rows, before the first AdamW call of the step; nothing when clipping is not armed"""
+        m = self.model
+        if getattr(m, "_grad_clip", None) is None:
+            return
+        word = m._word_info
+        w0 = word["offset"] if word is not None else float("inf")
+        dense = [(b, min(e, w0)) for b, e in ranges if min(e, w0) > b]
+        rows = word is not None and any(e > w0 for _, e in ranges)
+        seg_g = (C.c_void_p * max(len(dense), 1))(*[m._flat_grad.data_ptr() + b * 4 for b, _ in dense])
+        seg_n = (C.c_uint64 * max(len(dense), 1))(*[e - b for b, e in dense])
+        V, H = word["shape"] if rows else (0, 4)
+        _lib.check(_lib.lib().mmhip_op_grad_clip(seg_g, seg_n, len(dense), C.c_void_p(m._flat_grad.data_ptr() + w0 * 4) if rows else None, V, H,
+                                                 _lib.ptr(m._word_row_state) if rows else None, m._grad_clip[0], grad_scale, _lib.ptr(m._nonfinite),
+                                                 _lib.ptr(m._grad_clip[1]), _lib.stream_ptr()), "op_grad_clip")
+
+    def grad_clip_stats(self):
+        """{norm, coef, clipped_steps, steps} of the armed clip: the last step's norm (after grad_scale) and coefficient, and the counts since arming.
+        Synchronises: for logs and tests.  None when clipping is not armed."""
+        clip = getattr(self.model, "_grad_clip", None) if self.max_grad_norm is not None else None
+        if clip is None:
+            return None
+        words = clip[1][:16].cpu()
+        f, u = words.view(torch.float32), words.view(torch.int32)
+        return dict(norm=float(f[1]), coef=float(f[0]), clipped_steps=int(u[2]), steps=int(u[3]))
+
+    def _log_grad_clip(self):
+        """train()'s line per epoch -- only when armed"""
+        st = self.grad_clip_stats()
+        if st is not None:
+            print(f"grad clip (max_grad_norm {self.max_grad_norm:g}): last norm {st['norm']:.4g} coef {st['coef']:.4g}, "
+                  f"clipped {st['clipped_steps']} of {st['steps']} steps")
+
     def _adamw_ranges(self, ranges, lr, weight_decay, step, grad_scale, dense=True, rows=True):
-        """staged AdamW: the dense part of each range up to the word table, then the row-lazy word table (no word table: all of it is dense)"""
+        """staged AdamW: the dense part of each range up to the word table, then the row-lazy word table (no word table: all of it is dense).
+        With clipping armed (_grad_clip_norm has run) the calls carry the state block, as the fused step's launches do."""
         m, lib = self.model, _lib.lib()
         em, ev = self._moments()
         at = lambda t, el: C.c_void_p(t.data_ptr() + el * 4)
         word = m._word_info
         w0 = word["offset"] if word is not None else float("inf")    # the word table closes the trainable buffer
+        adamw, adamw_rows, tail = lib.mmhip_adamw_guarded, lib.mmhip_adamw_rows_guarded, ()
+        if getattr(m, "_grad_clip", None) is not None:
+            adamw, adamw_rows, tail = lib.mmhip_adamw_clipped, lib.mmhip_adamw_rows_clipped, (_lib.ptr(m._grad_clip[1]),)
         for b, e in ranges:
             dense_end = min(e, w0)
             if dense and dense_end > b:
-                _lib.check(lib.mmhip_adamw_guarded(at(m._flat_train, b), at(m._flat_grad, b), at(em, b), at(ev, b), dense_end - b, lr, 0.9, 0.999,
-                                                   1e-8, weight_decay, step, grad_scale, 1, _lib.stream_ptr(), _lib.ptr(m._nonfinite)), "adamw")
+                _lib.check(adamw(at(m._flat_train, b), at(m._flat_grad, b), at(em, b), at(ev, b), dense_end - b, lr, 0.9, 0.999,
+                                 1e-8, weight_decay, step, grad_scale, 1, _lib.stream_ptr(), _lib.ptr(m._nonfinite), *tail), "adamw")
             if rows and e > w0:
                 # rows without gradient and without moments only decay: same values as the dense update, 1/4 of its traffic
-                _lib.check(lib.mmhip_adamw_rows_guarded(at(m._flat_train, w0), at(m._flat_grad, w0), at(em, w0), at(ev, w0), *word["shape"],
-                                                        _lib.ptr(m._word_row_state), lr, 0.9, 0.999, 1e-8, weight_decay, step,
-                                                        grad_scale, 1, _lib.stream_ptr(), _lib.ptr(m._nonfinite)), "adamw_rows")
+                _lib.check(adamw_rows(at(m._flat_train, w0), at(m._flat_grad, w0), at(em, w0), at(ev, w0), *word["shape"],
+                                      _lib.ptr(m._word_row_state), lr, 0.9, 0.999, 1e-8, weight_decay, step,
+                                      grad_scale, 1, _lib.stream_ptr(), _lib.ptr(m._nonfinite), *tail), "adamw_rows")
 
     def _clamped_message(self, n):
         raise NotImplementedError

@@ -113,7 +113,8 @@ class ImageModel(OneTowerTrainer):
     _overflow_note = "non-finite gradient element(s) were dropped"
     _eval_line = "test loss: {:.4f} test acc: {:.4f}\n"
 
-    def __init__(self, batch_size, num_labels, model_name, conv_att=False, feature_extract=False, **model_kw):
+    def __init__(self, batch_size, num_labels, model_name, conv_att=False, feature_extract=False, max_grad_norm=None, **model_kw):
+        self._refuse_grad_clip_under_dp(max_grad_norm, mmdist.world_size())
         if model_name != "vit":
             raise NotImplementedError(f"image model {model_name!r}: the image-only path builds `vit` (HF ViTForImageClassification); beit, deit and "
                                       "the resnets are not part of this build")
@@ -128,6 +129,7 @@ class ImageModel(OneTowerTrainer):
         model_kw.setdefault("max_posts", batch_size)
         self.model = ViTClassifier(self.model_dir, num_labels, **model_kw)
         self.device = self.model.device_
+        self.set_max_grad_norm(max_grad_norm)
 
     # ---- data
     def load_data(self, data, img_file_fmt, testing=False, task_name=None):

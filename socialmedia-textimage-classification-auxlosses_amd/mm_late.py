@@ -502,7 +502,8 @@ class MMLate_Model(FlatTrainer):
     the step itself is fused: engine loss + backward + AdamW over flat buffers, gradients all-reduced per backward stage
     when torch.distributed is initialised (one process per GPU, RCCL)."""
 
-    def __init__(self, config, txt_model_name, img_model_name, fusion_name, multilabel=False, **model_kw):
+    def __init__(self, config, txt_model_name, img_model_name, fusion_name, multilabel=False, max_grad_norm=None, **model_kw):
+        self._refuse_grad_clip_under_dp(max_grad_norm, mmdist.world_size())
         if multilabel:
             raise NotImplementedError("multilabel BCE branch: no task enables it in the reference (models/config.py:10)")
         if fusion_name == "aspect-att" and config.use_tim_loss:
@@ -523,6 +524,7 @@ class MMLate_Model(FlatTrainer):
         # MMHIP_DP_OPT=shard: reduce-scatter -> sharded AdamW -> all-gather for the dense ranges instead of all-reduce + replicated AdamW (dist.ShardedBuckets)
         self.sharded_optimizer = os.environ.get("MMHIP_DP_OPT", "allreduce") == "shard"
         self.image_processor = None          # GpuImageProcessor when the loaders yield raw images (datasets.py)
+        self.set_max_grad_norm(max_grad_norm)     # global-norm gradient clipping of the fused step (None: off, nothing built)
 
     # ---- ITM negative sampling, reference :389-414 (same numpy RNG stream: one choice([True, False]) per row and one
     # choice(list(others)) per swapped row; sources are read from the original ids, so swaps do not chain)
@@ -580,6 +582,8 @@ class MMLate_Model(FlatTrainer):
         loss = torch.empty(4, device=self.device)
         ncorr = torch.empty(1, dtype=torch.int32, device=self.device)
         exchange = (self.world > 1 and not mmdist.SKIP_EXCHANGE) or mmdist.force_exchange()
+        if exchange and m._grad_clip is not None:          # (a forced exchange in one process: the constructor's refusal does not see it)
+            self._refuse_grad_clip_under_dp(self.max_grad_norm, max(self.world, 2))
         if not exchange and self.world == 1 and vision_keys is None and os.environ.get("MMHIP_NATIVE_STEP", "1") != "0":
             # single rank: the whole step is one native call (include/mmhip.h: mmhip_train_step) -- the host enqueues ~250
             # kernels from C++ instead of crossing ctypes ~40 times per step
@@ -613,6 +617,8 @@ class MMLate_Model(FlatTrainer):
         for w in works:
             w.wait()
         self._share_guard_flag(exchange)
+        # clipping armed (single process only): the norm over every range and flagged row, before the first AdamW call
+        self._grad_clip_norm(m.active_ranges(self.use_clip_loss, self.use_tim_loss), 1.0 / self.world)
         self._adamw(lr, weight_decay, step, rows=False)        # dense ranges first: the word-table rows are still travelling
         m._refresh_weights(2)                                  # 16-bit GEMM operand copies (no word-table dependence)
         for f in finishers:
@@ -644,6 +650,8 @@ class MMLate_Model(FlatTrainer):
         self._opt = None                             # the moments of the throw-away step are dropped (the next step starts from zeros)
         self._opt_rows = None
         m._word_row_state.zero_()
+        if m._grad_clip is not None:                 # ... nor in the clip's counters
+            m._grad_clip[1].zero_()
         if not torch.equal(before, m._flat_train):   # lr = 0: AdamW must have left every parameter untouched
             m._flat_train.copy_(before)
             m._refresh_weights(2)
@@ -910,6 +918,7 @@ class MMLate_Model(FlatTrainer):
                 if fname is not None and (epoch % 2 == 0 or epoch == epochs - 1) and mmdist.rank() == 0:
                     pd.DataFrame(agg_metrics_val(store, metric_names, self.num_labels)).to_csv(fname, index=False)
                     logger.info("%s saved!", fname)
+            self._log_grad_clip()
         if model_path is not None and mmdist.rank() == 0:
             self.save_model(model_path)
             logger.info("%s saved", model_path)

@@ -196,6 +196,7 @@ class OneTowerTrainer(FlatTrainer):
         m._engine_forward(*self._engine_inputs(*inputs), seed=seed)
         m._native("loss", _lib.ptr(onehot), _lib.ptr(cw), _lib.ptr(loss), _lib.ptr(ncorr), _lib.stream_ptr())
         m._engine_backward(None)
+        self._grad_clip_norm(m.active_ranges(), 1.0)
         self._adamw_ranges(m.active_ranges(), lr, weight_decay, step, 1.0)
         m._grad_dirty = False
         m._refresh_weights()
@@ -237,6 +238,7 @@ class OneTowerTrainer(FlatTrainer):
                 if fname is not None and (epoch % 2 == 0 or epoch == epochs - 1):
                     pd.DataFrame(agg_metrics_val(store, metric_names, self.num_labels)).to_csv(fname, index=False)
                     logger.info("%s saved!", fname)
+            self._log_grad_clip()
         if model_path is not None:
             self.save_model(model_path)
             logger.info("%s saved", model_path)

@@ -1,5 +1,5 @@
 """Command line of the image-only runs -- same flags, defaults, file names and CSV layouts as the reference's models/run_img.py:19-92.
-Additive flags: --synthetic / --n_synthetic (no dataset on disk), --dtype, --batch_size, --results_dir, --arch_layers.  Single process.
+Additive flags: --synthetic / --n_synthetic (no dataset on disk), --dtype, --batch_size, --results_dir, --arch_layers, --max_grad_norm.  Single process.
 `--model_name vit` is what this build trains; beit, deit, the resnets, --conv_att and --feature_extract are refused.
 
     python -m smtc_amd.run_img --model_name vit --task 3 --testing
@@ -48,6 +48,7 @@ def build_parser():
     p.add_argument("--dtype", choices=["bf16", "f16", "bf16x3"], default="bf16", help="bf16x3 = strict-parity mode (fp32 activations, 3 bf16 MFMA products per Linear)")
     p.add_argument("--results_dir", type=str, default=None, help="default ../results/img_only/ as in the reference")
     p.add_argument("--arch_layers", type=int, default=None, help="(testing) override encoder depth")
+    p.add_argument("--max_grad_norm", type=float, default=None, help="clip the gradient to this global L2 norm before AdamW, as torch.nn.utils.clip_grad_norm_ (default: off)")
     return p
 
 
@@ -110,7 +111,7 @@ def main(argv=None):
         args.model_name, args.task, args.feature_extract, args.conv_att, args.epochs, args.seed))
     logger.info("Loading model and data")
     cfg = Config(args, multimodal=False)
-    kw = dict(dtype=args.dtype, seed=args.seed)
+    kw = dict(dtype=args.dtype, seed=args.seed, max_grad_norm=args.max_grad_norm)
     if args.arch_layers:
         kw["arch"] = dict(layers=args.arch_layers)
     image_model = ImageModel(cfg.batch_size, cfg.num_labels, args.model_name, conv_att=args.conv_att, feature_extract=args.feature_extract, **kw)

@@ -1,6 +1,6 @@
 """Command line of the late-fusion runs -- same flags, defaults, file names and CSV layouts as the reference's
 models/run_mm_late.py:20-191.  Additive flags: --batch_size, --synthetic/--n_synthetic (no dataset on disk),
---dtype, --results_dir, --cpu_preprocess, --num_workers, --cache_vision, --itc_global.  Data parallel: launch with `python -m torch.distributed.run --nproc-per-node N ...`.
+--dtype, --results_dir, --cpu_preprocess, --num_workers, --cache_vision, --itc_global, --max_grad_norm (single process).  Data parallel: launch with `python -m torch.distributed.run --nproc-per-node N ...`.
 
     python -m smtc_amd.run_mm_late --txt_model_name bernice --img_model_name vit --fusion_name attention --task 2 --testing
 """
@@ -65,6 +65,7 @@ def build_parser():
     p.add_argument("--dtype", choices=["bf16", "f16", "bf16x3"], default="bf16", help="bf16x3 = strict-parity mode (fp32 activations, 3 bf16 MFMA products per Linear)")
     p.add_argument("--results_dir", type=str, default=None, help="default ../results/mm_late/ as in the reference")
     p.add_argument("--arch_layers", type=int, default=None, help="(testing) override encoder depth")
+    p.add_argument("--max_grad_norm", type=float, default=None, help="clip the gradient to this global L2 norm before AdamW, as torch.nn.utils.clip_grad_norm_ (default: off); single process")
     p.add_argument("--cpu_preprocess", action="store_true", help="resize / normalize images on the host (PIL) instead of the GPU kernels")
     p.add_argument("--num_workers", type=int, default=0, help="DataLoader workers (reference: 0); 8 or more keep the image decode ahead of the GPU step (tools/loader_bench.py)")
     p.add_argument("--item_tokenize", action="store_true", help="tokenise per item like the reference instead of once per batch in the collate")
@@ -124,7 +125,7 @@ def main(argv=None):
         args.txt_model_name, args.img_model_name, args.task, args.fusion_name, args.testing, args.use_clip_loss, args.use_tim_loss,
         args.beta_itc, args.beta_itm, args.nsamples, args.seed))
     cfg = Config(args)
-    kw = dict(dtype=args.dtype, seed=args.seed, itc_global=args.itc_global)
+    kw = dict(dtype=args.dtype, seed=args.seed, itc_global=args.itc_global, max_grad_norm=args.max_grad_norm)
     if args.arch_layers:
         kw["arch"] = dict(layers_txt=args.arch_layers, layers_img=args.arch_layers)
     trainer = MMLate_Model(cfg, args.txt_model_name, args.img_model_name, args.fusion_name, multilabel=cfg.multilabel, **kw)

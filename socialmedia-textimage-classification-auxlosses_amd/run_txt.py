@@ -1,5 +1,5 @@
 """Command line of the text-only runs -- same flags, defaults, file names and CSV layouts as the reference's models/run_txt.py:19-104.
-Additive flags: --synthetic / --n_synthetic (no dataset on disk), --dtype, --batch_size, --results_dir, --arch_layers.  Single process.
+Additive flags: --synthetic / --n_synthetic (no dataset on disk), --dtype, --batch_size, --results_dir, --arch_layers, --max_grad_norm.  Single process.
 
     python -m smtc_amd.run_txt --model_name bernice --task 3 --testing
 """
@@ -48,6 +48,7 @@ def build_parser():
     p.add_argument("--dtype", choices=["bf16", "f16", "bf16x3"], default="bf16", help="bf16x3 = strict-parity mode (fp32 activations, 3 bf16 MFMA products per Linear)")
     p.add_argument("--results_dir", type=str, default=None, help="default ../results/txt_only/ as in the reference")
     p.add_argument("--arch_layers", type=int, default=None, help="(testing) override encoder depth")
+    p.add_argument("--max_grad_norm", type=float, default=None, help="clip the gradient to this global L2 norm before AdamW, as torch.nn.utils.clip_grad_norm_ (default: off)")
     return p
 
 
@@ -106,7 +107,7 @@ def main(argv=None):
     logger.info("Model: {}, Task: {}, Epochs: {}, LC:{}, seed: {}".format(args.model_name, args.task, args.epochs, args.use_loss_correction, args.seed))
     logger.info("Loading model and data")
     cfg = Config(args, multimodal=False, txt=True)
-    kw = dict(dtype=args.dtype, seed=args.seed)
+    kw = dict(dtype=args.dtype, seed=args.seed, max_grad_norm=args.max_grad_norm)
     if args.arch_layers:
         kw["arch"] = dict(layers=args.arch_layers)
     text_model = TextModel(cfg, args.model_name, **kw)

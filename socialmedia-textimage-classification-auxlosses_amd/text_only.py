@@ -135,7 +135,8 @@ class TextModel(OneTowerTrainer):
     _overflow_note = "step(s) were skipped"
     _eval_line = "loss: {:.4f} acc: {:.4f}\n"
 
-    def __init__(self, config, model_name, freeze=False, **model_kw):
+    def __init__(self, config, model_name, freeze=False, max_grad_norm=None, **model_kw):
+        self._refuse_grad_clip_under_dp(max_grad_norm, mmdist.world_size())
         if freeze:
             raise NotImplementedError("freeze=True: the reference's command line never passes it (models/run_txt.py:51); the HIP step trains the encoder")
         if getattr(config, "use_loss_correction", False):
@@ -160,6 +161,7 @@ class TextModel(OneTowerTrainer):
         self.model = cls(self.model_dir, self.num_labels, dropout=self.dropout, **model_kw)
         self.with_types = model_name not in {"roberta", "bernice"}
         self.device = self.model.device_
+        self.set_max_grad_norm(max_grad_norm)
 
     # ---- data
     def load_data(self, data, testing=False, eval_txt_test=False, task_name=None):
